@@ -19,7 +19,21 @@ one rank.  Without one, `--gpus N` with N > 1 starts the N ranks itself (a child
 `torch.distributed.run` on 127.0.0.1, started before this process touches the
 GPU) and exits non-zero when fewer than N devices are visible.
 
-Prints ONE JSON line (rank 0).  Besides the contract keys it carries
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K sweeps
+and prints the contract keys (metric, value, unit, higher_is_better, dtype,
+ms_per_step) with the run's config and acceptance, nothing else.
+
+    --dump-outputs DIR   after the timed sweeps, write what they computed (the state a
+                         caller of Engine.mh_sweeps reads back) as DIR/<name>.npy, float64:
+                         params (H,W,3), dlog (H,W, the last sweep's log acceptance ratios),
+                         accepted (1,), residual_sample (a fixed sample of the carried
+                         residual, see dump_outputs).  Inputs are seeded: the same arguments
+                         give the same inputs in every run.
+    --full               also measure everything below (own runs, CPU baselines, N > 1's
+                         config-4 leg); --no-cpu / --no-extras / --no-deep /
+                         --no-conv-beyond-mall / --conv-iters trim what --full adds.
+
+With --full the line also carries
   roofline             -- the MH sweep kernel (k_mh_ws): algorithmic bytes / launch time
   roofline_beyond_mall -- the same kernel on a 300x300x256 cube, whose residual +
                           1/variance (369 MB) exceed the 256 MB Infinity Cache
@@ -490,6 +504,32 @@ def conv_beyond_mall_leg(args, local_rank, fs):
     return out
 
 
+DUMP_RESIDUAL_VOXELS = 1 << 20      # 8 MB of the carried residual at most
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, eng, accepted):
+    """--dump-outputs: the state the timed sweeps leave behind, read back as a caller of
+    Engine.mh_sweeps would (parameters, last sweep's log ratios, accepted count), plus the
+    carried residual (SLOT_ERR, pending layers flushed first) as a fixed sample: the voxels
+    of the flattened (D,H,W) cube at the sorted indices default_rng(0).choice(D*H*W,
+    2^20, replace=False), or the whole cube when it has at most 2^20 voxels.  About 11 MB
+    at config 3."""
+    from deconv3d_amd import _lib
+    err = eng.download_slot(_lib.SLOT_ERR).reshape(-1)
+    if err.size > DUMP_RESIDUAL_VOXELS:
+        idx = np.sort(np.random.default_rng(0).choice(err.size, DUMP_RESIDUAL_VOXELS, replace=False))
+        err = err[idx]
+    arrays = {"params": eng.get_params(), "dlog": eng.get_dlog(),
+              "accepted": np.array([accepted], dtype=np.float64), "residual_sample": err}
+    total = sum(a.size * 8 for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -523,11 +563,24 @@ def main():
     ap.add_argument("--only-conv-beyond-mall", action="store_true",
                     help="run only the 600x600x128 convolution leg and print its record "
                          "(tools/profile_round.sh: its counters are taken in a run of their own)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed sweeps, measure the rooflines, extra legs, CPU baselines "
+                         "and (N > 1) the config-4 leg; a plain run measures the contract line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed sweeps, write their outputs as DIR/<name>.npy (float64)")
     ap.add_argument("--wait-stdin", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.mode == "tiled" or args.only_conv_beyond_mall):
+        raise SystemExit("--dump-outputs: the ensemble mode's sweeps only")
+    if not args.full:
+        # a plain run: set-up, warm-up, the K timed sweeps, their outputs, the contract line
+        args.no_cpu = True
+        args.no_extras = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args))
     rank = int(os.environ.get("RANK", "0"))
@@ -545,7 +598,7 @@ def main():
         # rank 0's CPU baselines and the extra legs belong to the N = 1 line only
         args.no_cpu = True
         args.no_extras = True
-        if (args.mode == "ensemble" and not args.dry_run and not args.no_tiled_leg
+        if (args.full and args.mode == "ensemble" and not args.dry_run and not args.no_tiled_leg
                 and os.environ.get("D3D_BENCH_TILED_LEG", "1") != "0"):
             try:
                 leg = start_tiled_leg(args, rank)
@@ -644,109 +697,113 @@ def main():
     total_updates = args.steps * n_spaxels * world
     value = total_updates / dt
 
-    # ---- roofline of the dominant kernel (k_mh, one launch per colour) --------
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, accepted)
+
     fh, fw = fsf.shape
-    ncol = sum(1 for c in range(fh * fw) if eng.colour_count(c) > 0)
-    bytes_per_sweep = 3 * 8 * D * window_voxels(H, W, fh, fw)     # read err, read 1/var, write err
-    launches = ncol * args.steps
-    avg_launch_us = dev_ms * 1e3 / launches
-    achieved = bytes_per_sweep / ncol / (avg_launch_us * 1e-6) / 1e9
-    small = eng.get_option("small_parts") > 0       # launches that do not fill the chip: k_mh_small
-    roofline = {"kernel": ("k_mh_small" if small else "k_mh_ws") + " (one launch per colour class)", "bound": "hbm",
-                "achieved": round(achieved, 1),
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                "traffic": measured_traffic("k_mh_ws<256, false, 2, 2, 2,", args.workload, "false, false, false>"),
-                "bytes_per_launch": bytes_per_sweep // ncol,
-                "avg_launch_us": round(avg_launch_us, 2), "launches": launches,
-                # `achieved` prices the 24 B per window voxel of SURVEY 8(d) (read residual,
-                # read 1/var, write residual); the kernel itself stores the residual only
-                # every `residual_written_every` colours and applies the pending updates
-                # in registers in between, which is why `traffic` is lower
-                "residual_written_every": eng.mh_layers()}
-    # HBM bytes the counters saw per launch / the same launch time (the
-    # kernel moves fewer bytes than the algorithmic 24 B per window voxel)
-    traffic_rates(roofline, avg_launch_us)
-
-    # ---- separable convolution roofline (north_star's second target) ---------
-    # cube in -> cube out, device resident.  (a) in the reference's own (D,H,W)
-    # layout (d3d_stage_convolve: what d3d_convolve runs between its upload and
-    # download), (b) between two spectrum-contiguous slots (the layout of the MH
-    # loop, used by the forward model / residual refresh).
-    conv_bytes = 2 * 8 * D * H * W                                # cube in -> cube out
     ntaps_lsf = kept_lsf_taps(lsf)
-    conv_flops = 2.0 * (fh * fw + ntaps_lsf) * D * H * W
+    if args.full:
+        # ---- roofline of the dominant kernel (k_mh, one launch per colour) --------
+        ncol = sum(1 for c in range(fh * fw) if eng.colour_count(c) > 0)
+        bytes_per_sweep = 3 * 8 * D * window_voxels(H, W, fh, fw)     # read err, read 1/var, write err
+        launches = ncol * args.steps
+        avg_launch_us = dev_ms * 1e3 / launches
+        achieved = bytes_per_sweep / ncol / (avg_launch_us * 1e-6) / 1e9
+        small = eng.get_option("small_parts") > 0       # launches that do not fill the chip: k_mh_small
+        roofline = {"kernel": ("k_mh_small" if small else "k_mh_ws") + " (one launch per colour class)", "bound": "hbm",
+                    "achieved": round(achieved, 1),
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                    "traffic": measured_traffic("k_mh_ws<256, false, 2, 2, 2,", args.workload, "false, false, false>"),
+                    "bytes_per_launch": bytes_per_sweep // ncol,
+                    "avg_launch_us": round(avg_launch_us, 2), "launches": launches,
+                    # `achieved` prices the 24 B per window voxel of SURVEY 8(d) (read residual,
+                    # read 1/var, write residual); the kernel itself stores the residual only
+                    # every `residual_written_every` colours and applies the pending updates
+                    # in registers in between, which is why `traffic` is lower
+                    "residual_written_every": eng.mh_layers()}
+        # HBM bytes the counters saw per launch / the same launch time (the
+        # kernel moves fewer bytes than the algorithmic 24 B per window voxel)
+        traffic_rates(roofline, avg_launch_us)
 
-    def conv_entry(ms, kernel, traffic_key, flops=conv_flops, instr=None):
-        gbs = conv_bytes / (ms * 1e-3) / 1e9
-        e = {"kernel": kernel, "bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
-                "traffic": measured_traffic(traffic_key, args.workload),
-                "ms_per_conv": round(ms, 4)}
-        fp64_rates(e, flops, ms, (D, H, W) if instr else None, instr, fh)
-        return e
+        # ---- separable convolution roofline (north_star's second target) ---------
+        # cube in -> cube out, device resident.  (a) in the reference's own (D,H,W)
+        # layout (d3d_stage_convolve: what d3d_convolve runs between its upload and
+        # download), (b) between two spectrum-contiguous slots (the layout of the MH
+        # loop, used by the forward model / residual refresh).
+        conv_bytes = 2 * 8 * D * H * W                                # cube in -> cube out
+        conv_flops = 2.0 * (fh * fw + ntaps_lsf) * D * H * W
 
-    eng.stage_upload(data)
-    eng.stage_convolve()                                          # warm
-    eng.sync()
-    eng.timer_start()
-    for _ in range(args.conv_iters):
-        eng.stage_convolve()
-    stage_ms = eng.timer_stop() / max(args.conv_iters, 1)
-    eng.convolve_slots(_lib.SLOT_DATA, _lib.SLOT_SIM)             # warm
-    eng.sync()
-    eng.timer_start()
-    for _ in range(args.conv_iters):
-        eng.convolve_slots(_lib.SLOT_DATA, _lib.SLOT_SIM)
-    slots_ms = eng.timer_stop() / max(args.conv_iters, 1)
-    # (136 / 68 fp64 instructions per z-pair and march step: radial / outer-product FSF + 17-tap
-    # LSF epilogue at 128 channels, csrc/d3d_conv.h; other shapes: no issued figure)
-    at128 = D == 128 and fh == 11
-    roofline_conv = conv_entry(slots_ms, "k_conv_rows (LSF x FSF in one pass, slot layout)",
-                               "k_conv_rows<11, 15, true, true, false, 1,",
-                               instr=136 if at128 else None)
-    roofline_conv["algorithmic_bytes"] = conv_bytes
-    roofline_conv_ref_layout = conv_entry(stage_ms, "k_spectral_z + k_spatial_z (reference layout)",
-                                          "k_spatial_z")
+        def conv_entry(ms, kernel, traffic_key, flops=conv_flops, instr=None):
+            gbs = conv_bytes / (ms * 1e-3) / 1e9
+            e = {"kernel": kernel, "bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
+                    "traffic": measured_traffic(traffic_key, args.workload),
+                    "ms_per_conv": round(ms, 4)}
+            fp64_rates(e, flops, ms, (D, H, W) if instr else None, instr, fh)
+            return e
 
-    # ---- the other two things north_star names, priced with SURVEY 8(d)'s bytes ----
-    # forward model (lib/run.py:1011-1029): parameters -> convolved cube = k_lines (raw lines,
-    # one exp per voxel) + k_conv_rows (FSF, LSF in its epilogue): H W 3 8 + D H W 8 algorithmic
-    # bytes; the 92 MB line cube between the two launches is traffic, not algorithm.
-    # chi2 map (lib/run.py:423-424): 0.5 sum_z err^2 / var per spaxel from the CARRIED residual
-    # and 1/var (2 D H W 8 + H W 8 bytes; SURVEY's 276.5 MB is the three-cube form data, sim, var).
-    eng.forward(fetch=False)
-    eng.sync()
-    eng.timer_start()
-    for _ in range(args.conv_iters):
+        eng.stage_upload(data)
+        eng.stage_convolve()                                          # warm
+        eng.sync()
+        eng.timer_start()
+        for _ in range(args.conv_iters):
+            eng.stage_convolve()
+        stage_ms = eng.timer_stop() / max(args.conv_iters, 1)
+        eng.convolve_slots(_lib.SLOT_DATA, _lib.SLOT_SIM)             # warm
+        eng.sync()
+        eng.timer_start()
+        for _ in range(args.conv_iters):
+            eng.convolve_slots(_lib.SLOT_DATA, _lib.SLOT_SIM)
+        slots_ms = eng.timer_stop() / max(args.conv_iters, 1)
+        # (136 / 68 fp64 instructions per z-pair and march step: radial / outer-product FSF + 17-tap
+        # LSF epilogue at 128 channels, csrc/d3d_conv.h; other shapes: no issued figure)
+        at128 = D == 128 and fh == 11
+        roofline_conv = conv_entry(slots_ms, "k_conv_rows (LSF x FSF in one pass, slot layout)",
+                                   "k_conv_rows<11, 15, true, true, false, 1,",
+                                   instr=136 if at128 else None)
+        roofline_conv["algorithmic_bytes"] = conv_bytes
+        roofline_conv_ref_layout = conv_entry(stage_ms, "k_spectral_z + k_spatial_z (reference layout)",
+                                              "k_spatial_z")
+
+        # ---- the other two things north_star names, priced with SURVEY 8(d)'s bytes ----
+        # forward model (lib/run.py:1011-1029): parameters -> convolved cube = k_lines (raw lines,
+        # one exp per voxel) + k_conv_rows (FSF, LSF in its epilogue): H W 3 8 + D H W 8 algorithmic
+        # bytes; the 92 MB line cube between the two launches is traffic, not algorithm.
+        # chi2 map (lib/run.py:423-424): 0.5 sum_z err^2 / var per spaxel from the CARRIED residual
+        # and 1/var (2 D H W 8 + H W 8 bytes; SURVEY's 276.5 MB is the three-cube form data, sim, var).
         eng.forward(fetch=False)
-    fwd_ms = eng.timer_stop() / max(args.conv_iters, 1)
-    fwd_bytes = H * W * 3 * 8 + D * H * W * 8
-    fwd_gbs = fwd_bytes / (fwd_ms * 1e-3) / 1e9
-    roofline_forward = {"kernel": "k_lines + k_conv_rows (parameters -> convolved cube, two launches)",
-                        "bound": "hbm", "achieved": round(fwd_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round(fwd_gbs / HBM_PEAK_GBS, 4), "algorithmic_bytes": fwd_bytes,
-                        "ms_per_forward": round(fwd_ms, 4),
-                        "ms_line_build": round(fwd_ms - slots_ms, 4)}
-    # (both launches' counter bytes: the 92 MB line cube is written by one and read by the other)
-    t_lines = measured_traffic("k_lines<256>", args.workload)
-    t_conv = measured_traffic("k_conv_rows<11, 15, true, true, false, 1,", args.workload)
-    roofline_forward["traffic"] = (t_lines + t_conv) if isinstance(t_lines, int) and isinstance(t_conv, int) \
-        else ("stale" if "stale" in (t_lines, t_conv) else None)
-    traffic_rates(roofline_forward, fwd_ms * 1e3)
-    eng.chi2_map(fetch=False)
-    eng.sync()
-    eng.timer_start()
-    for _ in range(args.conv_iters):
+        eng.sync()
+        eng.timer_start()
+        for _ in range(args.conv_iters):
+            eng.forward(fetch=False)
+        fwd_ms = eng.timer_stop() / max(args.conv_iters, 1)
+        fwd_bytes = H * W * 3 * 8 + D * H * W * 8
+        fwd_gbs = fwd_bytes / (fwd_ms * 1e-3) / 1e9
+        roofline_forward = {"kernel": "k_lines + k_conv_rows (parameters -> convolved cube, two launches)",
+                            "bound": "hbm", "achieved": round(fwd_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "frac": round(fwd_gbs / HBM_PEAK_GBS, 4), "algorithmic_bytes": fwd_bytes,
+                            "ms_per_forward": round(fwd_ms, 4),
+                            "ms_line_build": round(fwd_ms - slots_ms, 4)}
+        # (both launches' counter bytes: the 92 MB line cube is written by one and read by the other)
+        t_lines = measured_traffic("k_lines<256>", args.workload)
+        t_conv = measured_traffic("k_conv_rows<11, 15, true, true, false, 1,", args.workload)
+        roofline_forward["traffic"] = (t_lines + t_conv) if isinstance(t_lines, int) and isinstance(t_conv, int) \
+            else ("stale" if "stale" in (t_lines, t_conv) else None)
+        traffic_rates(roofline_forward, fwd_ms * 1e3)
         eng.chi2_map(fetch=False)
-    chi_ms = eng.timer_stop() / max(args.conv_iters, 1)
-    chi_bytes = 2 * D * H * W * 8 + H * W * 8
-    chi_gbs = chi_bytes / (chi_ms * 1e-3) / 1e9
-    roofline_chi2 = {"kernel": "k_chi2_map (carried residual, 1/var -> per-spaxel 0.5 chi2)", "bound": "hbm",
-                     "achieved": round(chi_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(chi_gbs / HBM_PEAK_GBS, 4), "algorithmic_bytes": chi_bytes,
-                     "us_per_map": round(chi_ms * 1e3, 2),
-                     "traffic": measured_traffic("k_chi2_map", args.workload)}
-    traffic_rates(roofline_chi2, chi_ms * 1e3)
+        eng.sync()
+        eng.timer_start()
+        for _ in range(args.conv_iters):
+            eng.chi2_map(fetch=False)
+        chi_ms = eng.timer_stop() / max(args.conv_iters, 1)
+        chi_bytes = 2 * D * H * W * 8 + H * W * 8
+        chi_gbs = chi_bytes / (chi_ms * 1e-3) / 1e9
+        roofline_chi2 = {"kernel": "k_chi2_map (carried residual, 1/var -> per-spaxel 0.5 chi2)", "bound": "hbm",
+                         "achieved": round(chi_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": round(chi_gbs / HBM_PEAK_GBS, 4), "algorithmic_bytes": chi_bytes,
+                         "us_per_map": round(chi_ms * 1e3, 2),
+                         "traffic": measured_traffic("k_chi2_map", args.workload)}
+        traffic_rates(roofline_chi2, chi_ms * 1e3)
 
     out = {
         "metric": "spaxel-updates/sec (MH-Gibbs)",
@@ -770,12 +827,15 @@ def main():
                    "parallelism": "1 chain" if world == 1 else "ensemble of %d chains" % world,
                    "variance": "per-voxel cube (heteroscedastic)"},
         "acceptance": round(accepted / float(args.steps * n_spaxels), 4),
-        "roofline": roofline,
-        "roofline_conv": roofline_conv,
-        "roofline_conv_ref_layout": roofline_conv_ref_layout,
-        "roofline_forward": roofline_forward,
-        "roofline_chi2": roofline_chi2,
     }
+    if args.full:
+        out.update({
+            "roofline": roofline,
+            "roofline_conv": roofline_conv,
+            "roofline_conv_ref_layout": roofline_conv_ref_layout,
+            "roofline_forward": roofline_forward,
+            "roofline_chi2": roofline_chi2,
+        })
 
     if rank == 0 and not args.no_extras:
         # PCIe-inclusive: the same sweeps with EVERY sweep streamed to a host chain
@@ -796,7 +856,7 @@ def main():
             "note": "same kernel path as `value`, every sweep copied to the host chain"}
         sweep += ks
         del chain, dlog
-    if rank == 0:
+    if rank == 0 and args.full:
         out["host"] = host_info()
     if rank == 0 and not args.no_extras and args.workload == "c3_300x300x128":
         out["roofline_beyond_mall"] = beyond_mall_leg(args, local_rank, fs)

@@ -21,6 +21,9 @@ Fixtures
                        FSF, theoretical parameters (c already 0-based)
   ref_galpak_pair.npz  the reference's saved convolved/deconvolved cube pair
                        (tests/input/GalPaK_*_myrun100k_*.fits)
+  ref_galpak_cube.fits the reference's input cube, copied byte for byte
+                       (tests/input/GalPaK_cube_1101_..._seeing1.0_PAm50.fits):
+                       the FITS reader's fixture, header cards included
   oracle_*.npz         oracle outputs on the seeded parity cases (regression
                        pins + the vectors the GPU tests compare against)
 """
@@ -128,6 +131,13 @@ def ref_galpak_pair():
     np.savez_compressed(os.path.join(HERE, "ref_galpak_pair.npz"), convolved=conv, clean=clean)
 
 
+def ref_galpak_cube():
+    import shutil
+    shutil.copyfile(os.path.join(REF, "tests/input/GalPaK_cube_1101_size4.08_flux1e-16_incl60_vmax199_"
+                                      "disp80_seeing1.0_PAm50.fits"),
+                    os.path.join(HERE, "ref_galpak_cube.fits"))
+
+
 def oracle_cases():
     for name in ("c1", "odd_depth", "asym"):
         case = make_case(name)
@@ -171,7 +181,8 @@ if __name__ == "__main__":
     ref_rtnorm()
     ref_mat_fixture()
     ref_galpak_pair()
+    ref_galpak_cube()
     oracle_cases()
     for f in sorted(os.listdir(HERE)):
-        if f.endswith(".npz"):
+        if f.endswith((".npz", ".fits")):
             print("%-28s %8d bytes" % (f, os.path.getsize(os.path.join(HERE, f))))

@@ -138,3 +138,54 @@ def test_window_probe_matches_oracle_on_full_cube(problem):
         np.testing.assert_allclose(got[:3], ref[:3], rtol=1e-10, atol=1e-12 * max(ref[0], ref[1]))
         np.testing.assert_allclose(got[3:], ref[3:], rtol=1e-10,
                                    atol=1e-12 * max(abs(ref[3]), abs(ref[4])))
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run measures the contract line only, and `--dump-outputs` writes what
+    its timed sweeps computed: the same arrays in two runs, and the parameters, log ratios and
+    accepted count of the same seeded chain run here through the Engine."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench as B
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    recs = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3",
+                            "--warmup", "2", "--dump-outputs", str(tmp_path / d)],
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        recs.append(json.loads(lines[0]))
+    rec = recs[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in rec, key
+    assert rec["steps"] == 3 and rec["warmup"] == 2 and rec["ms_per_step"] > 0 and rec["value"] > 0
+    assert not [k for k in rec if k.startswith(("roofline", "cpu_baseline", "chain")) or k == "host"], rec
+    assert recs[1]["acceptance"] == rec["acceptance"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["accepted.npy", "dlog.npy", "params.npy", "residual_sample.npy"]
+    out = {}
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float64
+        np.testing.assert_array_equal(a, b)
+        out[name[:-4]] = a
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    assert out["residual_sample"].shape == (B.DUMP_RESIDUAL_VOXELS,)
+    fsf, lsf = B.build_taps(D, 11)
+    with _lib.Engine((D, H, W), fsf.shape) as eng:
+        eng.set_taps(fsf, lsf)
+        data, var, truth, init, min_b, max_b = B.synthetic_inputs(eng, D, H, W, fsf, 12345)
+        eng.set_data(data, var, mask=np.ones((H, W)))
+        eng.set_params(init)
+        eng.mh_config(min_b, max_b, 0.1, float(max_b[0] ** 2), seed=12345, refresh_every=1000)
+        eng.residual(fetch=False)
+        eng.mh_sweeps(2, 1)
+        accepted = eng.mh_sweeps(3, 3)
+        np.testing.assert_array_equal(out["params"], eng.get_params())
+        np.testing.assert_array_equal(out["dlog"], eng.get_dlog())
+    assert out["accepted"][0] == accepted

@@ -328,7 +328,7 @@ def test_two_gloo_ranks_on_one_gpu_are_bit_identical(tmp_path):
 
 
 def test_bench_two_ranks_report_the_tiled_leg():
-    """`bench.py --gpus 2` (no launcher; gloo, both ranks on this one GPU): the contract line
+    """`bench.py --gpus 2 --full` (no launcher; gloo, both ranks on this one GPU): the contract line
     is the ensemble's, and the config-4 leg -- one chain tiled over the same ranks, run by
     child processes the ranks started before touching the GPU -- arrives as
     `config4_tiled`; rank 0's CPU baselines stay out of an N > 1 line."""
@@ -340,7 +340,7 @@ def test_bench_two_ranks_report_the_tiled_leg():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
                         "--backend", "gloo", "--workload", "c2_64x64x64", "--steps", "2",
-                        "--warmup", "1", "--conv-iters", "2"], env=env, capture_output=True,
+                        "--warmup", "1", "--conv-iters", "2", "--full"], env=env, capture_output=True,
                        text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

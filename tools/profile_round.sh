@@ -10,7 +10,7 @@ TAG=${1:-r01}
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-CMD="bench.py --steps 5 --warmup 1 --no-cpu --conv-iters 10 --no-conv-beyond-mall"
+CMD="bench.py --full --steps 5 --warmup 1 --no-cpu --conv-iters 10 --no-conv-beyond-mall"
 python $CMD > $OUT/bench_plain.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o trace -- python $CMD > $OUT/bench_traced.json 2> $OUT/trace.log
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT -o fetch -- python $CMD > /dev/null 2> $OUT/fetch.log
@@ -29,7 +29,7 @@ python tools/summarize_profile.py $O2 $TAG conv_600x600x128 _conv600 "python $C2
 # ---- config 2's cube: the small colour launches (k_mh_small), kernel trace + stats
 O3=$OUT/c2
 mkdir -p $O3
-C3="bench.py --workload c2_64x64x64 --steps 20 --warmup 2 --no-cpu --no-extras --conv-iters 5"
+C3="bench.py --full --workload c2_64x64x64 --steps 20 --warmup 2 --no-cpu --no-extras --conv-iters 5"
 python $C3 > $O3/bench_plain.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $O3 -o trace -- python $C3 > $O3/bench_traced.json 2> $O3/trace.log
 python tools/summarize_profile.py $O3 $TAG c2_64x64x64 _c2 "python $C3"

@@ -9,7 +9,7 @@ import sys
 src, tag = sys.argv[1], sys.argv[2]
 workload = sys.argv[3] if len(sys.argv) > 3 else "c3_300x300x128"
 suffix = sys.argv[4] if len(sys.argv) > 4 else ""
-command = sys.argv[5] if len(sys.argv) > 5 else ("python bench.py --steps 5 --warmup 1 --no-cpu --conv-iters 10 "
+command = sys.argv[5] if len(sys.argv) > 5 else ("python bench.py --full --steps 5 --warmup 1 --no-cpu --conv-iters 10 "
                                                  "--no-conv-beyond-mall")
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 dst = os.path.join(root, "profiles")
