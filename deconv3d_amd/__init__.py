@@ -6,7 +6,7 @@ reference's own ``Run / Instrument / SpreadFunction / LineModel`` API
 """
 from .cube import Axis, Cube, HyperspectralCube  # noqa: F401
 from .instruments import MUSE, Instrument  # noqa: F401
-from .line_models import LineModel, SingleGaussianLineModel  # noqa: F401
+from .line_models import GaussianMultipletLineModel, LineModel, SingleGaussianLineModel  # noqa: F401
 from .masks import above_percentile  # noqa: F401
 from .math_utils import median_clip  # noqa: F401
 from .run import Run, logger  # noqa: F401

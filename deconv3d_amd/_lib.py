@@ -23,7 +23,7 @@ SYMBOLS = [
     "d3d_ctx_create", "d3d_ctx_destroy", "d3d_ctx_set_stream", "d3d_sync",
     "d3d_ctx_set_option", "d3d_ctx_get_option", "d3d_has_experiments",
     "d3d_timer_start", "d3d_timer_stop",
-    "d3d_set_taps", "d3d_set_data", "d3d_set_params", "d3d_get_params",
+    "d3d_set_taps", "d3d_set_data", "d3d_set_params", "d3d_get_params", "d3d_set_line_shape",
     "d3d_build_clean", "d3d_convolve", "d3d_forward", "d3d_simulate", "d3d_residual",
     "d3d_chi2_map", "d3d_upload_slot", "d3d_download_slot",
     "d3d_convolve_slots", "d3d_stage_upload", "d3d_stage_convolve", "d3d_stage_download",
@@ -92,6 +92,7 @@ def load():
                                  C.POINTER(C.c_uint8)]
     lib.d3d_set_params.argtypes = [ctx_p, dbl_p]
     lib.d3d_get_params.argtypes = [ctx_p, dbl_p]
+    lib.d3d_set_line_shape.argtypes = [ctx_p, C.c_int, dbl_p, dbl_p]
     lib.d3d_build_clean.argtypes = [ctx_p, dbl_p]
     lib.d3d_convolve.argtypes = [ctx_p, dbl_p, dbl_p]
     lib.d3d_forward.argtypes = [ctx_p, dbl_p]
@@ -321,6 +322,18 @@ class Engine(object):
     def set_params(self, params):
         params = _c64(params, self.shape[1:] + (3,))
         _check(self._lib.d3d_set_params(self._ctx, _dp(params)))
+
+    def set_line_shape(self, offsets, ratios):
+        """Unit line of the kernels (include/deconv3d_hip.h: d3d_set_line_shape): 1 to 4
+        Gaussians at channel ``offsets`` from the centre with flux ``ratios`` relative to the
+        first (offsets[0] == 0, ratios[0] == 1).  Default: one Gaussian, ([0], [1])."""
+        off = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1)
+        rat = np.ascontiguousarray(ratios, dtype=np.float64).reshape(-1)
+        if off.size != rat.size:
+            raise ValueError("line shape: %d offsets but %d ratios" % (off.size, rat.size))
+        if off.size == 0:
+            raise ValueError("a line shape has 1 to 4 components, got 0")
+        _check(self._lib.d3d_set_line_shape(self._ctx, int(off.size), _dp(off), _dp(rat)))
 
     def get_params(self):
         out = np.empty(self.shape[1:] + (3,), dtype=np.float64)

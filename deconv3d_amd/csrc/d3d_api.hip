@@ -1032,6 +1032,36 @@ int d3d_set_params(d3d_ctx *c, const double *params) {
     return D3D_OK;
 }
 
+int d3d_set_line_shape(d3d_ctx *c, int K, const double *offsets, const double *ratios) {
+    NEED(c && offsets && ratios, D3D_ERR_INVALID, "NULL argument");
+    NEED(K >= 1 && K <= d3d::LINE_KMAX, D3D_ERR_INVALID, "a line shape has 1 to %d components, got %d",
+         d3d::LINE_KMAX, K);
+    for (int k = 0; k < K; ++k)
+        NEED(std::isfinite(offsets[k]) && std::isfinite(ratios[k]), D3D_ERR_INVALID,
+             "line shape: offsets and ratios must be finite (component %d)", k);
+    NEED(offsets[0] == 0.0 && ratios[0] == 1.0, D3D_ERR_INVALID,
+         "line shape: offsets[0] must be 0 and ratios[0] must be 1 (c and a are the first line's)");
+    for (int k = 0; k < K; ++k) {
+        NEED(ratios[k] >= 0.0, D3D_ERR_INVALID, "line shape: ratios must be >= 0 (component %d)", k);
+        for (int j = 0; j < k; ++j)
+            NEED(offsets[j] != offsets[k], D3D_ERR_INVALID,
+                 "line shape: offsets must be distinct (components %d and %d)", j, k);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    // the pending updates were made with the old line: written back with it, then everything
+    // built from the line -- the residual, the sweep's proposal and line tables -- is stale
+    if (int rc = flush_pending(c)) return rc;
+    d3d::LineShape L = {K, {0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+    for (int k = 0; k < K; ++k) {
+        L.off[k] = offsets[k];
+        L.ratio[k] = ratios[k];
+    }
+    c->line = L;
+    c->err_valid = false;
+    c->props_sweep = -1;
+    return D3D_OK;
+}
+
 int d3d_get_params(d3d_ctx *c, double *params) {
     NEED(c && params, D3D_ERR_INVALID, "NULL argument");
     NEED(c->have_params, D3D_ERR_STATE, "parameters not set");
@@ -1589,6 +1619,11 @@ int d3d_mh_sweeps_batch(d3d_ctx **ctxs, int n_ctx, int n_sweeps, int first_sweep
              D3D_ERR_INVALID, "ctx %d: uniform and per-voxel variances cannot share a launch", r);
         NEED(c->mh_zigzag == L->mh_zigzag && c->sweep_origin == L->sweep_origin, D3D_ERR_INVALID,
              "ctx %d: another walk order or sweep origin than ctx 0", r);
+        bool same_line = c->line.K == L->line.K;
+        for (int k = 0; k < d3d::LINE_KMAX; ++k)
+            same_line = same_line && c->line.off[k] == L->line.off[k] && c->line.ratio[k] == L->line.ratio[k];
+        NEED(same_line, D3D_ERR_INVALID,
+             "ctx %d: another line shape than ctx 0 (the chains share the launch's arguments)", r);
         // (the chains share the leader's pending-layer state, and a from-scratch residual
         // clears a chain's own: they must all be rebuilt at the same sweeps)
         NEED(c->refresh_every == L->refresh_every, D3D_ERR_INVALID,

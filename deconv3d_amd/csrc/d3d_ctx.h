@@ -134,6 +134,7 @@ struct d3d_ctx {
     long halo_count = 0;
     std::vector<uint8_t> h_mask;
 
+    d3d::LineShape line = {1, {0.0, 0.0, 0.0, 0.0}, {1.0, 0.0, 0.0, 0.0}};  // d3d_set_line_shape
     bool have_taps = false, have_data = false, have_params = false, have_cfg = false;
     bool err_valid = false;
     double min_b[3] = {}, max_b[3] = {}, amp[3] = {};

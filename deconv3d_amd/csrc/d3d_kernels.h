@@ -96,11 +96,45 @@ __device__ __forceinline__ double unit_gaussian(double z, double c, double w) {
     return (w2 > 0.0) ? exp(-(d * d) / w2) : ((d == 0.0) ? 1.0 : 0.0);
 }
 
+// The unit line of the line model (d3d_set_line_shape): K Gaussians of one centre and width
+// at channel offsets off[k] from c with flux ratios ratio[k] relative to the first
+// (off[0] == 0, ratio[0] == 1) -- GaussianMultipletLineModel, deconv3d_amd/line_models.py.
+// K == 1 is SingleGaussianLineModel.
+constexpr int LINE_KMAX = 4;
+struct LineShape {
+    int K;
+    double off[LINE_KMAX];
+    double ratio[LINE_KMAX];
+};
+
+// The unit line at channel z.  MULTI = false (the instantiation every kernel runs for K == 1):
+// unit_gaussian itself, the shape unread -- that kernel is the single Gaussian's code, bit for bit
+// and register for register.  MULTI = true (K > 1): sum_k ratio[k] g_k in component order with g_k
+// from d = (z - c) - off[k] -- the order of GaussianMultipletLineModel.modelize -- and
+// unit_gaussian's delta rule for w == 0 per component.
+template <bool MULTI>
+__device__ __forceinline__ double unit_line(const LineShape &L, double z, double c, double w) {
+    if constexpr (!MULTI) return unit_gaussian(z, c, w);
+    const double w2 = 2.0 * w * w;
+    double s = 0.0;
+    // (constant indices: the shape stays in scalar registers of the kernarg segment)
+#pragma unroll
+    for (int k = 0; k < LINE_KMAX; ++k) {
+        if (k < L.K) {
+            const double d = (z - c) - L.off[k];
+            const double g = (w2 > 0.0) ? exp(-(d * d) / w2) : ((d == 0.0) ? 1.0 : 0.0);
+            s += L.ratio[k] * g;
+        }
+    }
+    return s;
+}
+
 struct SpectralArgs {
     int D, Dp, HL, N, ntaps;
     long nspax;
     const int *shift;      // [ntaps]  (N/2 - h - t) mod N
     const double *weight;  // [ntaps]
+    LineShape line;        // the unit line of k_lines*
 };
 
 // Closed form of convolve_1d (lib/convolution.py:89-120):
@@ -114,7 +148,7 @@ __device__ __forceinline__ double lsf_apply(const double *ext, int k, const Spec
 // params (H,W,3) -> cube of LSF-convolved lines (mode 1) or clean lines
 // (mode 0), zero where mask == 0.  lib/run.py:597-621 and :1011-1024.
 // One group of HL threads per spaxel, G groups per block, ext[] in LDS.
-template <int NT>
+template <int NT, bool MULTI = false>
 __global__ __launch_bounds__(NT) void k_lines(SpectralArgs A, const double *__restrict__ params,
                                               const uint8_t *__restrict__ mask,
                                               double *__restrict__ out, int convolved) {
@@ -136,8 +170,8 @@ __global__ __launch_bounds__(NT) void k_lines(SpectralArgs A, const double *__re
     double2 v = make_double2(0.0, 0.0);
     if (active && live) {
         const int z = 2 * zl;
-        v.x = (z < A.D) ? a * unit_gaussian((double)z, c, w) : 0.0;
-        v.y = (z + 1 < A.D) ? a * unit_gaussian((double)(z + 1), c, w) : 0.0;
+        v.x = (z < A.D) ? a * unit_line<MULTI>(A.line, (double)z, c, w) : 0.0;
+        v.y = (z + 1 < A.D) ? a * unit_line<MULTI>(A.line, (double)(z + 1), c, w) : 0.0;
     }
     if (use_lsf) {
         if (active) {
@@ -278,7 +312,7 @@ __device__ __forceinline__ double exp_nonpositive(double x) {
     return ldexp(p, (int)k);
 }
 
-template <bool FAST>
+template <bool FAST, bool MULTI = false>
 static __global__ __launch_bounds__(256) void k_lines_dense(SpectralArgs A, int HLG, int steps, int L,
                                                             const double *__restrict__ wl,
                                                             const double *__restrict__ params,
@@ -320,7 +354,8 @@ static __global__ __launch_bounds__(256) void k_lines_dense(SpectralArgs A, int 
         const bool live = __shfl(plive, src) != 0;
         const double inv_w2 = 1.0 / (2.0 * w * w);  // (FAST; w == 0 or a denormal 2 w^2: the delta at z == c)
         auto line_at = [&](int zi) {
-            if (!FAST) return a * unit_gaussian((double)zi, c, w);
+            static_assert(!(FAST && MULTI), "the own exp is the single Gaussian's (launch_lines)");
+            if (!FAST) return a * unit_line<MULTI>(A.line, (double)zi, c, w);
             const double d = (double)zi - c;
             return inv_w2 <= 1.79769313486231570815e+308 ? a * exp_nonpositive(-(d * d) * inv_w2)
                                                          : (d == 0.0 ? a : a * 0.0);
@@ -1808,6 +1843,9 @@ struct MHArgs {
     // row of this launch's pair of colour classes
     const double *ptab;
     int ptab_row[2];  // (one per pending layer the kernel can apply)
+    // the unit line of every update (unit_line; d3d_set_line_shape) -- last, so that the
+    // other arguments keep their places in the kernarg segment
+    LineShape line;
 #ifdef D3D_EXPERIMENTS
     // k_mh_ws phase stamps (100 MHz wall clock), 8 slots per workgroup: 0 entry,
     // 1 setup done, 2 window streamed, 3 prepare wavefront done, 4 update written
@@ -2147,7 +2185,7 @@ __device__ __forceinline__ bool mh_finish(const MHArgs &P, const MHShared &S, co
 // The whole decision with every thread of an NT-thread block taking part
 // (thread t <-> channel t); group partial sums must be in S.red (no barrier
 // needed before the call).
-template <int NT>
+template <int NT, bool MULTI = false>
 __device__ __forceinline__ bool mh_decide(const MHArgs &P, const MHShared &S, int sp,
                                           uint32_t sweep, double *Gz_out) {
     const int tid = threadIdx.x;
@@ -2158,8 +2196,8 @@ __device__ __forceinline__ bool mh_decide(const MHArgs &P, const MHShared &S, in
             S.gO[tid] = (tid < P.D) ? L[tid] : 0.0;
             S.gN[tid] = (tid < P.D) ? L[P.D + tid] : 0.0;
         } else {
-            S.gO[tid] = (tid < P.D) ? unit_gaussian((double)tid, q.c_old, q.w_old) : 0.0;
-            S.gN[tid] = (tid < P.D) ? unit_gaussian((double)tid, q.pn[1], q.pn[2]) : 0.0;
+            S.gO[tid] = (tid < P.D) ? unit_line<MULTI>(P.line, (double)tid, q.c_old, q.w_old) : 0.0;
+            S.gN[tid] = (tid < P.D) ? unit_line<MULTI>(P.line, (double)tid, q.pn[1], q.pn[2]) : 0.0;
         }
     }
     __syncthreads();
@@ -2182,7 +2220,7 @@ __device__ __forceinline__ bool mh_decide(const MHArgs &P, const MHShared &S, in
 
 // Immediate write-back.  MAXIT > 0: the err window stays in MAXIT double2
 // registers per thread between the passes; MAXIT == 0: pass 2 re-reads it.
-template <int NT, int MAXIT>
+template <int NT, int MAXIT, bool MULTI = false>
 __global__ __launch_bounds__(NT) void k_mh(MHArgs P, uint32_t sweep) {
     extern __shared__ double smem[];
     const int tid = threadIdx.x;
@@ -2256,7 +2294,7 @@ __global__ __launch_bounds__(NT) void k_mh(MHArgs P, uint32_t sweep) {
     }
 
     double Gt;
-    if (!mh_decide<NT>(P, S, sp, sweep, &Gt)) return;
+    if (!mh_decide<NT, MULTI>(P, S, sp, sweep, &Gt)) return;
     if (tid < Dp) S.G[tid] = Gt;
     __syncthreads();
 
@@ -2310,7 +2348,7 @@ __device__ __forceinline__ int covering_coord(int q, int c, int per, int hw, int
 // window position p: [0] local spaxel index of the voxel column (-1 = outside
 // the cube), [1] tap index of the pending update there (-1 = none), [2] which
 // of the <= 4 staged pending G rows.
-template <int NT>
+template <int NT, bool MULTI = false>
 __global__ __launch_bounds__(NT) void k_mh_defer(MHArgs P, uint32_t sweep) {
     extern __shared__ double smem[];
     const int tid = threadIdx.x;
@@ -2403,7 +2441,7 @@ __global__ __launch_bounds__(NT) void k_mh_defer(MHArgs P, uint32_t sweep) {
 
     if (!real) return;
     double Gt;
-    if (!mh_decide<NT>(P, S, sp, sweep, &Gt)) return;
+    if (!mh_decide<NT, MULTI>(P, S, sp, sweep, &Gt)) return;
     if (tid < Dp) P.Gcur[((long)(y / P.fh) * P.slots_x + x / P.fw) * Dp + tid] = Gt;
 }
 
@@ -2705,7 +2743,7 @@ __device__ __forceinline__ void mh_lsf_block(const MHArgs &P, const MHZ &Z, cons
 // with the block's wave sums and its lines handed to k_mh_zdecide (item = the window's index
 // in the launch).
 template <int NS, bool UV, bool COH, int U, int M, bool COHG = COH, bool PRE = false, bool NTV = false,
-          bool PROPS = false, bool ZBK = false>
+          bool PROPS = false, bool ZBK = false, bool MULTI = false>
 __device__ __forceinline__ void mh_ws_run(const MHArgs &P, const MHShared &S, const MHWsItem &I,
                                           uint32_t sweep, long stamp_at,
                                           const MHPre<U> *pre = nullptr, const MHZ *Zp = nullptr,
@@ -2867,13 +2905,13 @@ __device__ __forceinline__ void mh_ws_run(const MHArgs &P, const MHShared &S, co
             for (int j = lane; j < N; j += 64) {
                 int m = (Zp->z0 - LSF_RL + j) % Zp->Nfull;
                 if (m < 0) m += Zp->Nfull;
-                S.gO[j] = (m < Zp->Dfull) ? unit_gaussian((double)m, q.c_old, q.w_old) : 0.0;
-                S.gN[j] = (m < Zp->Dfull) ? unit_gaussian((double)m, q.pn[1], q.pn[2]) : 0.0;
+                S.gO[j] = (m < Zp->Dfull) ? unit_line<MULTI>(P.line, (double)m, q.c_old, q.w_old) : 0.0;
+                S.gN[j] = (m < Zp->Dfull) ? unit_line<MULTI>(P.line, (double)m, q.pn[1], q.pn[2]) : 0.0;
             }
         } else {
             for (int j = lane; j < N; j += 64) {
-                S.gO[j] = (j < P.D) ? unit_gaussian((double)j, q.c_old, q.w_old) : 0.0;
-                S.gN[j] = (j < P.D) ? unit_gaussian((double)j, q.pn[1], q.pn[2]) : 0.0;
+                S.gO[j] = (j < P.D) ? unit_line<MULTI>(P.line, (double)j, q.c_old, q.w_old) : 0.0;
+                S.gN[j] = (j < P.D) ? unit_line<MULTI>(P.line, (double)j, q.pn[1], q.pn[2]) : 0.0;
             }
         }
         __builtin_amdgcn_wave_barrier();  // wave-private region: LDS is in order per wave
@@ -2952,7 +2990,7 @@ __device__ __forceinline__ void mh_ws_run(const MHArgs &P, const MHShared &S, co
 // (chain-major); the chain's cubes, parameters, bounds and random stream replace the
 // arguments' -- everything else (work list, taps, pending-layer geometry) is common.
 template <int NS, bool UV, int U, int M, int K, int NL = -1, bool NTV = false, bool ZBK = false,
-          bool BATCH = false>
+          bool BATCH = false, bool MULTI = false>
 __global__ __launch_bounds__(NS + 64) void k_mh_ws(MHArgs P, uint32_t sweep) {
     extern __shared__ double smem[];
     constexpr int NT = NS + 64;
@@ -3019,7 +3057,7 @@ __global__ __launch_bounds__(NS + 64) void k_mh_ws(MHArgs P, uint32_t sweep) {
         mh_ws_table<M>(P, S, I, NT, &tap0);
         mh_ws_gp_store<M, K>(P, S, I, NT, gv);
         __syncthreads();
-        mh_ws_run<NS, UV, false, U, M, false, true, NTV, true, true>(P, S, I, sweep, blockIdx.x, &pre, &Z,
+        mh_ws_run<NS, UV, false, U, M, false, true, NTV, true, true, MULTI>(P, S, I, sweep, blockIdx.x, &pre, &Z,
                                                                       item, zb);
         return;
     }
@@ -3059,7 +3097,7 @@ __global__ __launch_bounds__(NS + 64) void k_mh_ws(MHArgs P, uint32_t sweep) {
     __syncthreads();
     D3D_MH_STAMP(blockIdx.x, 1, 0);
     // (U >= 4 or the wide form: the variants of launches that do not fill the chip)
-    mh_ws_run<NS, UV, false, U, M, false, true, NTV, (U >= 4 || NS != 256)>(P, S, I, sweep, blockIdx.x,
+    mh_ws_run<NS, UV, false, U, M, false, true, NTV, (U >= 4 || NS != 256), false, MULTI>(P, S, I, sweep, blockIdx.x,
                                                                            &pre);
 }
 
@@ -3345,8 +3383,8 @@ __global__ __launch_bounds__(NTMAX) void k_mh_chain(MHArgs P, MHChain F) {
                 double go = 0.0, gn = 0.0;
                 if ((sgeo[(k0 + kk) * MH_CHAIN_GEO + 2] & 2) && j < P.D) {
                     const MHProposal &q = sprop[k0 + kk];
-                    go = unit_gaussian((double)j, q.c_old, q.w_old);
-                    gn = unit_gaussian((double)j, q.pn[1], q.pn[2]);
+                    go = unit_line<false>(P.line, (double)j, q.c_old, q.w_old);  // (K == 1 only: launch_mh_chain)
+                    gn = unit_line<false>(P.line, (double)j, q.pn[1], q.pn[2]);
                 }
                 S.gO[(size_t)kk * 2 * N + j] = go;
                 S.gO[(size_t)kk * 2 * N + N + j] = gn;
@@ -3912,7 +3950,7 @@ __global__ __launch_bounds__(NS + 64) void k_mh_pair(MHArgs P, MHPair F, uint32_
 // part of the window that lies inside the local region; spaxels inside the
 // region also get their parameters.  Thread t <-> channel t for the lines, then
 // z-pairs for the window.
-template <int NT>
+template <int NT, bool MULTI = false>
 __global__ __launch_bounds__(NT) void k_apply_updates(MHArgs P, const double *__restrict__ rec,
                                                       int nrec) {
     extern __shared__ double smem[];
@@ -3925,8 +3963,8 @@ __global__ __launch_bounds__(NT) void k_apply_updates(MHArgs P, const double *__
     const double a_old = r8[2], c_old = r8[3], w_old = r8[4];
     const double a_new = r8[5], c_new = r8[6], w_new = r8[7];
     for (int j = tid; j < P.N; j += NT) {
-        gO[j] = (j < P.D) ? unit_gaussian((double)j, c_old, w_old) : 0.0;
-        gN[j] = (j < P.D) ? unit_gaussian((double)j, c_new, w_new) : 0.0;
+        gO[j] = (j < P.D) ? unit_line<MULTI>(P.line, (double)j, c_old, w_old) : 0.0;
+        gN[j] = (j < P.D) ? unit_line<MULTI>(P.line, (double)j, c_new, w_new) : 0.0;
     }
     __syncthreads();
     for (int ch = tid; ch < P.Dp; ch += NT) {
@@ -4053,6 +4091,7 @@ constexpr int MH_DEEP_ZB = 4;               // z-pairs per thread of k_mh_deep (
 constexpr int MH_DEEP_MAX = 2 * 1024 * MH_DEEP_ZB;
 
 // k_lines for any depth: one workgroup per spaxel.
+template <bool MULTI = false>
 static __global__ __launch_bounds__(1024) void k_lines_deep(SpectralArgs A,
                                                             const double *__restrict__ params,
                                                             const uint8_t *__restrict__ mask,
@@ -4064,11 +4103,11 @@ static __global__ __launch_bounds__(1024) void k_lines_deep(SpectralArgs A,
     const bool use_lsf = convolved && A.ntaps > 0;
     if (!use_lsf) {
         for (int z = threadIdx.x; z < A.Dp; z += 1024)
-            out[sp * A.Dp + z] = (live && z < A.D) ? a * unit_gaussian((double)z, c, w) : 0.0;
+            out[sp * A.Dp + z] = (live && z < A.D) ? a * unit_line<MULTI>(A.line, (double)z, c, w) : 0.0;
         return;
     }
     for (int j = threadIdx.x; j < A.N; j += 1024)
-        smem[j] = (live && j < A.D) ? a * unit_gaussian((double)j, c, w) : 0.0;
+        smem[j] = (live && j < A.D) ? a * unit_line<MULTI>(A.line, (double)j, c, w) : 0.0;
     __syncthreads();
     for (int z = threadIdx.x; z < A.Dp; z += 1024)
         out[sp * A.Dp + z] = (live && z < A.D) ? lsf_apply(smem, z, A) : 0.0;
@@ -4142,6 +4181,7 @@ __device__ __forceinline__ void mh_channel_terms(const MHProposal &q, double EO,
 // depth up to MH_DEEP_MAX: k_mh with every thread looping over its z-pairs tid, tid + 1024,
 // ...  The window sums stay in registers (one position group), the zero-extended unit lines
 // go to LDS, the decision is mh_decide_wave's.  Probe and external-lines modes as k_mh.
+template <bool MULTI = false>
 static __global__ __launch_bounds__(1024) void k_mh_deep(MHArgs P, uint32_t sweep) {
     extern __shared__ double smem[];
     constexpr int NT = 1024, ZB = MH_DEEP_ZB;
@@ -4172,8 +4212,8 @@ static __global__ __launch_bounds__(1024) void k_mh_deep(MHArgs P, uint32_t swee
             S.gO[j] = (j < P.D) ? L[j] : 0.0;
             S.gN[j] = (j < P.D) ? L[P.D + j] : 0.0;
         } else {
-            S.gO[j] = (j < P.D) ? unit_gaussian((double)j, q.c_old, q.w_old) : 0.0;
-            S.gN[j] = (j < P.D) ? unit_gaussian((double)j, q.pn[1], q.pn[2]) : 0.0;
+            S.gO[j] = (j < P.D) ? unit_line<MULTI>(P.line, (double)j, q.c_old, q.w_old) : 0.0;
+            S.gN[j] = (j < P.D) ? unit_line<MULTI>(P.line, (double)j, q.pn[1], q.pn[2]) : 0.0;
         }
     }
     __syncthreads();

@@ -57,6 +57,7 @@ void fill_mh_args(d3d_ctx *c, d3d::MHArgs &P) {
     P.fw_inv = (65536 + c->fw - 1) / c->fw;
     P.ptab = nullptr;
     P.ptab_row[0] = P.ptab_row[1] = c->fh * c->fw;
+    P.line = c->line;
     P.batch = nullptr;  // (mh_sweeps_batch)
     P.b_items = 0;
     P.b_gcur = 0;
@@ -119,11 +120,32 @@ void fill_mh_args(d3d_ctx *c, d3d::MHArgs &P) {
 #endif
 }
 
+// The instantiation of k_mh_ws for the context's line shape: the single Gaussian's kernel for
+// K == 1 (MULTI = false: unchanged code), the multiplet form (unit_line<true>) for K > 1.
+template <int NS, bool UV, int U, int M, int K, int NL, bool NTV = false, bool ZBK = false, bool BATCH = false>
+static auto mh_ws_kernel(bool multi) {
+    return multi ? &d3d::k_mh_ws<NS, UV, U, M, K, NL, NTV, ZBK, BATCH, true>
+                 : &d3d::k_mh_ws<NS, UV, U, M, K, NL, NTV, ZBK, BATCH, false>;
+}
+
+// options whose kernels have no multiplet form (EXPERIMENTS builds): refused, never ignored
+static int need_single_line(const d3d_ctx *c, const char *what) {
+    if (c->line.K == 1) return 0;
+    return fail(D3D_ERR_UNSUPPORTED, "%s has no multiplet form: the line shape has %d components "
+                "(d3d_set_line_shape; one Gaussian only)", what, c->line.K);
+}
+
 template <int NT, int MAXIT>
 int launch_mh_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep) {
     const size_t lds = d3d::mh_lds_doubles(NT, c->HL, c->Dp, c->N, P.npos) * sizeof(double);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh<NT, MAXIT>), dim3(grid), dim3(NT), lds, c->stream,
-                       P, sweep);
+    if (c->line.K > 1) {
+        if constexpr (MAXIT != 0) return need_single_line(c, "option mh_maxit (register-resident k_mh)");
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh<NT, MAXIT, true>), dim3(grid), dim3(NT), lds, c->stream,
+                           P, sweep);
+    } else {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh<NT, MAXIT>), dim3(grid), dim3(NT), lds, c->stream,
+                           P, sweep);
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -146,9 +168,10 @@ int launch_mh_nt(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep
 int launch_mh(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep) {
     if (c->deep) {  // more than 1024 channels: threads loop over their z-pairs
         const size_t lds = d3d::mh_deep_lds_doubles(c->N, P.npos) * sizeof(double);
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(d3d::k_mh_deep),
+        auto kern = c->line.K > 1 ? &d3d::k_mh_deep<true> : &d3d::k_mh_deep<false>;
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(d3d::k_mh_deep, dim3(grid), dim3(1024), lds, c->stream, P, sweep);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), lds, c->stream, P, sweep);
         HIP_TRY(hipGetLastError());
         return 0;
     }
@@ -163,8 +186,12 @@ int launch_mh(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep) {
 template <int NT>
 int launch_mh_defer_nt(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep) {
     const size_t lds = d3d::mh_lds_doubles(NT, c->HL, c->Dp, c->N, P.npos) * sizeof(double);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh_defer<NT>), dim3(grid), dim3(NT), lds, c->stream,
-                       P, sweep);
+    if (c->line.K > 1)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh_defer<NT, true>), dim3(grid), dim3(NT), lds, c->stream,
+                           P, sweep);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh_defer<NT>), dim3(grid), dim3(NT), lds, c->stream,
+                           P, sweep);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -186,13 +213,13 @@ int launch_mh_ws_um(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sw
     };
     // (the number of pending layers as a template constant: see k_mh_ws)
     switch (P.n_lay <= M ? P.n_lay : -1) {
-        case 0: go(d3d::k_mh_ws<NS, UV, U, M, K, 0, NTV>); break;
-        case 1: go(d3d::k_mh_ws<NS, UV, U, M, K, 1, NTV>); break;
+        case 0: go(mh_ws_kernel<NS, UV, U, M, K, 0, NTV>(P.line.K > 1)); break;
+        case 1: go(mh_ws_kernel<NS, UV, U, M, K, 1, NTV>(P.line.K > 1)); break;
         case 2:
-            if constexpr (M >= 2) go(d3d::k_mh_ws<NS, UV, U, M, K, 2, NTV>);
+            if constexpr (M >= 2) go(mh_ws_kernel<NS, UV, U, M, K, 2, NTV>(P.line.K > 1));
             break;
         case 3:
-            if constexpr (M >= 3) go(d3d::k_mh_ws<NS, UV, U, M, K, 3, NTV>);
+            if constexpr (M >= 3) go(mh_ws_kernel<NS, UV, U, M, K, 3, NTV>(P.line.K > 1));
             break;
         default:
             return fail(D3D_ERR_STATE, "internal: %d pending layers for a %d-layer kernel", P.n_lay, M);
@@ -427,6 +454,7 @@ int launch_mh_flow_t(d3d_ctx *c, const d3d::MHArgs &P, const d3d::MHFlow &F, uin
 }
 
 int launch_mh_flow(d3d_ctx *c, uint32_t sweep) {
+    if (int rc = need_single_line(c, "option mh_flow (k_mh_flow)")) return rc;
     HIP_TRY(hipMemsetAsync(c->flow_state, 0, c->flow_state_bytes, c->stream));
     d3d::MHArgs P;
     fill_mh_args(c, P);
@@ -468,6 +496,7 @@ int launch_mh_pair_t(d3d_ctx *c, const d3d::MHArgs &P, const d3d::MHPair &F, uin
 }
 
 int launch_mh_pair(d3d_ctx *c, int ka, uint32_t sweep) {
+    if (int rc = need_single_line(c, "option mh_pair (k_mh_pair)")) return rc;
     d3d::MHArgs P;
     fill_mh_args(c, P);
     P.rev = c->mh_zigzag;  // zig-zag enabled: the kernel derives each item's direction
@@ -536,23 +565,23 @@ int launch_mh_zb_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned n_items, uint32_t 
     const int nl = P.n_lay;
     if (layers >= 2) {
         if (few) {
-            if (nl == 0) go(d3d::k_mh_ws<NS, UV, 4, 2, 4, 0, false, true>, 2);
-            else if (nl == 1) go(d3d::k_mh_ws<NS, UV, 4, 2, 4, 1, false, true>, 2);
-            else go(d3d::k_mh_ws<NS, UV, 4, 2, 4, 2, false, true>, 2);
+            if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 2, 4, 0, false, true>(P.line.K > 1), 2);
+            else if (nl == 1) go(mh_ws_kernel<NS, UV, 4, 2, 4, 1, false, true>(P.line.K > 1), 2);
+            else go(mh_ws_kernel<NS, UV, 4, 2, 4, 2, false, true>(P.line.K > 1), 2);
         } else if (ntv) {
             if constexpr (!UV) {
-                if (nl == 0) go(d3d::k_mh_ws<NS, UV, 2, 2, 4, 0, true, true>, 2);
-                else if (nl == 1) go(d3d::k_mh_ws<NS, UV, 2, 2, 4, 1, true, true>, 2);
-                else go(d3d::k_mh_ws<NS, UV, 2, 2, 4, 2, true, true>, 2);
+                if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 4, 0, true, true>(P.line.K > 1), 2);
+                else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 4, 1, true, true>(P.line.K > 1), 2);
+                else go(mh_ws_kernel<NS, UV, 2, 2, 4, 2, true, true>(P.line.K > 1), 2);
             }
         } else {
-            if (nl == 0) go(d3d::k_mh_ws<NS, UV, 2, 2, 4, 0, false, true>, 2);
-            else if (nl == 1) go(d3d::k_mh_ws<NS, UV, 2, 2, 4, 1, false, true>, 2);
-            else go(d3d::k_mh_ws<NS, UV, 2, 2, 4, 2, false, true>, 2);
+            if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 4, 0, false, true>(P.line.K > 1), 2);
+            else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 4, 1, false, true>(P.line.K > 1), 2);
+            else go(mh_ws_kernel<NS, UV, 2, 2, 4, 2, false, true>(P.line.K > 1), 2);
         }
     } else {
-        if (nl == 0) go(d3d::k_mh_ws<NS, UV, 4, 1, 4, 0, false, true>, 1);
-        else go(d3d::k_mh_ws<NS, UV, 4, 1, 4, 1, false, true>, 1);
+        if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 1, 4, 0, false, true>(P.line.K > 1), 1);
+        else go(mh_ws_kernel<NS, UV, 4, 1, 4, 1, false, true>(P.line.K > 1), 1);
     }
     HIP_TRY(hipGetLastError());
     const int nw = P.z_nb * (NS / 64);
@@ -605,17 +634,17 @@ int launch_mh_batch_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t 
     const int nl = P.n_lay;
     if (layers >= 2) {  // Dp <= 160: the staged G rows in two registers
         if (few) {
-            if (nl == 0) go(d3d::k_mh_ws<NS, UV, 4, 2, 2, 0, false, false, true>, 2);
-            else if (nl == 1) go(d3d::k_mh_ws<NS, UV, 4, 2, 2, 1, false, false, true>, 2);
-            else go(d3d::k_mh_ws<NS, UV, 4, 2, 2, 2, false, false, true>, 2);
+            if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 2, 2, 0, false, false, true>(P.line.K > 1), 2);
+            else if (nl == 1) go(mh_ws_kernel<NS, UV, 4, 2, 2, 1, false, false, true>(P.line.K > 1), 2);
+            else go(mh_ws_kernel<NS, UV, 4, 2, 2, 2, false, false, true>(P.line.K > 1), 2);
         } else {
-            if (nl == 0) go(d3d::k_mh_ws<NS, UV, 2, 2, 2, 0, false, false, true>, 2);
-            else if (nl == 1) go(d3d::k_mh_ws<NS, UV, 2, 2, 2, 1, false, false, true>, 2);
-            else go(d3d::k_mh_ws<NS, UV, 2, 2, 2, 2, false, false, true>, 2);
+            if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 2, 0, false, false, true>(P.line.K > 1), 2);
+            else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 2, 1, false, false, true>(P.line.K > 1), 2);
+            else go(mh_ws_kernel<NS, UV, 2, 2, 2, 2, false, false, true>(P.line.K > 1), 2);
         }
     } else {
-        if (nl == 0) go(d3d::k_mh_ws<NS, UV, 4, 1, 4, 0, false, false, true>, 1);
-        else go(d3d::k_mh_ws<NS, UV, 4, 1, 4, 1, false, false, true>, 1);
+        if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 1, 4, 0, false, false, true>(P.line.K > 1), 1);
+        else go(mh_ws_kernel<NS, UV, 4, 1, 4, 1, false, false, true>(P.line.K > 1), 1);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -692,7 +721,8 @@ int mh_sweeps_batch(d3d_ctx **cs, int R, int n_sweeps, int first_sweep, int64_t 
                 fill_mh_args(L, T);
                 const int n = (L->oy1 - L->oy0) * (L->ox1 - L->ox0);
                 const size_t lds = (size_t)4 * 2 * L->N * sizeof(double);
-                hipLaunchKernelGGL(d3d::k_mh_line_table, dim3((unsigned)(((long)n * R + 3) / 4)), dim3(256), lds,
+                hipLaunchKernelGGL(L->line.K > 1 ? &d3d::k_mh_line_table<true> : &d3d::k_mh_line_table<false>,
+                                   dim3((unsigned)(((long)n * R + 3) / 4)), dim3(256), lds,
                                    L->stream, T, rs, L->oy0, L->oy1, L->ox0, L->ox1, L->props, L->ltab,
                                    (const d3d::MHChainArgs *)dev, R);
                 if (hipGetLastError() != hipSuccess) { rc = fail(D3D_ERR_HIP, "k_mh_line_table"); break; }
@@ -785,7 +815,8 @@ int ensure_proposals(d3d_ctx *c, uint32_t sweep) {
         if (int rc = ensure_ptab(c)) return rc;
     if (n > 0 && lines) {
         const size_t lds = (size_t)4 * 2 * c->N * sizeof(double);
-        hipLaunchKernelGGL(d3d::k_mh_line_table, dim3((unsigned)((n + 3) / 4)), dim3(256), lds, c->stream, P,
+        hipLaunchKernelGGL(c->line.K > 1 ? &d3d::k_mh_line_table<true> : &d3d::k_mh_line_table<false>,
+                           dim3((unsigned)((n + 3) / 4)), dim3(256), lds, c->stream, P,
                            sweep, c->oy0, c->oy1, c->ox0, c->ox1, c->props, c->ltab,
                            (const d3d::MHChainArgs *)nullptr, 0);
         HIP_TRY(hipGetLastError());
@@ -856,6 +887,7 @@ int launch_mh_chain_uv(d3d_ctx *c, const d3d::MHArgs &P, const d3d::MHChain &F, 
 }  // namespace
 
 int launch_mh_chain(d3d_ctx *c, int pi, uint32_t sweep0, int n_sweeps) {
+    if (int rc = need_single_line(c, "option mh_chain (k_mh_chain)")) return rc;
     d3d_ctx::Part &pt = c->parts[pi];
     if (!pt.chain || n_sweeps <= 0) return fail(D3D_ERR_STATE, "internal: part %d has no chain form", pi);
     if (c->lay_n)  // the kernel starts from a residual with nothing pending
@@ -928,7 +960,14 @@ int launch_mh_chain(d3d_ctx *c, int pi, uint32_t sweep0, int n_sweeps) {
 
 int launch_apply_updates(d3d_ctx *c, const d3d::MHArgs &P, const double *rec, int n) {
     const size_t lds = (size_t)(2 * c->N + c->Dp) * sizeof(double);
-    if (c->HL <= 256) {
+    if (c->line.K > 1) {
+        if (c->HL <= 256)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_apply_updates<256, true>), dim3((unsigned)n), dim3(256),
+                               lds, c->stream, P, rec, n);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_apply_updates<1024, true>), dim3((unsigned)n),
+                               dim3(1024), lds, c->stream, P, rec, n);
+    } else if (c->HL <= 256) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_apply_updates<256>), dim3((unsigned)n), dim3(256),
                            lds, c->stream, P, rec, n);
     } else {

@@ -446,6 +446,7 @@ __global__ __launch_bounds__(NS) void k_mh_small(MHArgs P, uint32_t sweep) {
 // wave-private LDS region, mh_lsf per channel): the same bits.
 // batch != NULL: the tables of R chains in one launch (grid over R x spaxels, chain-major): the
 // chain's parameters, bounds, random stream and table pointers replace the arguments'.
+template <bool MULTI = false>
 static __global__ __launch_bounds__(256) void k_mh_line_table(MHArgs P, uint32_t sweep, int y0, int y1,
                                                                int x0, int x1, MHProposal *props,
                                                                double *ltab, const MHChainArgs *batch,
@@ -482,8 +483,8 @@ static __global__ __launch_bounds__(256) void k_mh_line_table(MHArgs P, uint32_t
                         (uint32_t)((y + P.gy0) * P.Wg + (x + P.gx0)), sweep);
     if (lane == 0) props[sp] = q;
     for (int j = lane; j < N; j += 64) {
-        gO[j] = (j < P.D) ? unit_gaussian((double)j, q.c_old, q.w_old) : 0.0;
-        gN[j] = (j < P.D) ? unit_gaussian((double)j, q.pn[1], q.pn[2]) : 0.0;
+        gO[j] = (j < P.D) ? unit_line<MULTI>(P.line, (double)j, q.c_old, q.w_old) : 0.0;
+        gN[j] = (j < P.D) ? unit_line<MULTI>(P.line, (double)j, q.pn[1], q.pn[2]) : 0.0;
     }
     __builtin_amdgcn_wave_barrier();  // wave-private region: LDS is in order per wave
     for (int ch = lane; ch < Dp; ch += 64) {

@@ -3,10 +3,13 @@
 Line-model plugin interface -- same names and contracts as the reference's
 ``lib/line_models.py`` (LineModel :4-61, SingleGaussianLineModel :64-109).
 
-The device kernels implement ``SingleGaussianLineModel`` (amplitude Gibbs-
-sampled, centre/width Metropolis-Hastings).  ``modelize`` below is the host
-evaluation of the same curve, kept for API parity (plots, user scripts).
+The device kernels implement ``SingleGaussianLineModel`` and
+``GaussianMultipletLineModel`` (amplitude Gibbs-sampled, centre/width
+Metropolis-Hastings).  ``modelize`` below is the host evaluation of the same
+curve, kept for API parity (plots, user scripts).
 """
+import math
+
 import numpy as np
 
 
@@ -69,3 +72,127 @@ class SingleGaussianLineModel(LineModel):
     @staticmethod
     def gaussian(x, a, c, w):
         return a * np.exp(-1. * (x - c) ** 2 / (2. * w ** 2))
+
+
+class GaussianMultipletLineModel(LineModel):
+    """
+    K Gaussians of ONE centre and ONE width at fixed channel offsets with fixed
+    flux ratios -- a multiplet with tied kinematics ([OII] 3726,3729, Halpha with
+    the [NII] pair, the [SII] and [OIII] doublets)::
+
+        a * sum_k ratios[k] * exp(-((x - c) - offsets[k])^2 / (2 w^2))
+
+    The parameters are those of ``SingleGaussianLineModel``, ``['a', 'c', 'w']``
+    with the same Gibbs index and bounds: ``c`` and ``a`` are the first
+    component's centre and amplitude (``offsets[0] == 0``, ``ratios[0] == 1``).
+    The line is still linear in ``a``, so the amplitude stays Gibbs-sampled, and
+    the device kernels evaluate it themselves (``d3d_set_line_shape``).
+
+    ``offsets``: channel offsets of the components from ``c``; ``ratios``: their
+    flux ratios to ``a``.  1 to 4 components, every value finite, ratios >= 0,
+    offsets distinct; anything else raises ``ValueError``.
+    """
+
+    MAX_COMPONENTS = 4
+
+    def __init__(self, offsets, ratios):
+        LineModel.__init__(self)
+        try:
+            off = [float(v) for v in np.atleast_1d(np.asarray(offsets, dtype=np.float64)).ravel()]
+            rat = [float(v) for v in np.atleast_1d(np.asarray(ratios, dtype=np.float64)).ravel()]
+        except (TypeError, ValueError):
+            raise ValueError("offsets and ratios must be sequences of numbers")
+        if len(off) != len(rat):
+            raise ValueError("offsets and ratios must have the same length, got %d and %d"
+                             % (len(off), len(rat)))
+        if not 1 <= len(off) <= self.MAX_COMPONENTS:
+            raise ValueError("a multiplet has 1 to %d components, got %d"
+                             % (self.MAX_COMPONENTS, len(off)))
+        if not all(math.isfinite(v) for v in off + rat):
+            raise ValueError("offsets and ratios must be finite")
+        if off[0] != 0. or rat[0] != 1.:
+            raise ValueError("offsets[0] must be 0 and ratios[0] must be 1: c and a are the "
+                             "first line's centre and amplitude")
+        if any(r < 0. for r in rat):
+            raise ValueError("ratios must be >= 0")
+        if len(set(off)) != len(off):
+            raise ValueError("offsets must be distinct")
+        self.offsets = tuple(off)
+        self.ratios = tuple(rat)
+
+    @classmethod
+    def from_rest_wavelengths(cls, cube, rest_wavelengths, ratios, redshift):
+        """
+        The multiplet of lines at ``rest_wavelengths`` (micrometres, the unit of
+        ``Cube.z_step``; the first is the line of ``c``) observed at
+        ``redshift`` in ``cube``: offsets ``(l_k - l_0) (1 + z) / cube.z_step``
+        channels.  [OII] at z = 0.7 on a MUSE cube (1.25 A channels)::
+
+            >>> import numpy as np
+            >>> from deconv3d_amd import MUSE, GaussianMultipletLineModel
+            >>> cube = MUSE().build_cube(np.zeros((64, 8, 8)))
+            >>> oii = GaussianMultipletLineModel.from_rest_wavelengths(
+            ...     cube, [0.372603, 0.372882], [1.0, 1.4], redshift=0.7)
+            >>> round(oii.offsets[1], 2)
+            3.79
+        """
+        lam = np.atleast_1d(np.asarray(rest_wavelengths, dtype=np.float64))
+        if lam.size == 0:
+            raise ValueError("a multiplet has 1 to %d components, got 0" % cls.MAX_COMPONENTS)
+        offsets = (lam - lam[0]) * (1. + float(redshift)) / cube.z_step
+        return cls(offsets, ratios)
+
+    def parameters(self):
+        return ['a', 'c', 'w']
+
+    def gibbs_parameter_index(self):
+        return 0
+
+    def min_boundaries(self, runner):
+        return [0, 0, 0]
+
+    def max_boundaries(self, runner):
+        # the single Gaussian's bounds (lib/line_models.py:79-90): c and a are the first line's
+        return SingleGaussianLineModel.max_boundaries(self, runner)
+
+    def modelize(self, runner, x, parameters):
+        return self.multiplet(np.asarray(x, dtype=np.float64),
+                              parameters[0], parameters[1], parameters[2])
+
+    def multiplet(self, x, a, c, w):
+        """``a * sum_k r_k exp(-((x - c) - d_k)^2 / (2 w^2))`` in component order -- the
+        order of the device's unit_line (K == 1: SingleGaussianLineModel.gaussian, bit for bit)."""
+        s = 0.
+        for off, r in zip(self.offsets, self.ratios):
+            s = s + r * np.exp(-1. * ((x - c) - off) ** 2 / (2. * w ** 2))
+        return a * s
+
+
+SINGLE_LINE_SHAPE = ((0.,), (1.,))
+
+
+def model_is_on_device(model):
+    """True when the HIP kernels evaluate ``model`` themselves:
+    ``SingleGaussianLineModel`` or ``GaussianMultipletLineModel`` (subclasses may change
+    names and bounds, but not the curve, the jump hook or the Gibbs index).  Any other
+    LineModel plugin is evaluated on the host (host_model.HostModelChain)."""
+    if isinstance(model, GaussianMultipletLineModel):
+        curve = (type(model).modelize is GaussianMultipletLineModel.modelize
+                 and type(model).multiplet is GaussianMultipletLineModel.multiplet)
+    elif isinstance(model, SingleGaussianLineModel):
+        curve = (type(model).modelize is SingleGaussianLineModel.modelize
+                 and type(model).gaussian is SingleGaussianLineModel.gaussian)
+    else:
+        return False
+    return (curve
+            and type(model).post_jump is LineModel.post_jump
+            and model.gibbs_parameter_index() == 0
+            and len(model.parameters()) == 3)
+
+
+def device_line_shape(model):
+    """(offsets, ratios) of the device's unit line for a model that runs on the device."""
+    # (the very attributes modelize sums over: the device cannot disagree with the host curve)
+    if isinstance(model, GaussianMultipletLineModel):
+        return tuple(model.offsets), tuple(model.ratios)
+    return SINGLE_LINE_SHAPE

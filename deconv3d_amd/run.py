@@ -21,8 +21,9 @@ Differences from the reference, all deliberate:
   * the user's mask is copied, not mutated; zero variances become 1e12 for
     ndarray input too; NaN voxels get zero weight in the Gibbs sums as well;
   * 1-D ``initial_parameters`` are broadcast as the docstring promises;
-  * ``SingleGaussianLineModel`` (and subclasses that only change names/bounds)
-    is evaluated on the device; any other ``LineModel`` plugin is evaluated on
+  * ``SingleGaussianLineModel`` and ``GaussianMultipletLineModel`` (and
+    subclasses that only change names/bounds) are evaluated on the device; any
+    other ``LineModel`` plugin is evaluated on
     the host per colour class (host_model.py) with the same device kernels for
     everything else -- correct, but python-speed.
 """
@@ -37,7 +38,8 @@ import numpy as np
 from . import _lib
 from .cube import Cube, read_fits
 from .instruments import Instrument
-from .line_models import LineModel, SingleGaussianLineModel
+from .line_models import (LineModel, SingleGaussianLineModel, SINGLE_LINE_SHAPE,
+                          device_line_shape, model_is_on_device)
 from .math_utils import median_clip
 
 logging.basicConfig(level=logging.INFO)
@@ -192,6 +194,8 @@ class Run:
             if not isinstance(self.model, LineModel):
                 raise TypeError("Provided model is not a LineModel")
         self._host_model = not self._model_is_on_device()
+        # (offsets, ratios) of the device's unit line; None for a host-evaluated model
+        self.line_shape = None if self._host_model else device_line_shape(self.model)
         min_boundaries = np.array(self.model.min_boundaries(self), dtype=np.float64)
         max_boundaries = np.array(self.model.max_boundaries(self), dtype=np.float64)
         names = self.model.parameters()
@@ -299,6 +303,19 @@ class Run:
                 int(state["total_iterations"] if "total_iterations" in files else state["iteration"]))
             if n_chains > 1 and "per_chain_accepted" in files:
                 resumed_per_chain = [int(v) for v in state["per_chain_accepted"]]
+            # (a checkpoint without a line shape was written by a single-Gaussian run)
+            if self.line_shape is not None:
+                saved = SINGLE_LINE_SHAPE
+                if "line_offsets" in files:
+                    saved = (state["line_offsets"], state["line_ratios"])
+                if not (np.array_equal(np.asarray(saved[0], dtype=np.float64),
+                                       np.asarray(self.line_shape[0], dtype=np.float64))
+                        and np.array_equal(np.asarray(saved[1], dtype=np.float64),
+                                           np.asarray(self.line_shape[1], dtype=np.float64))):
+                    raise ValueError("resume_state was written with the line shape offsets %s, "
+                                     "ratios %s; this run's model has offsets %s, ratios %s"
+                                     % (tuple(np.ravel(saved[0])), tuple(np.ravel(saved[1])),
+                                        self.line_shape[0], self.line_shape[1]))
 
         # ---- device context ----------------------------------------------
         self.engines = []
@@ -307,6 +324,8 @@ class Run:
             self.engines.append(eng)
             eng.set_taps(self.fsf, self.lsf)
             eng.set_data(self.cube.data, self.variance_cube, mask=self.mask)
+            if self.line_shape is not None:
+                eng.set_line_shape(*self.line_shape)
         self.engine = self.engines[0]
         host_chain = None
         if self._host_model:
@@ -429,18 +448,12 @@ class Run:
     # ------------------------------------------------------------------------
 
     def _model_is_on_device(self):
-        """The HIP kernels evaluate SingleGaussianLineModel themselves (subclasses
-        may change names/bounds but not the curve or the Gibbs index); any other
-        LineModel plugin is evaluated on the host (host_model.HostModelChain):
-        same device kernels for LSF, window statistics, accept, Gibbs draw and
-        residual, but python-speed proposals and modelize() calls."""
-        m = self.model
-        return (isinstance(m, SingleGaussianLineModel)
-                and type(m).modelize is SingleGaussianLineModel.modelize
-                and type(m).gaussian is SingleGaussianLineModel.gaussian
-                and type(m).post_jump is LineModel.post_jump
-                and m.gibbs_parameter_index() == 0
-                and len(m.parameters()) == 3)
+        """The HIP kernels evaluate SingleGaussianLineModel and GaussianMultipletLineModel
+        themselves (line_models.model_is_on_device: subclasses may change names/bounds but
+        not the curve or the Gibbs index); any other LineModel plugin is evaluated on the
+        host (host_model.HostModelChain): same device kernels for LSF, window statistics,
+        accept, Gibbs draw and residual, but python-speed proposals and modelize() calls."""
+        return model_is_on_device(self.model)
 
     def _sweep_chains(self, n, first, all_likelihoods):
         """n sweeps of every chain: ONE launch per colour class for all of them where the
@@ -500,6 +513,9 @@ class Run:
         if self.n_chains > 1:
             state["per_chain_accepted"] = np.array(
                 [a + b for a, b in zip(per_chain_accepted, self._acc_base_chain)], dtype=np.int64)
+        if self.line_shape is not None:     # (resume_state= checks it)
+            state["line_offsets"] = np.array(self.line_shape[0], dtype=np.float64)
+            state["line_ratios"] = np.array(self.line_shape[1], dtype=np.float64)
         np.savez("%s_state.npz" % name, **state)
         if self._host_model:
             maps = [hc.params for hc in self._host_chains]

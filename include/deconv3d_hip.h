@@ -125,6 +125,19 @@ int d3d_set_data(d3d_ctx *ctx, const double *data, const double *var,
 /* Current parameter map, lib/run.py:294-314,338. */
 int d3d_set_params(d3d_ctx *ctx, const double *params);
 int d3d_get_params(d3d_ctx *ctx, double *params);
+/* Unit line of the line model (lib/line_models.py:17-61, 92-109): K Gaussians of the
+ * spaxel's one centre c and width w at channel offsets offsets[k] from c, with flux ratios
+ * ratios[k] relative to the first,
+ *   sum_k ratios[k] * exp(-((z - c) - offsets[k])^2 / (2 w^2)),
+ * summed in component order -- a multiplet with tied kinematics ([OII] 3726,3729, Halpha
+ * with [NII]; python: GaussianMultipletLineModel).  Still linear in the amplitude a, so the
+ * parameters stay (a, c, w).  1 <= K <= 4, offsets[0] == 0 and ratios[0] == 1 (c and a are
+ * the first line's), every value finite, ratios >= 0, offsets distinct; anything else is
+ * D3D_ERR_INVALID.  Default on creation: K = 1, {0}, {1} (SingleGaussianLineModel, bit for
+ * bit).  Writes the pending updates back, then invalidates the residual and the sweep's
+ * proposal / line tables: every later line build (forward model, simulate, MH updates,
+ * residual refresh) uses the new shape. */
+int d3d_set_line_shape(d3d_ctx *ctx, int K, const double *offsets, const double *ratios);
 
 /* ---- forward model ------------------------------------------------------ */
 
