@@ -725,6 +725,10 @@ int d3d_ctx_get_option(d3d_ctx *c, const char *key, long *value) {
         *value = c->mh_nt_ivar ? 1 : 0;
         return D3D_OK;
     }
+    if (!strcmp(key, "batch_layers")) {   // pending layers of the last d3d_mh_sweeps_batch: 2 = its joint launches filled the chip
+        *value = c->batch_layers;
+        return D3D_OK;
+    }
     if (!strcmp(key, "lsf_fits")) {       // the LSF taps lie within +-LSF_RL channels: fused / z-blocked kernels
         *value = (c->have_taps && (c->ntaps == 0 || c->lsf_dense_any)) ? 1 : 0;
         return D3D_OK;

@@ -165,6 +165,7 @@ struct d3d_ctx {
     // not been written into SLOT_ERR yet (k_mh_ws applies up to mh_layers of them)
     int lay_n = 0, lay_cy[3] = {-1, -1, -1}, lay_cx[3] = {-1, -1, -1}, lay_g[3] = {0, 0, 0};
     int mh_layers = 2;            // most pending layers any part uses (d3d_mh_layers)
+    int batch_layers = 0;         // pending layers of the last d3d_mh_sweeps_batch this context was in (0: none yet)
     bool mh_nt_ivar = false;      // 1/variance loads non-temporal: residual + 1/variance exceed the Infinity Cache
     int mh_nt_ivar_opt = -1;      // option mh_nt_ivar: -1 by working set, 0 / 1 forced (within the raw buffer's 2 GiB)
     int mh_zigzag = 1;            // option mh_zigzag: odd colour ordinals walk windows / work lists backwards (MHArgs::rev)

@@ -659,6 +659,7 @@ int mh_sweeps_batch(d3d_ctx **cs, int R, int n_sweeps, int first_sweep, int64_t 
     for (int col = 0; col < ncol; ++col) most = std::max(most, pt.off[col + 1] - pt.off[col]);
     // two pending layers where the launch of all chains together fills the chip
     const int layers = (L->Dp <= 160 && (long)most * R >= L->flow_grid / 2) ? 2 : 1;
+    for (int r = 0; r < R; ++r) cs[r]->batch_layers = layers;  // (read-only option batch_layers)
     const bool uv = L->ivar_is_uniform && L->uniform_fast_path;
     // a joint launch that still does not fill the chip: k_mh_small with the chains' sweep tables
     bool small = layers == 1;

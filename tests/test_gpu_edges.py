@@ -75,6 +75,12 @@ def test_512_thread_wave_specialised_kernel_is_bit_identical_to_the_other_scheme
     """257 .. 512 channels: k_mh_ws with 512 streaming threads -- one or two pending layers,
     the few-windows form (four positions in flight) as chosen for this small cube -- against
     the plain deferred kernel and the immediate one (same position groups: same bits)."""
+    check_512_thread_schemes(D)
+
+
+def check_512_thread_schemes(D, line_shape=None):
+    """The body of test_512_thread_wave_specialised_kernel_is_bit_identical_to_the_other_schemes
+    (line_shape: (offsets, ratios) set on every context)."""
     H, W = 9, 13
     fsf = O.gaussian_fsf_image(1.6)
     lsf = O.gaussian_lsf_vector(D, 1.1)
@@ -84,6 +90,8 @@ def test_512_thread_wave_specialised_kernel_is_bit_identical_to_the_other_scheme
         with _lib.Engine((D, H, W), fsf.shape, options=opts) as eng:
             eng.set_taps(fsf, lsf)
             eng.set_data(data, var, mask=mask)
+            if line_shape is not None:
+                eng.set_line_shape(*line_shape)
             eng.set_params(init)
             eng.mh_config(min_b, max_b, 0.1, 40.0, seed=3, refresh_every=0)
             if opts == {"mh_defer": 1, "mh_layers": 2}:
@@ -102,6 +110,12 @@ def test_z_blocked_sweep_kernels_against_the_plain_ones(D, uniform):
     uniform variance, masked spaxels, a ragged last block -- against the plain kernels
     (mh_zblocks = 0: k_mh_defer / k_mh_deep): another grouping of the channel sums, so to
     rounding; the two layer depths of the z-blocked form bit for bit."""
+    check_z_blocked_against_plain(D, uniform)
+
+
+def check_z_blocked_against_plain(D, uniform, line_shape=None):
+    """The body of test_z_blocked_sweep_kernels_against_the_plain_ones (line_shape: (offsets,
+    ratios) set on every context)."""
     H, W = 13, 12
     fsf = O.gaussian_fsf_image(1.6)
     lsf = O.muse_like_lsf(D)             # taps within +-8 channels: what the z-blocked form takes
@@ -113,6 +127,8 @@ def test_z_blocked_sweep_kernels_against_the_plain_ones(D, uniform):
         with _lib.Engine((D, H, W), fsf.shape, options=opts) as eng:
             eng.set_taps(fsf, lsf)
             eng.set_data(data, var, mask=mask)
+            if line_shape is not None:
+                eng.set_line_shape(*line_shape)
             eng.set_params(init)
             eng.mh_config(min_b, max_b, 0.1, 40.0, seed=3, refresh_every=0)
             if uniform:

@@ -33,11 +33,15 @@ pytestmark = pytest.mark.gpu
 SEED = 12345
 
 
-def build(D, H, W, fs, options=None):
+def build(D, H, W, fs, options=None, line_shape=None):
+    """line_shape: (offsets, ratios), set before the data are built -- bench.synthetic_inputs
+    builds them with the engine's own forward model."""
     import bench as B
     fsf, lsf = B.build_taps(D, fs)
     eng = _lib.Engine((D, H, W), fsf.shape, options=options)
     eng.set_taps(fsf, lsf)
+    if line_shape is not None:
+        eng.set_line_shape(*line_shape)
     data, var, truth, init, min_b, max_b = B.synthetic_inputs(eng, D, H, W, fsf, SEED)
     mask = np.ones((H, W))
     mask[17, min(200, W - 1)] = mask[H // 2 + 1, W // 2 - 1] = mask[H // 2, W // 2] = 0
@@ -116,17 +120,24 @@ def test_beyond_cache_policy_is_bit_identical_and_matches_the_oracle():
     context whose working set exceeds the 256 MiB Infinity Cache, option mh_nt_ivar)
     forced on for a 300x300x16 cube whose colour launches fill the chip: same bytes,
     same results as the default policy -- and both equal the oracle."""
+    check_beyond_cache_policy()
+
+
+def check_beyond_cache_policy(line_shape=None, sweeps=2):
+    """The body of test_beyond_cache_policy_is_bit_identical_and_matches_the_oracle; with a
+    line_shape the caller has patched the oracle's line to the same multiplet."""
     outs = []
     for nt in (0, 1):
-        eng, pb = build(16, 300, 300, 11, options={"mh_nt_ivar": nt})
+        eng, pb = build(16, 300, 300, 11, options={"mh_nt_ivar": nt}, line_shape=line_shape)
         with eng:
             assert eng.mh_layers() == 2          # chip-filling launches: the NTV kernels' family
             assert eng.get_option("mh_nt_ivar") == nt
+            assert eng.get_option("mh_nt_ivar_on") == nt
             err0 = start(eng, pb)
-            accepted = eng.mh_sweeps(2, 1)
+            accepted = eng.mh_sweeps(sweeps, 1)
             if nt:
                 st = oracle_state(pb, err0)
-                for s in (1, 2):
+                for s in range(1, sweeps + 1):
                     O.mh_sweep(st, s)
                 assert_matches_oracle(eng, st, accepted, pb)
             outs.append((eng.get_params(), eng.get_dlog(), eng.download_slot(_lib.SLOT_ERR),

@@ -27,27 +27,33 @@ def lsf_asym(D, rng):
     return v / v.sum()
 
 
-def line_cubes(D, H, W, lsf, params, mask, dense, rounds=0):
+def line_cubes(D, H, W, lsf, params, mask, dense, rounds=0, line_shape=None):
     """(clean, LSF-convolved) line cubes with lines_dense = `dense`; the LSF is applied by the
     line kernel itself (no fused epilogue in the FSF pass).  rounds: spaxel rounds per wavefront
-    (0: by the cube's size -- one for cubes this small)."""
+    (0: by the cube's size -- one for cubes this small).  line_shape: (offsets, ratios) of a
+    multiplet."""
     if dense == 1:                             # (1 keeps the tap-list kernel for clean lines: the
         dense = 3                              #  test-only value 3 = k_lines_dense everywhere, library exp)
     opts = {"lines_dense": dense, "lines_rounds": rounds, "conv_rows": 0, "sep_fuse": 0}
     with _lib.Engine((D, H, W), DELTA.shape, options=opts) as eng:
         eng.set_taps(DELTA, lsf)
         eng.set_data(np.zeros((D, H, W)), np.ones((D, H, W)), mask=mask)
+        if line_shape is not None:
+            eng.set_line_shape(*line_shape)
         return eng.simulate(params, convolved=False), eng.simulate(params, convolved=True)
 
 
-@pytest.mark.parametrize("D,lsf_kind", [
+DEPTHS = [
     (128, "muse"), (128, "asym"), (128, "none"), (64, "asym"), (32, "muse"), (32, "asym"),
     (21, "muse"), (30, "asym"), (100, "asym"), (48, "muse"),
     (127, "asym"), (125, "asym"), (121, "asym"), (63, "asym"),       # partial wrap of the padded grid
     (256, "asym"), (255, "asym"), (249, "asym"), (200, "muse"), (130, "asym"), (301, "asym"),
     (384, "muse"), (1020, "asym"), (1024, "asym"),
-])
-def test_dense_line_kernel_matches_the_oracle_and_the_tap_list_kernel(D, lsf_kind):
+]
+
+
+def line_problem(D, lsf_kind):
+    """The 7 x 9 problem of the line cube tests at depth D: (H, W, lsf, params, mask)."""
     H, W = 7, 9
     rng = np.random.default_rng(D * 7 + len(lsf_kind))
     lsf = {"muse": O.muse_like_lsf, "asym": lambda d: lsf_asym(d, rng), "none": lambda d: None}[lsf_kind](D)
@@ -58,6 +64,12 @@ def test_dense_line_kernel_matches_the_oracle_and_the_tap_list_kernel(D, lsf_kin
     params[1, 0] = (4.0, 5.0, 0.0)             # w == 0: the delta at z == c
     mask = np.ones((H, W), dtype=np.uint8)
     mask[2, 3] = mask[6, 8] = 0
+    return H, W, lsf, params, mask
+
+
+@pytest.mark.parametrize("D,lsf_kind", DEPTHS)
+def test_dense_line_kernel_matches_the_oracle_and_the_tap_list_kernel(D, lsf_kind):
+    H, W, lsf, params, mask = line_problem(D, lsf_kind)
     clean0, conv0 = line_cubes(D, H, W, lsf, params, mask, 0)
     clean1, conv1 = line_cubes(D, H, W, lsf, params, mask, 1)
     clean2, conv2 = line_cubes(D, H, W, lsf, params, mask, 2)

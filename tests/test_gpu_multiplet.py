@@ -21,6 +21,9 @@ SHAPES = {
     "doublet": ([0., 3.8], [1., 1.4]),                      # [OII]-like
     "triplet": ([0., -14.5, 15.2], [1., 0.34, 0.11]),       # Halpha + [NII]-like: past the edge of short cubes
 }
+# K = 4 (LINE_KMAX, the last unrolled component): one component with ratio 0, one that leaves
+# short cubes on the low side and one on the high side (tests/test_gpu_multiplet_variants.py)
+QUAD = ([0., 2.5, -6.0, 11.25], [1., 0.0, 2.5, 0.3])
 
 
 def multiplet(offsets, ratios):
@@ -142,8 +145,16 @@ def test_every_default_mh_kernel_depth_matches_the_multiplet_oracle(D, lsf_kind,
     """Depths that select each default MH kernel (as test_deep_cubes_chain_matches_oracle):
     k_mh_ws with 256 / 512 streaming threads, the z-blocked form beyond 512 channels with
     the MUSE-like LSF, the thread-looped deep kernels beyond 1024."""
-    off, rat = SHAPES["triplet"]
-    monkeypatch.setattr(O, "gaussian_line", multiplet(off, rat))
+    monkeypatch.setattr(O, "gaussian_line", multiplet(*SHAPES["triplet"]))
+    depth_chain_against_oracle(D, lsf_kind, SHAPES["triplet"])
+
+
+def depth_chain_against_oracle(D, lsf_kind, line_shape, lsf_fits=None):
+    """The 5 x 6 problem of test_deep_cubes_chain_matches_oracle at depth D with the line shape
+    (the caller has patched the oracle's line to it): forward model and two sweeps against the
+    oracle.  lsf_fits: the value option lsf_fits must report (0: the taps do not fit +-8
+    channels, so the plain deferred / thread-looped kernels run beyond 512 channels)."""
+    off, rat = line_shape
     H, W = 5, 6
     fsf = O.gaussian_fsf_image(1.6)
     lsf = O.gaussian_lsf_vector(D, 1.1) if lsf_kind == "gauss" else O.muse_like_lsf(D)
@@ -161,6 +172,8 @@ def test_every_default_mh_kernel_depth_matches_the_multiplet_oracle(D, lsf_kind,
     init[..., 2] = np.maximum(init[..., 2], 0.5)
     with _lib.Engine((D, H, W), fsf.shape) as eng:
         eng.set_taps(fsf, lsf)
+        if lsf_fits is not None:
+            assert eng.get_option("lsf_fits") == lsf_fits
         eng.set_data(data, var, mask=mask)
         eng.set_line_shape(off, rat)
         eng.set_params(truth)

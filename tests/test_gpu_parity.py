@@ -16,12 +16,14 @@ pytestmark = pytest.mark.gpu
 CUBE_RTOL = 1e-12
 
 
-def engine_for(case, options=None):
+def engine_for(case, options=None, line_shape=None):
     from deconv3d_amd import _lib
     D, H, W = case["D"], case["H"], case["W"]
     eng = _lib.Engine((D, H, W), case["fsf"].shape, options=options)
     eng.set_taps(case["fsf"], case["lsf"])
     eng.set_data(case["data"], case["var"], mask=case["mask"])
+    if line_shape is not None:
+        eng.set_line_shape(*line_shape)
     return eng
 
 
@@ -216,18 +218,27 @@ def test_write_back_schemes_are_bit_identical(name):
     k_mh_defer: the next colour applies the pending update), immediate re-read and
     immediate register-resident kernels are the same arithmetic: bit-identical
     chains and residuals."""
-    case = make_case(name)
+    check_write_back_schemes(make_case(name))
+
+
+def check_write_back_schemes(case, line_shape=None, more_variants=(), variants=None):
+    """The body of test_write_back_schemes_are_bit_identical.  line_shape: (offsets, ratios)
+    set on every context (tests/test_gpu_multiplet_variants.py) -- the EXPERIMENTS kernels
+    have no multiplet form and are left out then; more_variants: further option sets that
+    must give the first one's bits; variants: another list altogether."""
     outs = []
     from deconv3d_amd import _lib
-    variants = [{"mh_defer": 1}, {"mh_defer": 1, "mh_props": 0}, {"mh_defer": 1, "mh_layers": 1},
-                {"mh_defer": 1, "mh_layers": 2},
-                {"mh_defer": 1, "mh_layers": 3}, {"mh_defer": 2},
-                {"mh_defer": 0}]
-    if _lib.has_experiments():   # k_mh_pair / k_mh_flow / register-resident k_mh: `make EXPERIMENTS=1`
+    default = variants is None
+    if default:
+        variants = [{"mh_defer": 1}, {"mh_defer": 1, "mh_props": 0}, {"mh_defer": 1, "mh_layers": 1},
+                    {"mh_defer": 1, "mh_layers": 2},
+                    {"mh_defer": 1, "mh_layers": 3}, {"mh_defer": 2},
+                    {"mh_defer": 0}] + list(more_variants)
+    if _lib.has_experiments() and line_shape is None and default:   # k_mh_pair / k_mh_flow / register-resident k_mh: `make EXPERIMENTS=1`
         variants += [{"mh_defer": 1, "mh_layers": 2, "mh_pair": 1}, {"mh_defer": 1, "mh_flow": 1},
                      {"mh_defer": 0, "mh_maxit": 8}]   # same workgroup size: same summation order
     for opts in variants:
-        with engine_for(case, options=opts) as eng:
+        with engine_for(case, options=opts, line_shape=line_shape) as eng:
             eng.set_params(case["init"])
             eng.mh_config(case["min_b"], case["max_b"], 0.1, 50.0, seed=5, refresh_every=0)
             eng.mh_sweeps(2, 1)
@@ -237,6 +248,7 @@ def test_write_back_schemes_are_bit_identical(name):
     for other in outs[1:]:
         for a, b in zip(outs[0], other):
             np.testing.assert_array_equal(a, b)
+    return outs[0]
 
 
 @pytest.mark.parametrize("name", ["c1", "odd_depth", "big_fsf"])
@@ -246,7 +258,12 @@ def test_uniform_variance_variant_is_bit_identical(name, how):
     MH kernel takes 1/var from a register instead of SLOT_IVAR.  Same
     arithmetic as the general kernel (option uniform_ivar = 0) -> bit-identical
     chains, residuals and delta maps; and it matches the oracle."""
-    case = make_case(name)
+    check_uniform_variance_variant(make_case(name), how)
+
+
+def check_uniform_variance_variant(case, how, line_shape=None):
+    """The body of test_uniform_variance_variant_is_bit_identical; with a line_shape the
+    caller has patched the oracle's line to the same multiplet."""
     shape = (case["D"], case["H"], case["W"])
     v0 = float(np.median(case["var"]))
     var_cube = np.full(shape, v0)
@@ -259,6 +276,8 @@ def test_uniform_variance_variant_is_bit_identical(name, how):
                 eng.set_data(case["data"], None, var_scalar=v0, mask=case["mask"])
             else:
                 eng.set_data(case["data"], var_cube, mask=case["mask"])
+            if line_shape is not None:
+                eng.set_line_shape(*line_shape)
             assert eng.variance_is_uniform() == (knob == 1)
             eng.set_params(case["init"])
             eng.mh_config(case["min_b"], case["max_b"], 0.1, 50.0, seed=31, refresh_every=0)
@@ -367,18 +386,37 @@ def test_small_launch_kernel_wide_form_is_bit_identical_to_round3s():
     """The same for the WIDE form (704 streaming threads: the small launches of a partitioned
     128-channel context): a 128 x 30 x 40 cube cut into a far and a near
     part like a row-strip tile, zig-zag walk, masked spaxels."""
-    from deconv3d_amd import _lib
+    check_wide_form_of_the_small_launch_kernel()
+
+
+def wide_form_problem():
+    """The 128 x 30 x 40 two-part problem of the wide-form tests: (dims, fsf, lsf, data, var,
+    mask, init, min_b, max_b, parts as (phase, rect))."""
     D, H, W = 128, 30, 40
     fsf = O.moffat_cropped(11, 3.0, 2.5)
     lsf = O.muse_like_lsf(D)
     data, var, mask, truth, init, mn, mx = O.synthetic_case(D, H, W, fsf, lsf, seed=77)
     mask[3, 5] = mask[20, 33] = 0
+    parts = [(0, (0, H - 10, 0, W)), (1, (H - 10, H, 0, W))]
+    return (D, H, W), fsf, lsf, data, var, mask, init, mn, mx, parts
+
+
+def check_wide_form_of_the_small_launch_kernel(line_shape=None):
+    """The body of test_small_launch_kernel_wide_form_is_bit_identical_to_round3s; with a
+    line_shape the wide form must be the one that ran (small_parts > 0).  Returns the
+    mh_small = 1 outputs (parameters, residual, log-ratio map, [accepted])."""
+    from deconv3d_amd import _lib
+    (D, H, W), fsf, lsf, data, var, mask, init, mn, mx, parts = wide_form_problem()
     outs = []
     for small in (1, 0):
         with _lib.Engine((D, H, W), fsf.shape, options={"mh_small": small}) as eng:
             eng.set_taps(fsf, lsf)
             eng.set_data(data, var, mask=mask)
-            eng.set_parts([(0, H - 10, 0, W), (H - 10, H, 0, W)], [0, 1])
+            if line_shape is not None:
+                eng.set_line_shape(*line_shape)
+            eng.set_parts([r for _, r in parts], [ph for ph, _ in parts])
+            if line_shape is not None:
+                assert (eng.get_option("small_parts") > 0) == (small == 1)
             eng.set_params(init)
             eng.mh_config(mn, mx, 0.1, float(mx[0] ** 2), seed=9, refresh_every=2)
             acc = eng.mh_sweeps(3, 1)
@@ -386,6 +424,7 @@ def test_small_launch_kernel_wide_form_is_bit_identical_to_round3s():
                          np.array([acc])))
     for a, b in zip(*outs):
         np.testing.assert_array_equal(a, b)
+    return outs[0]
 
 
 @pytest.mark.parametrize("kind", ["two layers", "one layer", "uniform variance", "beyond-cache policy",

@@ -100,7 +100,51 @@ def test_random_shape_matches_oracle(seed):
     check_case(draw_case(seed), seed)
 
 
-def check_case(c, seed):
+def draw_line_shape(seed, D):
+    """A multiplet for the draw `seed`, from a generator of its own (the case generators keep
+    drawing what they drew): K in {2, 3, 4}; offsets within +-min(D/2, 20) channels, to 1e-3,
+    distinct; ratios in [0.05, 2], one of them exactly 0 with probability 1/4."""
+    rng = np.random.default_rng(77000 + seed)
+    K = int(rng.integers(2, 5))
+    span = min(D / 2., 20.)
+    while True:
+        off = np.concatenate(([0.], np.round(rng.uniform(-span, span, K - 1), 3)))
+        if len(set(off.tolist())) == K:
+            break
+    rat = np.concatenate(([1.], rng.uniform(0.05, 2., K - 1)))
+    if rng.random() < 0.25:
+        rat[int(rng.integers(1, K))] = 0.
+    return off.tolist(), rat.tolist()
+
+
+def patch_oracle_line(monkeypatch, line_shape):
+    from tests.test_gpu_multiplet import multiplet
+    monkeypatch.setattr(O, "gaussian_line", multiplet(*line_shape))
+
+
+@pytest.mark.parametrize("seed", range(int(__import__("os").environ.get("D3D_TEST_RANDOM_SHAPES", "32")) * 3 // 4))
+def test_random_shape_with_a_drawn_multiplet_matches_oracle(seed, monkeypatch):
+    """test_random_shape_matches_oracle's draws with a drawn line shape (24 seeds by default)."""
+    c = draw_case(seed)
+    shape = draw_line_shape(seed, c["D"])
+    patch_oracle_line(monkeypatch, shape)
+    check_case(c, seed, line_shape=shape)
+
+
+@pytest.mark.parametrize("seed,depth", [(s, d) for s, d in enumerate(
+    [200, 264, 300, 512, 520, 700, 770, 1030, 1100, 2100, 257, 640])])
+def test_random_shape_at_greater_depths_with_a_drawn_multiplet_matches_oracle(seed, depth, monkeypatch):
+    """test_random_shape_at_greater_depths_matches_oracle's draws with a drawn line shape."""
+    c = draw_case(900 + seed, depth=depth, extent=22)
+    shape = draw_line_shape(900 + seed, depth)
+    patch_oracle_line(monkeypatch, shape)
+    check_case(c, seed, line_shape=shape)
+
+
+def check_case(c, seed, line_shape=None):
+    """line_shape: (offsets, ratios) set on the context; the caller has patched the oracle's
+    line to the same multiplet (the case's data stay the single Gaussian's: a model mismatch
+    the chain does not mind)."""
     D, H, W = shape = (c["D"], c["H"], c["W"])
     # the oracle (like lib/run.py:153-162) drops spaxels with a NaN in their spectrum
     nan_spax = np.isnan(c["data"]).any(axis=0)
@@ -114,6 +158,8 @@ def check_case(c, seed):
         else:
             eng.set_data(data, var, mask=c["mask"])
         assert eng.variance_is_uniform() == (c["vkind"] != "cube" and not nan_spax.any())
+        if line_shape is not None:
+            eng.set_line_shape(*line_shape)
         eng.set_params(c["truth"])
         sim = eng.forward()
         ref = O.forward_full(shape, c["truth"], mask, c["fsf"], c["lsf"])

@@ -62,7 +62,7 @@ def draw(seed):
                 sweeps=int(rng.integers(2, 5)))
 
 
-def run_chain(c, small):
+def run_chain(c, small, line_shape=None):
     shape = (c["D"], c["H"], c["W"])
     with _lib.Engine(shape, c["fsf"].shape, options=dict(c["opts"], mh_small=small)) as eng:
         eng.set_taps(c["fsf"], c["lsf"])
@@ -72,6 +72,8 @@ def run_chain(c, small):
             eng.set_data(c["data"], c["var"], mask=c["mask"])
         if c["parts"]:
             eng.set_parts(*c["parts"])
+        if line_shape is not None:
+            eng.set_line_shape(*line_shape)
         eng.set_params(c["init"])
         mn = np.array([0.0, 0.0, 0.3])
         mx = np.array([30.0, c["D"] - 1.0, 6.0])
@@ -84,9 +86,12 @@ def run_chain(c, small):
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("D3D_TEST_RANDOM_SMALL", "24"))))
 def test_random_small_launch_problem_is_bit_identical_to_round3s_kernels(seed):
-    c = draw(seed)
-    new, on_small = run_chain(c, 1)
-    old, on_old = run_chain(c, 0)
+    check_small_launch_draw(draw(seed))
+
+
+def check_small_launch_draw(c, line_shape=None):
+    new, on_small = run_chain(c, 1, line_shape)
+    old, on_old = run_chain(c, 0, line_shape)
     assert on_old == 0
     if on_small == 0:                          # (a 3x3 FSF on a 69x69 footprint: 529 windows per launch)
         pytest.skip("every launch of this draw fills the chip: not k_mh_small's case")
@@ -100,8 +105,11 @@ def test_random_batched_chains_are_the_chains_they_would_be_alone(seed):
     own data, start and seed each -- advanced by ONE launch per colour class are, bit for bit,
     the chains their contexts produce alone (k_mh_small<..., BATCH> while the joint launch does
     not fill the chip, k_mh_ws's batched form once it does), over two calls."""
+    check_batched_draw(draw(seed), seed)
+
+
+def check_batched_draw(c, seed, line_shape=None):
     from deconv3d_amd import ensemble
-    c = draw(seed)
     rng = np.random.default_rng(9000 + seed)
     R = int(rng.integers(2, 9))
     shape = (c["D"], c["H"], c["W"])
@@ -117,6 +125,8 @@ def test_random_batched_chains_are_the_chains_they_would_be_alone(seed):
             eng.set_data(data, c["var"] * (1.0 + 0.05 * r), mask=c["mask"])
         init = c["init"].copy()
         init[..., 2] = np.clip(init[..., 2] + 0.05 * r, 0.3, 6.0)
+        if line_shape is not None:
+            eng.set_line_shape(*line_shape)
         eng.set_params(init)
         eng.mh_config(mn, mx, 0.1, 900.0, seed=c["seed"] + r, refresh_every=c["refresh"])
         return eng
@@ -138,3 +148,23 @@ def test_random_batched_chains_are_the_chains_they_would_be_alone(seed):
     finally:
         for e in engs:
             e.close()
+
+
+@pytest.mark.parametrize("seed", range(int(os.environ.get("D3D_TEST_RANDOM_SMALL", "24")) // 2))
+def test_random_small_launch_problem_with_a_drawn_multiplet_is_bit_identical(seed):
+    """The same draws with a drawn line shape (tests/test_gpu_random_shapes.draw_line_shape;
+    12 seeds by default): k_mh_line_table<true> feeding k_mh_small, narrow and wide, against
+    k_mh_ws<..., true>.  Whether a draw skips depends on its geometry alone (every part has a
+    colour class of 512 or more window positions on a 256-CU chip); counted on the host: none
+    of the seeds 0 .. 39 does."""
+    from tests.test_gpu_random_shapes import draw_line_shape
+    c = draw(seed)
+    check_small_launch_draw(c, draw_line_shape(seed, c["D"]))
+
+
+@pytest.mark.parametrize("seed", range(int(os.environ.get("D3D_TEST_RANDOM_BATCH", "12")) * 2 // 3))
+def test_random_batched_chains_with_a_drawn_multiplet_are_the_chains_they_would_be_alone(seed):
+    """The batched twin (8 seeds by default): every chain of the batch has the drawn shape."""
+    from tests.test_gpu_random_shapes import draw_line_shape
+    c = draw(seed)
+    check_batched_draw(c, seed, draw_line_shape(seed, c["D"]))

@@ -14,16 +14,19 @@ import pytest
 from deconv3d_amd import _lib, tiling
 from oracle import deconv3d_oracle as O
 from tests.cases import make_case
-from tests.tiling_oracle import sweep_in_part_order
+from tests.test_gpu_multiplet import QUAD, SHAPES, multiplet
+from tests.tiling_oracle import part_order, sweep_in_part_order
 
 pytestmark = pytest.mark.gpu
 
 
-def single_context(case, lay, ra, seed, sweeps, refresh_every=0):
+def single_context(case, lay, ra, seed, sweeps, refresh_every=0, line_shape=None):
     D, H, W = case["D"], case["H"], case["W"]
     with _lib.Engine((D, H, W), case["fsf"].shape) as ref:
         ref.set_taps(case["fsf"], case["lsf"])
         ref.set_data(case["data"], case["var"], mask=case["mask"])
+        if line_shape is not None:
+            ref.set_line_shape(*line_shape)
         if lay is not None:
             tiling.apply_parts(ref, lay)
         ref.set_params(case["init"])
@@ -33,10 +36,11 @@ def single_context(case, lay, ra, seed, sweeps, refresh_every=0):
         return ref.get_params(), ref.download_slot(_lib.SLOT_ERR), accepted, err0
 
 
-def tiled_contexts(case, lay, ra, seed, err0, refresh_every=0):
+def tiled_contexts(case, lay, ra, seed, err0, refresh_every=0, line_shape=None):
     return [tiling.make_tile_engine(lay, r, case["data"], case["var"], case["mask"], case["fsf"],
                                     case["lsf"], case["init"], case["min_b"], case["max_b"], 0.1,
-                                    ra, seed, err=err0, refresh_every=refresh_every)
+                                    ra, seed, err=err0, refresh_every=refresh_every,
+                                    line_shape=line_shape)
             for r in range(lay.n)]
 
 
@@ -212,7 +216,12 @@ def test_update_records_replay_on_another_context():
     """The finer-grained alternative to halo copies (d3d_mh_colour /
     d3d_export_updates / d3d_apply_updates): the 8-double records of one colour
     class, replayed on a second context, reproduce the first one's residual."""
-    case = make_case("c1")
+    check_update_records_replay(make_case("c1"), (0, 40, 80))
+
+
+def check_update_records_replay(case, colours, line_shape=None):
+    """The body of test_update_records_replay_on_another_context (line_shape: (offsets, ratios)
+    set on both contexts)."""
     D, H, W = case["D"], case["H"], case["W"]
     fh, fw = case["fsf"].shape
 
@@ -220,13 +229,15 @@ def test_update_records_replay_on_another_context():
         e = _lib.Engine((D, H, W), (fh, fw))
         e.set_taps(case["fsf"], case["lsf"])
         e.set_data(case["data"], case["var"], mask=case["mask"])
+        if line_shape is not None:
+            e.set_line_shape(*line_shape)
         e.set_params(case["init"])
         e.mh_config(case["min_b"], case["max_b"], 0.1, 35.0, seed=3, refresh_every=0)
         e.residual(fetch=False)
         return e
     a, b = ctx(), ctx()
     try:
-        for colour in (0, 40, 80):
+        for colour in colours:
             a.mh_colour(colour, 1)
             cy, cx = divmod(colour, fw)
             ys, xs = np.nonzero(case["mask"][cy::fh, cx::fw] == 1)
@@ -418,6 +429,168 @@ def test_a_small_part_before_a_large_one_keeps_its_own_kernel_family():
             for (y, x) in part_order(parts, ph, mask, fs, fs):
                 O.mh_update(st, y, x, 1)
         np.testing.assert_allclose(eng.get_params(), st.params, rtol=1e-9, atol=1e-9)
+        assert accepted == st.accepted
+        err = eng.download_slot(_lib.SLOT_ERR)
+        assert np.max(np.abs(err - st.err)) <= 1e-11 * np.max(np.abs(st.err))
+
+
+# ---- the multiplet line shape (d3d_set_line_shape, K > 1) on tiled and partitioned chains ------
+
+@pytest.mark.parametrize("name,grid", [("tile_a", (2, 2)), ("tile_b", (2, 3)), ("tile_deep", (2, 1))])
+def test_tiled_doublet_chain_is_bit_identical_to_single_context(name, grid):
+    """tiling.make_tile_engine(line_shape=...): every tile builds the doublet, so the tiled chain
+    is the partitioned single context's bit for bit (tile_deep: the z-blocked kernels).  A tile
+    that kept the single Gaussian would differ; one that set the shape after the residual was
+    handed over would rebuild it from its own region."""
+    shape = SHAPES["doublet"]
+    case = make_case(name)
+    fh, fw = case["fsf"].shape
+    ra, seed, sweeps = 35.0, 77, 3
+    lay = tiling.TileLayout(case["H"], case["W"], fh, fw, *grid)
+    ref_params, ref_err, accepted, err0 = single_context(case, lay, ra, seed, sweeps, line_shape=shape)
+    assert accepted > 0
+    plain, _, _, _ = single_context(case, lay, ra, seed, sweeps)
+    assert not np.array_equal(plain, ref_params)          # the shape did change the chain
+    engines = tiled_contexts(case, lay, ra, seed, err0, line_shape=shape)
+    try:
+        tables = [tiling.plan_tables(lay, r) for r in range(lay.n)]
+        for s in range(1, sweeps + 1):
+            tiling.sweep_loopback(engines, lay, tables, s, device_copy=True)
+        compare(case, lay, engines, ref_params, ref_err)
+        assert sum(e.mh_accepted() for e in engines) == accepted
+    finally:
+        for e in engines:
+            e.close()
+
+
+def test_partitioned_k4_context_follows_the_oracle_in_part_order(monkeypatch):
+    """d3d_set_parts with the K = 4 shape: the partitioned single context -- the reference of
+    the tiled bit-identity tests -- against the patched oracle in (phase, part, colour) order."""
+    monkeypatch.setattr(O, "gaussian_line", multiplet(*QUAD))
+    case = make_case("tile_a")
+    fh, fw = case["fsf"].shape
+    lay = tiling.TileLayout(case["H"], case["W"], fh, fw, 2, 2)
+    st = O.MHState(case["data"], case["var"], case["mask"], case["fsf"], case["lsf"],
+                   case["init"], case["min_b"], case["max_b"], 0.1, 35.0, 77)
+    for s in (1, 2):
+        sweep_in_part_order(st, lay, s)
+    params, err, accepted, _ = single_context(case, lay, 35.0, 77, 2, line_shape=QUAD)
+    np.testing.assert_allclose(params, st.params, rtol=1e-9, atol=1e-9)
+    assert np.max(np.abs(err - st.err)) <= 1e-11 * np.max(np.abs(st.err))
+    assert accepted == st.accepted
+
+
+def test_partitioned_doublet_context_follows_the_oracle_in_part_order(monkeypatch):
+    """The same with the doublet on the layout the tiled doublet test uses: ties that test's
+    reference (tile_a 2x2, three sweeps, ra 35, seed 77) to the oracle."""
+    monkeypatch.setattr(O, "gaussian_line", multiplet(*SHAPES["doublet"]))
+    case = make_case("tile_a")
+    fh, fw = case["fsf"].shape
+    lay = tiling.TileLayout(case["H"], case["W"], fh, fw, 2, 2)
+    st = O.MHState(case["data"], case["var"], case["mask"], case["fsf"], case["lsf"],
+                   case["init"], case["min_b"], case["max_b"], 0.1, 35.0, 77)
+    for s in (1, 2, 3):
+        sweep_in_part_order(st, lay, s)
+    params, err, accepted, _ = single_context(case, lay, 35.0, 77, 3, line_shape=SHAPES["doublet"])
+    np.testing.assert_allclose(params, st.params, rtol=1e-9, atol=1e-9)
+    assert np.max(np.abs(err - st.err)) <= 1e-11 * np.max(np.abs(st.err))
+    assert accepted == st.accepted
+
+
+@pytest.mark.parametrize("name,colours", [("c1", (0, 40, 80)), ("tile_deep", (0, 20, 48))])
+def test_doublet_update_records_replay_on_another_context(name, colours):
+    """d3d_mh_colour (k_mh<..., true>) / d3d_export_updates / d3d_apply_updates with the doublet:
+    k_apply_updates<256, true> on c1, k_apply_updates<1024, true> on the 600-channel cube."""
+    check_update_records_replay(make_case(name), colours, line_shape=SHAPES["doublet"])
+
+
+@pytest.mark.parametrize("name,colours,rows", [("c1", (0, 40, 80, 13), (6, 16)),
+                                               ("tile_deep", (0, 20, 48), (11, 26))])
+def test_doublet_update_records_replay_clipped_on_another_region(name, colours, rows, monkeypatch):
+    """Records of whole colour classes, made on the whole cube with the doublet, replayed on a
+    context that holds only the rows `rows` of it: windows cut by the region's edge, windows
+    wholly outside it, spaxels outside it (no parameters to write).  Against O.replay_update of
+    the patched oracle on the same region, 1e-11 of the residual's peak; and the owner's own
+    updates (k_mh<..., true>) against O.mh_update."""
+    shape = SHAPES["doublet"]
+    monkeypatch.setattr(O, "gaussian_line", multiplet(*shape))
+    case = make_case(name)
+    D, H, W = case["D"], case["H"], case["W"]
+    fh, fw = case["fsf"].shape
+    r0, r1 = rows
+    sub = (slice(None), slice(r0, r1), slice(None))
+    with _lib.Engine((D, H, W), (fh, fw)) as a, _lib.Engine((D, r1 - r0, W), (fh, fw)) as b:
+        a.set_taps(case["fsf"], case["lsf"])
+        a.set_data(case["data"], case["var"], mask=case["mask"])
+        a.set_line_shape(*shape)
+        a.set_params(case["init"])
+        a.mh_config(case["min_b"], case["max_b"], 0.1, 35.0, seed=3, refresh_every=0)
+        err0 = a.residual()
+        b.set_taps(case["fsf"], case["lsf"])
+        b.set_data(np.ascontiguousarray(case["data"][sub]), np.ascontiguousarray(case["var"][sub]),
+                   mask=np.ascontiguousarray(case["mask"][r0:r1]))
+        b.set_line_shape(*shape)
+        b.set_params(np.ascontiguousarray(case["init"][r0:r1]))
+        b.upload_slot(_lib.SLOT_ERR, np.ascontiguousarray(err0[sub]))
+        own = O.MHState(case["data"], case["var"], case["mask"], case["fsf"], case["lsf"], case["init"],
+                        case["min_b"], case["max_b"], 0.1, 35.0, 3, err=err0)
+        st = O.MHState(case["data"][sub], case["var"][sub], case["mask"][r0:r1], case["fsf"], case["lsf"],
+                       case["init"][r0:r1], case["min_b"], case["max_b"], 0.1, 35.0, 3, err=err0[sub])
+        clipped = outside = 0
+        for colour in colours:
+            a.mh_colour(colour, 1)
+            cy, cx = divmod(colour, fw)
+            ys, xs = np.nonzero(case["mask"][cy::fh, cx::fw] == 1)
+            yy, xx = cy + ys * fh, cx + xs * fw
+            rec = a.export_updates((yy * W + xx).astype(np.int32))
+            np.testing.assert_array_equal(rec[:, 0], yy)
+            np.testing.assert_array_equal(rec[:, 1], xx)
+            for (y, x), r8 in zip(zip(yy, xx), rec):
+                O.mh_update(own, int(y), int(x), 1)
+                np.testing.assert_allclose(r8[5:], own.params[y, x], rtol=1e-9, atol=1e-9)
+                O.replay_update(st, int(y) - r0, int(x), r8[2:5], r8[5:8])
+                clipped += (y < r0 and y + (fh - 1) // 2 >= r0)
+                outside += (y + (fh - 1) // 2 < r0)
+            rec[:, 0] -= r0
+            b.apply_updates(rec)
+        assert clipped > 0 and outside > 0
+        got = b.download_slot(_lib.SLOT_ERR)
+        assert np.isfinite(got).all()
+        assert np.max(np.abs(got - st.err)) <= 1e-11 * np.max(np.abs(st.err))
+        whole = a.download_slot(_lib.SLOT_ERR)
+        assert np.max(np.abs(whole - own.err)) <= 1e-11 * np.max(np.abs(own.err))
+        # the region's rows of the owner's residual, bit for bit: the same f * G per cell
+        np.testing.assert_array_equal(got, whole[sub])
+        np.testing.assert_array_equal(b.get_params(), a.get_params()[r0:r1])
+
+
+def test_small_launch_kernel_wide_form_with_a_triplet(monkeypatch):
+    """The wide form of k_mh_small (partitioned 65..128-channel contexts) reading a multiplet line
+    table (k_mh_line_table<true>): the 128 x 30 x 40 two-part problem with the triplet, option
+    mh_small 1 against 0 bit for bit with small_parts > 0 asserted; and the mh_small = 1 chain,
+    two sweeps, against the patched oracle in part order."""
+    from tests.test_gpu_parity import check_wide_form_of_the_small_launch_kernel, wide_form_problem
+    shape = SHAPES["triplet"]
+    monkeypatch.setattr(O, "gaussian_line", multiplet(*shape))
+    check_wide_form_of_the_small_launch_kernel(line_shape=shape)
+    (D, H, W), fsf, lsf, data, var, mask, init, mn, mx, parts = wide_form_problem()
+    ra = float(mx[0] ** 2)
+    st = O.MHState(data, var, mask, fsf, lsf, init, mn, mx, 0.1, ra, 9)
+    with _lib.Engine((D, H, W), fsf.shape, options={"mh_small": 1}) as eng:
+        eng.set_taps(fsf, lsf)
+        eng.set_data(data, var, mask=mask)
+        eng.set_line_shape(*shape)
+        eng.set_parts([r for _, r in parts], [ph for ph, _ in parts])
+        assert eng.get_option("small_parts") > 0
+        eng.set_params(init)
+        eng.mh_config(mn, mx, 0.1, ra, seed=9, refresh_every=0)
+        accepted = eng.mh_sweeps(2, 1)
+        for s in (1, 2):
+            for ph in (0, 1):
+                for (y, x) in part_order(parts, ph, mask, *fsf.shape):
+                    O.mh_update(st, y, x, s)
+        live = mask == 1
+        np.testing.assert_allclose(eng.get_params()[live], st.params[live], rtol=1e-9, atol=1e-9)
         assert accepted == st.accepted
         err = eng.download_slot(_lib.SLOT_ERR)
         assert np.max(np.abs(err - st.err)) <= 1e-11 * np.max(np.abs(st.err))
