@@ -36,7 +36,22 @@ SYMBOLS = [
     "d3d_halo_exchange", "d3d_halo_pack", "d3d_halo_unpack", "d3d_halo_buffers",
     "d3d_halo_download", "d3d_halo_upload", "d3d_device_copy",
     "d3d_mh_colour", "d3d_export_updates", "d3d_apply_updates",
+    "d3d_post_begin", "d3d_post_schedule", "d3d_post_accumulate", "d3d_post_count", "d3d_post_get",
+    "d3d_post_end",
 ]
+
+# posterior moments (a table, so that tools/posterior_time.py can load the PARENT commit's library,
+# which lacks them, for its A/B: it empties the table and drops the names from SYMBOLS first)
+POST_PROTOTYPES = {
+    "d3d_post_begin": [C.c_int],
+    "d3d_post_schedule": [C.c_int, C.c_int],
+    "d3d_post_accumulate": [],
+    "d3d_post_count": [C.POINTER(C.c_int64)],
+    "d3d_post_get": [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    "d3d_post_end": [],
+}
+POST_CLEAN, POST_CONVOLVED = 1, 2                     # d3d_post_begin: bits of `what`
+POST_PARAMETERS, POST_CLEAN_CUBE, POST_CONVOLVED_CUBE = 0, 1, 2   # d3d_post_get: `which`
 
 PLAN_PARAMS = 16          # D3D_PLAN_PARAMS
 COMM_UID_BYTES = 128      # D3D_COMM_UID_BYTES
@@ -144,6 +159,8 @@ def load():
     lib.d3d_mh_colour.argtypes = [ctx_p, C.c_int, C.c_int]
     lib.d3d_export_updates.argtypes = [ctx_p, C.c_int, C.POINTER(C.c_int), dbl_p]
     lib.d3d_apply_updates.argtypes = [ctx_p, C.c_int, dbl_p]
+    for name, argtypes in POST_PROTOTYPES.items():
+        getattr(lib, name).argtypes = [ctx_p] + argtypes
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("d3d_version", "d3d_last_error", "d3d_source_hash", "d3d_has_experiments"):
@@ -599,3 +616,35 @@ class Engine(object):
         records = np.ascontiguousarray(records, dtype=np.float64).reshape(-1, 8)
         if records.shape[0]:
             _check(self._lib.d3d_apply_updates(self._ctx, records.shape[0], _dp(records)))
+
+    # -- posterior moments ------------------------------------------------------
+    def post_begin(self, what=POST_CLEAN | POST_CONVOLVED):
+        """Allocate and zero the running moments (include/deconv3d_hip.h: d3d_post_begin):
+        the (a, c, w, F) map always, ``what`` bit 0 the clean cube, bit 1 the convolved cube."""
+        _check(self._lib.d3d_post_begin(self._ctx, int(what)))
+
+    def post_schedule(self, first_sweep, every=1):
+        """mh_sweeps / mh_sweeps_batch take the state after the sweeps first_sweep,
+        first_sweep + every, ... as samples."""
+        _check(self._lib.d3d_post_schedule(self._ctx, int(first_sweep), int(every)))
+
+    def post_accumulate(self):
+        """The current parameters as one more sample."""
+        _check(self._lib.d3d_post_accumulate(self._ctx))
+
+    def post_count(self):
+        n = C.c_int64(0)
+        _check(self._lib.d3d_post_count(self._ctx, C.byref(n)))
+        return n.value
+
+    def post_get(self, which):
+        """(mean, M2) of the parameter map (which = 0: (H,W,4), columns a, c, w, F), the clean
+        cube (1) or the convolved cube (2: (D,H,W)); variance = M2 / (count - 1)."""
+        shape = self.shape[1:] + (4,) if int(which) == POST_PARAMETERS else self.shape
+        mean = np.empty(shape, dtype=np.float64)
+        m2 = np.empty(shape, dtype=np.float64)
+        _check(self._lib.d3d_post_get(self._ctx, int(which), _dp(mean), _dp(m2)))
+        return mean, m2
+
+    def post_end(self):
+        _check(self._lib.d3d_post_end(self._ctx))

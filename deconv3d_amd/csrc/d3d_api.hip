@@ -396,6 +396,52 @@ int build_colour_lists(d3d_ctx *c) {
 }
 
 
+// ---- posterior moments (d3d_post_*) ------------------------------------------------------
+void post_free(d3d_ctx *c) {
+    for (double *&p : c->post_cube) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    if (c->post_map) (void)hipFree(c->post_map);
+    c->post_map = nullptr;
+    c->post_on = false;
+    c->post_what = 0;
+    c->post_n = 0;
+    c->post_every = 0;
+}
+
+// count 0, accumulators zero (Welford's first sample starts from mean = M2 = 0)
+int post_reset(d3d_ctx *c) {
+    if (!c->post_on) return 0;
+    c->post_n = 0;
+    for (double *p : c->post_cube)
+        if (p) HIP_TRY(hipMemsetAsync(p, 0, c->cube_elems * sizeof(double), c->stream));
+    HIP_TRY(hipMemsetAsync(c->post_map, 0, (size_t)c->HW * 8 * sizeof(double), c->stream));
+    return 0;
+}
+
+// the chain state as one more sample
+int post_sample(d3d_ctx *c) {
+    NEED(c->post_on, D3D_ERR_STATE, "posterior moments not begun (d3d_post_begin)");
+    NEED(!c->tiled, D3D_ERR_UNSUPPORTED,
+         "posterior moments on a tile: the parameters of its frame belong to other ranks");
+    NEED(c->have_params, D3D_ERR_STATE, "parameters not set");
+    if (c->post_what & 2) {
+        NEED(c->have_taps, D3D_ERR_STATE, "taps not set");
+        if (int rc = forward_into(c, c->slot[D3D_SLOT_SIM], false)) return rc;
+    }
+    if (int rc = launch_post_accum(c)) return rc;
+    ++c->post_n;
+    return 0;
+}
+
+// sweep s (the caller's numbering) is one d3d_post_schedule asked for
+bool post_due(const d3d_ctx *c, int s) {
+    return c->post_on && c->post_every > 0 && s >= c->post_first &&
+           (s - c->post_first) % c->post_every == 0;
+}
+
+
 // ---- per-context options (d3d_ctx_set_option) -----------------------------------------
 // Every switch of the library is a field of the context.  The environment is only the
 // source of a new context's DEFAULTS (D3D_<KEY>, read once in d3d_ctx_create), so two
@@ -437,6 +483,7 @@ const OptDesc g_opts[] = {
     {"xcd_remap", "D3D_XCD_REMAP", &d3d_ctx::xcd_remap, OPT_LAUNCH, 0, 1},
     {"alt_dir", "D3D_ALT_DIR", &d3d_ctx::alt_dir, OPT_LAUNCH, 0, 1},
     {"stagger", "D3D_STAGGER", &d3d_ctx::stagger, OPT_LAUNCH, 0, 1 << 20},
+    {"post_nt", "D3D_POST_NT", &d3d_ctx::post_nt, OPT_LAUNCH, 0, 1},
 #ifdef D3D_EXPERIMENTS
     // measured-but-not-faster variants of DESIGN.md section 3 (make EXPERIMENTS=1)
     {"mh_chain", "D3D_MH_CHAIN", &d3d_ctx::mh_chain_opt, OPT_MH, 0, 1},
@@ -632,6 +679,9 @@ int d3d_ctx_destroy(d3d_ctx *c) {
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->halo_send) (void)hipFree(c->halo_send);
     if (c->halo_recv) (void)hipFree(c->halo_recv);
+    for (double *p : c->post_cube)
+        if (p) (void)hipFree(p);
+    if (c->post_map) (void)hipFree(c->post_map);
     for (hipEvent_t e : c->halo_ev) (void)hipEventDestroy(e);
     for (int s = 0; s < D3D_SLOT_COUNT; ++s)
         if (c->slot[s]) (void)hipFree(c->slot[s]);
@@ -690,7 +740,8 @@ int d3d_set_taps(d3d_ctx *c, const double *fsf, const double *lsf, double thr) {
     c->h_has_lsf = lsf != nullptr;
     if (lsf) c->h_lsf.assign(lsf, lsf + c->D);
     c->h_thr = thr;
-    return set_taps_impl(c, c->h_fsf.data(), c->h_has_lsf ? c->h_lsf.data() : nullptr, thr);
+    if (int rc = set_taps_impl(c, c->h_fsf.data(), c->h_has_lsf ? c->h_lsf.data() : nullptr, thr)) return rc;
+    return post_reset(c);  // moments over two instrument models mean nothing
 }
 
 int d3d_ctx_set_option(d3d_ctx *c, const char *key, long value) {
@@ -1020,7 +1071,7 @@ int d3d_set_data(d3d_ctx *c, const double *data, const double *var, double var_s
     c->have_data = true;
     c->err_valid = false;
     pend_clear(c);
-    return D3D_OK;
+    return post_reset(c);  // moments over two data sets mean nothing
 }
 
 int d3d_set_params(d3d_ctx *c, const double *params) {
@@ -1063,7 +1114,7 @@ int d3d_set_line_shape(d3d_ctx *c, int K, const double *offsets, const double *r
     c->line = L;
     c->err_valid = false;
     c->props_sweep = -1;
-    return D3D_OK;
+    return post_reset(c);  // moments over two line models mean nothing
 }
 
 int d3d_get_params(d3d_ctx *c, double *params) {
@@ -1515,7 +1566,7 @@ int d3d_mh_sweeps(d3d_ctx *c, int n_sweeps, int first_sweep, int keep_one_in, do
             for (int t = s; t <= last; ++t) {
                 const bool saved = t % keep_one_in == 0 && (chain_out || dlog_out);
                 const bool refresh = c->refresh_every > 0 && t % c->refresh_every == 0;
-                if (saved || refresh) {
+                if (saved || refresh || post_due(c, t)) {
                     last = t;
                     break;
                 }
@@ -1565,6 +1616,8 @@ int d3d_mh_sweeps(d3d_ctx *c, int n_sweeps, int first_sweep, int keep_one_in, do
             int rc = snap_push(c, snaps, s / keep_one_in, chain_out, dlog_out);
             if (rc) return rc;
         }
+        if (post_due(c, s))  // d3d_post_schedule: this sweep's state into the running moments
+            if (int rc = post_sample(c)) return rc;
         // lib/run.py:521-534: squash the error creep with a fresh residual.  A tile
         // first gathers the parameters of the spaxels of its frame from their owners.
         if (c->refresh_every > 0 && s % c->refresh_every == 0) {
@@ -1646,14 +1699,20 @@ int d3d_mh_sweeps_batch(d3d_ctx **ctxs, int n_ctx, int n_sweeps, int first_sweep
     auto lo = [&](int r) { return dlog_out ? dlog_out[r] : nullptr; };
     std::function<int(int)> after;
     std::function<int()> drain;
-    if (saving) {
+    bool scheduled = false;  // d3d_post_schedule on any of them
+    for (int r = 0; r < n_ctx; ++r) scheduled = scheduled || (ctxs[r]->post_on && ctxs[r]->post_every > 0);
+    if (saving || scheduled)
         after = [&](int s) {
-            if (s % keep_one_in) return 0;
+            if (saving && s % keep_one_in == 0)
+                for (int r = 0; r < n_ctx; ++r)
+                    if (co(r) || lo(r))
+                        if (int rc = snap_push(ctxs[r], snaps[r], s / keep_one_in, co(r), lo(r))) return rc;
             for (int r = 0; r < n_ctx; ++r)
-                if (co(r) || lo(r))
-                    if (int rc = snap_push(ctxs[r], snaps[r], s / keep_one_in, co(r), lo(r))) return rc;
+                if (post_due(ctxs[r], s))
+                    if (int rc = post_sample(ctxs[r])) return rc;
             return 0;
         };
+    if (saving) {
         drain = [&]() {
             for (int r = 0; r < n_ctx; ++r)
                 while (snaps[r].count > 0)
@@ -1695,6 +1754,84 @@ int d3d_flush(d3d_ctx *c) {
     NEED(c, D3D_ERR_INVALID, "ctx is NULL");
     HIP_TRY(hipSetDevice(c->device));
     return flush_pending(c);
+}
+
+int d3d_post_begin(d3d_ctx *c, int what) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    NEED(what >= 0 && what <= 3, D3D_ERR_INVALID,
+         "what = %d: bit 0 the clean cube, bit 1 the convolved cube (0..3)", what);
+    NEED(!c->tiled, D3D_ERR_UNSUPPORTED,
+         "posterior moments on a tile: the parameters of its frame belong to other ranks");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    post_free(c);
+    hipError_t e = hipMalloc(&c->post_map, (size_t)c->HW * 8 * sizeof(double));
+    for (int k = 0; k < 4 && e == hipSuccess; ++k)
+        if (what & (1 << (k / 2))) e = hipMalloc(&c->post_cube[k], c->cube_elems * sizeof(double));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // the context stays usable for the chain
+        post_free(c);
+        return fail(D3D_ERR_HIP, "posterior accumulators (%d cubes of %zu bytes): %s",
+                    2 * ((what & 1) + (what >> 1)), c->cube_elems * sizeof(double), hipGetErrorString(e));
+    }
+    c->post_on = true;
+    c->post_what = what;
+    return post_reset(c);
+}
+
+int d3d_post_schedule(d3d_ctx *c, int first_sweep, int every) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    NEED(first_sweep >= 0, D3D_ERR_INVALID, "first_sweep = %d is negative", first_sweep);
+    NEED(every >= 1, D3D_ERR_INVALID, "every = %d: accumulate one sweep in how many (>= 1)", every);
+    NEED(c->post_on, D3D_ERR_STATE, "posterior moments not begun (d3d_post_begin)");
+    c->post_first = first_sweep;
+    c->post_every = every;
+    return D3D_OK;
+}
+
+int d3d_post_accumulate(d3d_ctx *c) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    return post_sample(c);
+}
+
+int d3d_post_count(d3d_ctx *c, int64_t *n) {
+    NEED(c && n, D3D_ERR_INVALID, "NULL argument");
+    *n = c->post_on ? c->post_n : 0;
+    return D3D_OK;
+}
+
+int d3d_post_get(d3d_ctx *c, int which, double *mean, double *m2) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    NEED(which >= 0 && which <= 2, D3D_ERR_INVALID,
+         "which = %d: 0 the parameter map, 1 the clean cube, 2 the convolved cube", which);
+    NEED(c->post_on, D3D_ERR_STATE, "posterior moments not begun (d3d_post_begin)");
+    NEED(which == 0 || (c->post_what & which), D3D_ERR_STATE,
+         "the %s cube's moments were not begun (d3d_post_begin what = %d)",
+         which == 1 ? "clean" : "convolved", c->post_what);
+    HIP_TRY(hipSetDevice(c->device));
+    if (which == 0) {
+        const size_t bytes = (size_t)c->HW * 4 * sizeof(double);
+        if (mean) HIP_TRY(hipMemcpyAsync(mean, c->post_map, bytes, hipMemcpyDeviceToHost, c->stream));
+        if (m2)
+            HIP_TRY(hipMemcpyAsync(m2, c->post_map + (size_t)c->HW * 4, bytes, hipMemcpyDeviceToHost,
+                                   c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return D3D_OK;
+    }
+    if (mean)
+        if (int rc = download_cube(c, c->post_cube[2 * (which - 1)], mean)) return rc;
+    if (m2)
+        if (int rc = download_cube(c, c->post_cube[2 * (which - 1) + 1], m2)) return rc;
+    return D3D_OK;
+}
+
+int d3d_post_end(d3d_ctx *c) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    post_free(c);
+    return D3D_OK;
 }
 
 int d3d_get_dlog(d3d_ctx *c, double *out_hw) {

@@ -263,6 +263,16 @@ struct d3d_ctx {
     int march_mode = 2;
     int sp_nt = 256;              // spectral / spatial block size
     int march_stamp = 0;          // option march_stamp (EXPERIMENTS builds): phase stamps of the march kernel
+    // posterior moments (d3d_post_*): running mean and M2 = sum of squared deviations of the
+    // samples' clean cube, convolved cube and (a, c, w, F) map, updated on the device after the
+    // scheduled sweeps (k_post_accum).  Nothing is allocated before d3d_post_begin.
+    bool post_on = false;
+    int post_what = 0;             // bit 0 clean cube, bit 1 convolved cube
+    double *post_cube[4] = {};     // clean mean | clean M2 | convolved mean | convolved M2, device layout
+    double *post_map = nullptr;    // [2][HW*4]: mean | M2 of (a, c, w, F)
+    int64_t post_n = 0;            // samples accumulated
+    int post_first = 0, post_every = 0;  // d3d_post_schedule (every == 0: none)
+    int post_nt = 0;               // option post_nt = 1: the accumulators' loads and stores non-temporal
 };
 
 namespace d3dh {
@@ -280,6 +290,9 @@ int launch_spatial(d3d_ctx *c, const double *in, double *out, const double *data
                    bool fuse_lsf = false);
 // params -> SLOT_TMP0 (LSF lines) -> dst (sim, or residual when resid)
 int forward_into(d3d_ctx *c, double *dst, bool resid);
+// d3d_post.hip: one sample (the chain state; SLOT_SIM holds its convolved cube when that moment
+// is on) into the running moments, as sample number c->post_n + 1
+int launch_post_accum(d3d_ctx *c);
 bool zmajor_ok(const d3d_ctx *c);
 // LSF (x) FSF of c->stage in the reference layout (D,H,W), in place (zmajor_ok())
 int launch_zmajor_convolve(d3d_ctx *c);

@@ -35,7 +35,7 @@ from os.path import splitext
 
 import numpy as np
 
-from . import _lib
+from . import _lib, posterior as _posterior
 from .cube import Cube, read_fits
 from .instruments import Instrument
 from .line_models import (LineModel, SingleGaussianLineModel, SINGLE_LINE_SHAPE,
@@ -82,6 +82,22 @@ class Run:
     chain; a checkpoint holds all R chains (``<prefix>_parameters.npy`` is that 4-D array, chain
     r > 0's slots are ``<prefix>_c<r>_chain.npy``) and resumes R chains.  A custom
     (host-evaluated) line model advances its R chains one after the other.
+
+    ``posterior_burn_in=B`` (default ``None``: off, nothing allocated or launched) keeps, on the
+    device, running means and standard deviations of the SAMPLES' clean cube, convolved cube,
+    parameters and integrated flux: every chain accumulates its state after the sweeps
+    ``B, B + posterior_every, ...`` (with ``keep_one_in = 1`` exactly ``run.chain[B::every]``)
+    without a cube crossing to the host.  ``run.posterior`` is a
+    :class:`deconv3d_amd.posterior.PosteriorMoments` (``count``, ``clean_mean``, ``clean_std``,
+    ``convolved_mean``, ``convolved_std``, ``parameters_mean``, ``parameters_std``, ``flux_mean``,
+    ``flux_std``, ``clean_cube()``, ``convolved_cube()``, ``save(prefix)``), downloaded on first
+    access; with ``chains=R`` it pools the chains and ``run.posteriors[r]`` is chain r's.  Where
+    the FSF leaves single spaxels unidentified, ``posterior.convolved_mean`` fits the data
+    while the cube of the mean map (``run.convolved_cube``, the reference's estimator, unchanged)
+    does not.  A run that stops before sweep B has ``count == 0`` and NaN
+    arrays.  A host-evaluated line model raises ``NotImplementedError``.  The accumulators are
+    not part of a checkpoint: a ``resume_state=`` run starts fresh ones, scheduled in this
+    segment's sweep numbering.  Costs four more cubes of device memory per chain.
     """
 
     def __init__(
@@ -106,7 +122,12 @@ class Run:
         resume_state=None,
         chain_file=None,
         chains=1,
+        posterior_burn_in=None,
+        posterior_every=1,
     ):
+        if posterior_burn_in is not None:     # (before anything else: no device work yet)
+            posterior_burn_in, posterior_every = _posterior.check_schedule(posterior_burn_in,
+                                                                           posterior_every)
         # lib/run.py:112-114
         assert keep_one_in > 0, "keep_one_in= MUST be a positive integer"
         assert write_every > 0, "write_every= MUST be a positive integer"
@@ -194,6 +215,11 @@ class Run:
             if not isinstance(self.model, LineModel):
                 raise TypeError("Provided model is not a LineModel")
         self._host_model = not self._model_is_on_device()
+        if posterior_burn_in is not None and self._host_model:
+            raise NotImplementedError(
+                "posterior_burn_in=: the line model %s is evaluated on the host; the device "
+                "accumulates posterior moments only for the models it evaluates itself"
+                % type(self.model).__name__)
         # (offsets, ratios) of the device's unit line; None for a host-evaluated model
         self.line_shape = None if self._host_model else device_line_shape(self.model)
         min_boundaries = np.array(self.model.min_boundaries(self), dtype=np.float64)
@@ -344,6 +370,9 @@ class Run:
                 eng.mh_config(min_boundaries, max_boundaries, jumping_amplitude,
                               gibbs_apriori_variance, seed=self.seed + r,
                               refresh_every=refresh_every)
+                if posterior_burn_in is not None:
+                    eng.post_begin()
+                    eng.post_schedule(posterior_burn_in, posterior_every)
         if resume_state is not None:
             if host_chain is None:
                 for eng in self.engines:
@@ -444,6 +473,17 @@ class Run:
                                    meta=self.cube.meta, x=cube.x, y=cube.y, z=cube.z)
         self.clean_cube = Cube(data=self.simulate_clean(cube_shape, self.parameters),
                                meta=self.cube.meta, x=cube.x, y=cube.y, z=cube.z)
+        # posterior moments of the samples' cubes (still on the device: fetched on access)
+        self.posteriors, self.posterior = None, None
+        if posterior_burn_in is not None:
+            self.posteriors = [_posterior.PosteriorMoments.from_engine(eng, self.cube)
+                               for eng in self.engines]
+            self.posterior = self.posteriors[0] if n_chains == 1 else \
+                _posterior.pooled(self.posteriors, self.cube)
+            if self.posterior.count == 0:
+                self.logger.warning("posterior_burn_in=%d: the run stopped at iteration %d, before "
+                                    "the first accumulated sweep; run.posterior holds no sample"
+                                    % (posterior_burn_in, self.iterations_done))
 
     # ------------------------------------------------------------------------
 

@@ -47,7 +47,8 @@ cube = inst.build_cube(clean + rng.normal(0., sigma, clean.shape))
 t0 = time.perf_counter()
 run = Run(cube, inst, variance=np.full(clean.shape, sigma ** 2), max_iterations=iterations,
           keep_one_in=10, min_acceptance_rate=0., jump_amplitude=[0., 0.5, 0.2],
-          gibbs_apriori_variance=100., seed=1)   # amplitude prior, as tests/read_mat.py:109-119 sets one
+          gibbs_apriori_variance=100., seed=1,   # amplitude prior, as tests/read_mat.py:109-119 sets one
+          posterior_burn_in=max(1, iterations // 2))   # mean / std of the samples' cubes, kept on the device
 dt = time.perf_counter() - t0
 burn = run.chain.shape[0] // 2
 post = run.chain[burn:].mean(axis=0)                # posterior means over the second half
@@ -59,6 +60,12 @@ print("reduced chi2: last sample %.4f, extracted parameters %.4f; their convolve
       "rms %.2f %% of its peak" % (np.mean(((cube.data - last) / sigma) ** 2),
                                    np.mean(((cube.data - model) / sigma) ** 2),
                                    100. * np.sqrt(np.mean((model - clean) ** 2)) / clean.max()))
+# The mean of the samples' convolved CUBES (run.posterior, accumulated on the device over the second
+# half of the sweeps) beside the cube of the mean parameter MAP (run.convolved_cube)
+post_cube = run.posterior.convolved_mean
+print("reduced chi2: posterior mean cube %.4f (%d samples; median error bar %.3g) beside the cube of the mean map %.4f" % (
+    np.mean(((cube.data - post_cube) / sigma) ** 2), run.posterior.count, np.median(run.posterior.convolved_std),
+    np.mean(((cube.data - model) / sigma) ** 2)))
 # Per-spaxel parameters are what a 13x13-pixel seeing leaves of them: neighbours trade
 # flux, so single spaxels scatter far more than the convolved model does.
 bright = truth[..., 0] > 3.0

@@ -94,7 +94,8 @@ int d3d_timer_stop(d3d_ctx *ctx, double *elapsed_ms);
  * Keys: mh_defer 0|1|2, mh_zblocks, mh_layers 0(auto)|1|2|3,
  * mh_wide, mh_props, halo_timing, mh_zigzag, mh_nt_ivar -1(auto)|0|1, mh_nt, uniform_ivar, conv_rows,
  * conv_zb, conv_hy, spatial_sep, sep_fuse, spatial_mode, march_hy, zmajor, zmajor_hy,
- * spectral_dense, spectral_blocks, lines_dense, lines_rounds, spatial_nt, xcd_remap, alt_dir, stagger; a build with
+ * spectral_dense, spectral_blocks, lines_dense, lines_rounds, spatial_nt, xcd_remap, alt_dir, stagger,
+ * post_nt; a build with
  * `make EXPERIMENTS=1` adds mh_chain, mh_prio, mh_maxit, mh_flow, mh_pair, spectral_shfl, fuse_lsf, march_pf,
  * march_one, march_stamp.  Unknown key or value out of range: D3D_ERR_INVALID.
  * d3d_ctx_get_option also answers the read-only key "chain_parts": how many of the
@@ -242,6 +243,40 @@ int d3d_variance_is_uniform(d3d_ctx *ctx, int *out);
  * is bit-identical for every value.  Option mh_layers = 1|2|3 forces a depth; a
  * partitioned ctx reports the most layers any of its parts uses. */
 int d3d_mh_layers(d3d_ctx *ctx, int *out);
+
+/* ---- posterior moments -------------------------------------------------- */
+/* The reference's only estimator is the mean of the last 20 % of the saved parameter chain
+ * (Run.extract_parameters, lib/run.py:581-593), and its cubes are built from that mean map
+ * (lib/run.py:597-652).  These entries keep, on the device, the running mean and the sum of
+ * squared deviations M2 (Welford) of the SAMPLES' cubes -- what np.mean / np.var over
+ * simulate_clean / simulate_convolved (lib/run.py:597-652) of every chain slot would give, with no
+ * cube crossing to the host per sample -- and of the parameters with the integrated flux
+ * F = a w sqrt(2 pi) sum_k ratios[k].  variance = M2 / (n - 1).  Off until begun: a ctx that
+ * never calls d3d_post_begin allocates and launches nothing for them. */
+
+/* Allocate and zero the accumulators: the (H,W,4) map of (a, c, w, F) always; what bit 0 the
+ * clean cube (lib/run.py:597-621 per sample), bit 1 the convolved cube (lib/run.py:623-652 per
+ * sample): two cubes each.  Calling it again starts afresh.  A tile ctx (d3d_set_tile) is
+ * D3D_ERR_UNSUPPORTED; an allocation failure is D3D_ERR_HIP, frees what it got and leaves the ctx
+ * usable for the chain.  d3d_set_line_shape, d3d_set_taps and d3d_set_data on a ctx with
+ * accumulators reset them (count 0). */
+int d3d_post_begin(d3d_ctx *ctx, int what);
+/* d3d_mh_sweeps and d3d_mh_sweeps_batch (every ctx of the batch that has a schedule) take the
+ * state after every sweep s >= first_sweep with (s - first_sweep) % every == 0 as a sample -- s
+ * in the caller's numbering, the reference's cur_iteration (lib/run.py:344-353), where the saved
+ * sweeps are copied to the chain (lib/run.py:447-451).  every >= 1. */
+int d3d_post_schedule(d3d_ctx *ctx, int first_sweep, int every);
+/* The current parameters as one more sample (callers that drive d3d_mh_phase / d3d_mh_colour
+ * themselves; tests).  Needs parameters, and taps for the convolved cube: D3D_ERR_STATE. */
+int d3d_post_accumulate(d3d_ctx *ctx);
+/* *n = samples accumulated since d3d_post_begin or the last reset. */
+int d3d_post_count(d3d_ctx *ctx, int64_t *n);
+/* which = 0: the map, mean and m2 (H,W,4) each; 1: the clean cube; 2: the convolved cube, (D,H,W)
+ * each in the reference's layout (lib/run.py:146-149).  Either pointer may be NULL.  A moment
+ * that was not begun is D3D_ERR_STATE. */
+int d3d_post_get(d3d_ctx *ctx, int which, double *mean, double *m2);
+/* Free the accumulators and drop the schedule (d3d_ctx_destroy does it too). */
+int d3d_post_end(d3d_ctx *ctx);
 
 /* ---- spatial tiling (one chain over several GPUs) --------- */
 /* The reference has no counterpart (single process).  What makes tiling possible is
