@@ -9,6 +9,7 @@ from .instruments import MUSE, Instrument  # noqa: F401
 from .line_models import GaussianMultipletLineModel, LineModel, SingleGaussianLineModel  # noqa: F401
 from .masks import above_percentile  # noqa: F401
 from .math_utils import median_clip  # noqa: F401
+from . import adapt  # noqa: F401
 from . import posterior  # noqa: F401
 from .posterior import PosteriorMoments  # noqa: F401
 from .run import Run, logger  # noqa: F401

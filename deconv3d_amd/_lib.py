@@ -38,6 +38,7 @@ SYMBOLS = [
     "d3d_mh_colour", "d3d_export_updates", "d3d_apply_updates",
     "d3d_post_begin", "d3d_post_schedule", "d3d_post_accumulate", "d3d_post_count", "d3d_post_get",
     "d3d_post_end",
+    "d3d_adapt_begin", "d3d_adapt_get", "d3d_adapt_set", "d3d_adapt_end",
 ]
 
 # posterior moments (a table, so that tools/posterior_time.py can load the PARENT commit's library,
@@ -49,6 +50,14 @@ POST_PROTOTYPES = {
     "d3d_post_count": [C.POINTER(C.c_int64)],
     "d3d_post_get": [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)],
     "d3d_post_end": [],
+}
+# per-spaxel jump scales (a table for the same reason: tools that load the parent's library)
+ADAPT_PROTOTYPES = {
+    "d3d_adapt_begin": [C.c_double, C.c_int, C.c_int64, C.c_double, C.c_double, C.c_double],
+    "d3d_adapt_get": [C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_int64),
+                      C.POINTER(C.c_int64)],
+    "d3d_adapt_set": [C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_int64, C.c_int64],
+    "d3d_adapt_end": [],
 }
 POST_CLEAN, POST_CONVOLVED = 1, 2                     # d3d_post_begin: bits of `what`
 POST_PARAMETERS, POST_CLEAN_CUBE, POST_CONVOLVED_CUBE = 0, 1, 2   # d3d_post_get: `which`
@@ -159,7 +168,7 @@ def load():
     lib.d3d_mh_colour.argtypes = [ctx_p, C.c_int, C.c_int]
     lib.d3d_export_updates.argtypes = [ctx_p, C.c_int, C.POINTER(C.c_int), dbl_p]
     lib.d3d_apply_updates.argtypes = [ctx_p, C.c_int, dbl_p]
-    for name, argtypes in POST_PROTOTYPES.items():
+    for name, argtypes in list(POST_PROTOTYPES.items()) + list(ADAPT_PROTOTYPES.items()):
         getattr(lib, name).argtypes = [ctx_p] + argtypes
     for name in SYMBOLS:
         fn = getattr(lib, name)
@@ -648,3 +657,39 @@ class Engine(object):
 
     def post_end(self):
         _check(self._lib.d3d_post_end(self._ctx))
+
+    # -- per-spaxel jump scales ---------------------------------------------------
+    def adapt_begin(self, target=0.25, window=50, last_sweep=0, gain=2.0, scale_range=(1e-3, 1e3)):
+        """Allocate the (H,W) jump scale map (all 1) and accept counters (include/deconv3d_hip.h:
+        d3d_adapt_begin): every ``window`` sweeps up to sweep ``last_sweep`` each spaxel's scale
+        moves towards the acceptance rate ``target``; ``window = 0`` keeps a fixed map."""
+        _check(self._lib.d3d_adapt_begin(self._ctx, float(target), int(window), int(last_sweep),
+                                         float(gain), float(scale_range[0]), float(scale_range[1])))
+
+    def adapt_get(self):
+        """(scale map, accepted counters, sweeps counted since they were cleared, steps taken)."""
+        scale = np.empty(self.shape[1:], dtype=np.float64)
+        acc = np.empty(self.shape[1:], dtype=np.uint32)
+        n_win, k = C.c_int64(0), C.c_int64(0)
+        _check(self._lib.d3d_adapt_get(self._ctx, _dp(scale), acc.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                       C.byref(n_win), C.byref(k)))
+        return scale, acc, n_win.value, k.value
+
+    def adapt_set(self, scale=None, accepted=None, n_win=0, k=0):
+        """Install a scale map and / or counters (resume; a fixed map with ``window = 0``)."""
+        hw = self.shape[1:]
+        sp = ap = None
+        if scale is not None:
+            scale = np.ascontiguousarray(scale, dtype=np.float64)
+            if scale.shape != hw:
+                raise ValueError("scale map MUST have shape %s, got %s" % (hw, scale.shape))
+            sp = _dp(scale)
+        if accepted is not None:
+            accepted = np.ascontiguousarray(accepted, dtype=np.uint32)
+            if accepted.shape != hw:
+                raise ValueError("accepted map MUST have shape %s, got %s" % (hw, accepted.shape))
+            ap = accepted.ctypes.data_as(C.POINTER(C.c_uint32))
+        _check(self._lib.d3d_adapt_set(self._ctx, sp, ap, int(n_win), int(k)))
+
+    def adapt_end(self):
+        _check(self._lib.d3d_adapt_end(self._ctx))

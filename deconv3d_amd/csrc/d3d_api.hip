@@ -410,6 +410,26 @@ void post_free(d3d_ctx *c) {
     c->post_every = 0;
 }
 
+void adapt_free(d3d_ctx *c) {
+    if (c->jscale) (void)hipFree(c->jscale);
+    if (c->jacc) (void)hipFree(c->jacc);
+    c->jscale = nullptr;
+    c->jacc = nullptr;
+    c->adapt_on = false;
+    c->adapt_n_win = c->adapt_k = 0;
+    c->props_sweep = -1;
+}
+
+// The kernels that make proposals from parameters they keep to themselves across sweeps
+// (EXPERIMENTS builds) never see a scale map change: refused with adaptation on.
+int adapt_kernels_ok(const d3d_ctx *c) {
+    NEED(!c->mh_chain_opt && !c->mh_flow && !c->mh_pair, D3D_ERR_UNSUPPORTED,
+         "per-spaxel jump scales (d3d_adapt_begin) with option %s: k_mh_chain, k_mh_flow and k_mh_pair "
+         "keep their proposals' inputs across sweeps",
+         c->mh_chain_opt ? "mh_chain" : c->mh_flow ? "mh_flow" : "mh_pair");
+    return 0;
+}
+
 // count 0, accumulators zero (Welford's first sample starts from mean = M2 = 0)
 int post_reset(d3d_ctx *c) {
     if (!c->post_on) return 0;
@@ -682,6 +702,7 @@ int d3d_ctx_destroy(d3d_ctx *c) {
     for (double *p : c->post_cube)
         if (p) (void)hipFree(p);
     if (c->post_map) (void)hipFree(c->post_map);
+    adapt_free(c);
     for (hipEvent_t e : c->halo_ev) (void)hipEventDestroy(e);
     for (int s = 0; s < D3D_SLOT_COUNT; ++s)
         if (c->slot[s]) (void)hipFree(c->slot[s]);
@@ -751,6 +772,11 @@ int d3d_ctx_set_option(d3d_ctx *c, const char *key, long value) {
     NEED(opt_value_ok(*o, value), D3D_ERR_INVALID, "option %s: value %ld out of range", key, value);
     if (c->*(o->field) == (int)value) return D3D_OK;
     HIP_TRY(hipSetDevice(c->device));
+    if (c->adapt_on && value != 0 &&
+        (!strcmp(key, "mh_chain") || !strcmp(key, "mh_flow") || !strcmp(key, "mh_pair")))
+        return fail(D3D_ERR_UNSUPPORTED,
+                    "option %s with per-spaxel jump scales on (d3d_adapt_begin): the kernel keeps its "
+                    "proposals' inputs across sweeps", key);
     if (o->kind == OPT_MH)  // pending layers belong to the old kernel selection
         if (int rc = flush_pending(c)) return rc;
     c->*(o->field) = (int)value;
@@ -1618,6 +1644,8 @@ int d3d_mh_sweeps(d3d_ctx *c, int n_sweeps, int first_sweep, int keep_one_in, do
         }
         if (post_due(c, s))  // d3d_post_schedule: this sweep's state into the running moments
             if (int rc = post_sample(c)) return rc;
+        if (c->adapt_on)     // d3d_adapt_begin: the sweep that fills a window moves the jump scales
+            if (int rc = d3dh::adapt_after_sweep(c, s)) return rc;
         // lib/run.py:521-534: squash the error creep with a fresh residual.  A tile
         // first gathers the parameters of the spaxels of its frame from their owners.
         if (c->refresh_every > 0 && s % c->refresh_every == 0) {
@@ -1834,6 +1862,84 @@ int d3d_post_end(d3d_ctx *c) {
     return D3D_OK;
 }
 
+int d3d_adapt_begin(d3d_ctx *c, double target, int window, int64_t last_sweep, double gain,
+                    double scale_min, double scale_max) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    NEED(target > 0.0 && target < 1.0, D3D_ERR_INVALID, "target = %g: an acceptance rate inside (0, 1)", target);
+    NEED(window >= 0, D3D_ERR_INVALID, "window = %d is negative (0: a fixed map that never adapts)", window);
+    NEED(gain > 0.0 && std::isfinite(gain), D3D_ERR_INVALID, "gain = %g: a positive number", gain);
+    NEED(std::isfinite(scale_min) && std::isfinite(scale_max) && scale_min > 0.0 && scale_max > 0.0,
+         D3D_ERR_INVALID, "scale range (%g, %g): finite, positive numbers", scale_min, scale_max);
+    NEED(scale_min <= scale_max, D3D_ERR_INVALID, "scale range: min %g > max %g", scale_min, scale_max);
+    NEED(!c->tiled, D3D_ERR_UNSUPPORTED,
+         "per-spaxel jump scales on a tile: a window's scale steps would have to follow the ranks' phases");
+    if (int rc = adapt_kernels_ok(c)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    adapt_free(c);
+    hipError_t e = hipMalloc(&c->jscale, (size_t)c->HW * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&c->jacc, (size_t)c->HW * sizeof(unsigned));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // the context stays usable for the chain
+        adapt_free(c);
+        return fail(D3D_ERR_HIP, "jump scale map (%ld spaxels): %s", c->HW, hipGetErrorString(e));
+    }
+    std::vector<double> ones((size_t)c->HW, 1.0);
+    HIP_TRY(hipMemcpy(c->jscale, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(c->jacc, 0, (size_t)c->HW * sizeof(unsigned)));
+    c->adapt_target = target;
+    c->adapt_window = window;
+    c->adapt_last = last_sweep;
+    c->adapt_gain = gain;
+    c->adapt_min = scale_min;
+    c->adapt_max = scale_max;
+    c->adapt_n_win = c->adapt_k = 0;
+    c->adapt_on = true;
+    c->props_sweep = -1;
+    return D3D_OK;
+}
+
+int d3d_adapt_get(d3d_ctx *c, double *scale_hw, uint32_t *accepted_hw, int64_t *n_win, int64_t *k) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    NEED(c->adapt_on, D3D_ERR_STATE, "per-spaxel jump scales not begun (d3d_adapt_begin)");
+    HIP_TRY(hipSetDevice(c->device));
+    if (scale_hw)
+        HIP_TRY(hipMemcpyAsync(scale_hw, c->jscale, (size_t)c->HW * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (accepted_hw)
+        HIP_TRY(hipMemcpyAsync(accepted_hw, c->jacc, (size_t)c->HW * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (n_win) *n_win = c->adapt_n_win;
+    if (k) *k = c->adapt_k;
+    return D3D_OK;
+}
+
+int d3d_adapt_set(d3d_ctx *c, const double *scale_hw, const uint32_t *accepted_hw, int64_t n_win, int64_t k) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    NEED(c->adapt_on, D3D_ERR_STATE, "per-spaxel jump scales not begun (d3d_adapt_begin)");
+    NEED(n_win >= 0 && k >= 0, D3D_ERR_INVALID, "n_win = %lld / k = %lld is negative", (long long)n_win, (long long)k);
+    if (scale_hw)
+        for (long i = 0; i < c->HW; ++i)
+            NEED(std::isfinite(scale_hw[i]) && scale_hw[i] > 0.0, D3D_ERR_INVALID,
+                 "jump scale of spaxel (%ld, %ld) is %g: finite, positive numbers", i / c->W, i % c->W, scale_hw[i]);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (scale_hw) HIP_TRY(hipMemcpy(c->jscale, scale_hw, (size_t)c->HW * sizeof(double), hipMemcpyHostToDevice));
+    if (accepted_hw)
+        HIP_TRY(hipMemcpy(c->jacc, accepted_hw, (size_t)c->HW * sizeof(uint32_t), hipMemcpyHostToDevice));
+    c->adapt_n_win = n_win;
+    c->adapt_k = k;
+    c->props_sweep = -1;  // (a table made from the old scales)
+    return D3D_OK;
+}
+
+int d3d_adapt_end(d3d_ctx *c) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    adapt_free(c);
+    return D3D_OK;
+}
+
 int d3d_get_dlog(d3d_ctx *c, double *out_hw) {
     NEED(c && out_hw, D3D_ERR_INVALID, "NULL argument");
     HIP_TRY(hipMemcpyAsync(out_hw, c->dlog, (size_t)c->HW * sizeof(double), hipMemcpyDeviceToHost,
@@ -1912,6 +2018,8 @@ int d3d_set_tile(d3d_ctx *c, int gy0, int gx0, int Wg, int oy0, int oy1, int ox0
          c->W);
     NEED(0 <= oy0 && oy0 <= oy1 && oy1 <= c->H && 0 <= ox0 && ox0 <= ox1 && ox1 <= c->W,
          D3D_ERR_INVALID, "owned rectangle [%d,%d)x[%d,%d) outside the tile", oy0, oy1, ox0, ox1);
+    NEED(!c->adapt_on, D3D_ERR_UNSUPPORTED,
+         "per-spaxel jump scales are on (d3d_adapt_begin): not on a tile; call d3d_adapt_end first");
     c->gy0 = gy0;
     c->gx0 = gx0;
     c->Wg = Wg;

@@ -273,6 +273,17 @@ struct d3d_ctx {
     int64_t post_n = 0;            // samples accumulated
     int post_first = 0, post_every = 0;  // d3d_post_schedule (every == 0: none)
     int post_nt = 0;               // option post_nt = 1: the accumulators' loads and stores non-temporal
+    // per-spaxel jump scales (d3d_adapt_*): every `adapt_window` sweeps of d3d_mh_sweeps each
+    // spaxel's scale moves towards the target acceptance rate (k_mh_adapt), up to sweep
+    // adapt_last; the counters then go on counting.  Nothing is allocated before d3d_adapt_begin.
+    bool adapt_on = false;
+    double *jscale = nullptr;      // [HW] multiplicative jump scale of every spaxel
+    unsigned *jacc = nullptr;      // [HW] accepted proposals since the counters were last cleared
+    double adapt_target = 0.0, adapt_gain = 0.0, adapt_min = 0.0, adapt_max = 0.0;
+    int adapt_window = 0;          // sweeps per adaptation step (0: a fixed map that never adapts)
+    int64_t adapt_last = 0;        // no step after this sweep (the run's numbering: s + sweep_origin)
+    int64_t adapt_n_win = 0;       // sweeps counted since the counters were last cleared
+    int64_t adapt_k = 0;           // adaptation steps taken
 };
 
 namespace d3dh {
@@ -293,6 +304,9 @@ int forward_into(d3d_ctx *c, double *dst, bool resid);
 // d3d_post.hip: one sample (the chain state; SLOT_SIM holds its convolved cube when that moment
 // is on) into the running moments, as sample number c->post_n + 1
 int launch_post_accum(d3d_ctx *c);
+// d3d_mh.hip: after sweep `s` of a d3d_mh_sweeps call (d3d_adapt_begin): the sweep is counted and,
+// where it fills a window at or before the last adapted sweep, the jump scales take a step
+int adapt_after_sweep(d3d_ctx *c, int s);
 bool zmajor_ok(const d3d_ctx *c);
 // LSF (x) FSF of c->stage in the reference layout (D,H,W), in place (zmajor_ok())
 int launch_zmajor_convolve(d3d_ctx *c);

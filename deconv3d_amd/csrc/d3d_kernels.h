@@ -1744,6 +1744,9 @@ struct MHChainArgs {  // one chain of a batch: see MHArgs::batch
     // (k_mh_small: the chain's tables of the sweep)
     const MHProposal *props;
     const double *ltab;
+    // (d3d_adapt_begin: the chain's jump scales and accept counters, NULL when off)
+    const double *jscale;
+    unsigned *jacc;
 };
 struct MHArgs {
     int D, Dp, HL, H, W, fh, fw, N, ntaps, npos;
@@ -1852,6 +1855,11 @@ struct MHArgs {
     // (tools/mh_phases.py)
     unsigned long long *stamp;
 #endif
+    // Per-spaxel jump scales (d3d_adapt_begin), [H*W] by local spaxel index: the Cauchy
+    // amplitudes of spaxel sp are amp[] * jscale[sp], and every decision adds its verdict to
+    // jacc[sp] (one writer per spaxel and sweep).  NULL: the one amplitude of lib/run.py:251-262.
+    const double *jscale;
+    unsigned *jacc;
 };
 
 #ifdef D3D_EXPERIMENTS
@@ -1929,8 +1937,10 @@ struct MHProposal {
 
 // lib/run.py:369-388: Cauchy jump from the given current parameters and bounds test
 // (the arithmetic of mh_propose; k_mh_chain calls it with parameters it keeps in LDS).
+// sp: the local spaxel index (the jump scale map's, MHArgs::jscale).
 __device__ __forceinline__ MHProposal mh_propose_from(const MHArgs &P, double a_old, double c_old,
-                                                      double w_old, uint32_t gsp, uint32_t sweep) {
+                                                      double w_old, uint32_t gsp, uint32_t sweep,
+                                                      long sp) {
     MHProposal q;
     q.gsp = gsp;
     q.a_old = a_old;
@@ -1946,9 +1956,16 @@ __device__ __forceinline__ MHProposal mh_propose_from(const MHArgs &P, double a_
         const U2 u0 = philox_pair(P.seed, q.gsp, sweep, BLK_JUMP_AC);
         const U2 u1 = philox_pair(P.seed, q.gsp, sweep, BLK_JUMP_W);
         const double PI = 3.141592653589793;
-        q.pn[0] = q.a_old + P.amp[0] * tan(PI * (u0.x - 0.5));
-        q.pn[1] = q.c_old + P.amp[1] * tan(PI * (u0.y - 0.5));
-        q.pn[2] = q.w_old + P.amp[2] * tan(PI * (u1.x - 0.5));
+        double amp0 = P.amp[0], amp1 = P.amp[1], amp2 = P.amp[2];
+        if (P.jscale) {  // d3d_adapt_begin: this spaxel's own jump scale
+            const double js = P.jscale[sp];
+            amp0 *= js;
+            amp1 *= js;
+            amp2 *= js;
+        }
+        q.pn[0] = q.a_old + amp0 * tan(PI * (u0.x - 0.5));
+        q.pn[1] = q.c_old + amp1 * tan(PI * (u0.y - 0.5));
+        q.pn[2] = q.w_old + amp2 * tan(PI * (u1.x - 0.5));
         u_acc = u1.y;
     }
     q.log_u = log(u_acc);
@@ -1979,7 +1996,7 @@ __device__ __forceinline__ MHProposal mh_propose(const MHArgs &P, int sp, uint32
         return q;
     }
     return mh_propose_from(P, P.params[(long)sp * 3 + 0], P.params[(long)sp * 3 + 1],
-                           P.params[(long)sp * 3 + 2], q.gsp, sweep);
+                           P.params[(long)sp * 3 + 2], q.gsp, sweep, sp);
 }
 
 // The proposal of an update: taken from the sweep's table when there is one (same function,
@@ -2102,6 +2119,7 @@ __device__ __forceinline__ void mh_decide_core(const MHArgs &P, const MHProposal
             P.params[(long)sp * 3 + 2] = accept ? q.pn[2] : q.w_old;
         }
         P.dlog[sp] = delta;
+        if (P.jacc && !P.ext_lines) P.jacc[sp] += accept ? 1u : 0u;  // (one writer per spaxel and sweep)
         if (accept) atomicAdd(P.accepted, 1ULL);
     }
 }
@@ -3018,6 +3036,8 @@ __global__ __launch_bounds__(NS + 64) void k_mh_ws(MHArgs P, uint32_t sweep) {
         }
         P.ra = B.ra;
         P.seed = B.seed;
+        P.jscale = B.jscale;
+        P.jacc = B.jacc;
     }
     if constexpr (ZBK) {
         const int item = blockIdx.x / P.z_nb, zb = blockIdx.x - item * P.z_nb;
@@ -3369,7 +3389,7 @@ __global__ __launch_bounds__(NTMAX) void k_mh_chain(MHArgs P, MHChain F) {
                 const double a = si ? snew[3 * k2 + 0] : P.params[sp * 3 + 0];
                 const double cc = si ? snew[3 * k2 + 1] : P.params[sp * 3 + 1];
                 const double w = si ? snew[3 * k2 + 2] : P.params[sp * 3 + 2];
-                sprop[k2] = mh_propose_from(P, a, cc, w, gsp, sweep);
+                sprop[k2] = mh_propose_from(P, a, cc, w, gsp, sweep, sp);
             }
         }
         if (__syncthreads_or(!ok)) return;  // a timed-out wait: *F.err is set, the host reports it
@@ -4363,7 +4383,26 @@ static __global__ __launch_bounds__(256) void k_mh_proposals(MHArgs P, uint32_t 
     const long sp = (long)y * P.W + x;
     if (!P.mask[sp]) return;
     out[sp] = mh_propose_from(P, P.params[sp * 3 + 0], P.params[sp * 3 + 1], P.params[sp * 3 + 2],
-                              (uint32_t)((y + P.gy0) * P.Wg + (x + P.gx0)), sweep);
+                              (uint32_t)((y + P.gy0) * P.Wg + (x + P.gx0)), sweep, sp);
+}
+
+// d3d_adapt_begin: one adaptation step of the jump scales, one thread per spaxel, after the
+// sweep that fills a window of n_win sweeps (Robbins-Monro on the log scale, step gain / sqrt(k)).
+// Masked and unowned spaxels have no decisions: they keep their scale.
+static __global__ __launch_bounds__(256) void k_mh_adapt(double *jscale, unsigned *jacc,
+                                                          const uint8_t *mask, int W, int y0, int y1,
+                                                          int x0, int x1, int n_win, double step,
+                                                          double target, double scale_min,
+                                                          double scale_max) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int w = x1 - x0;
+    if (i >= (y1 - y0) * w) return;
+    const long sp = (long)(y0 + i / w) * W + (x0 + i % w);
+    if (!mask[sp]) return;
+    const double rate = (double)jacc[sp] / (double)n_win;
+    const double s = jscale[sp] * exp(step * (rate - target));
+    jscale[sp] = fmin(fmax(s, scale_min), scale_max);
+    jacc[sp] = 0u;
 }
 
 // Halo exchange of the tiled chain: the cells (all E values per spaxel: E = Dp for

@@ -118,6 +118,27 @@ void fill_mh_args(d3d_ctx *c, d3d::MHArgs &P) {
 #ifdef D3D_EXPERIMENTS
     P.stamp = nullptr;
 #endif
+    P.jscale = c->adapt_on ? c->jscale : nullptr;
+    P.jacc = c->adapt_on ? c->jacc : nullptr;
+}
+
+int adapt_after_sweep(d3d_ctx *c, int s) {
+    if (!c->adapt_on) return 0;
+    ++c->adapt_n_win;
+    const int64_t at = (int64_t)s + (int64_t)c->sweep_origin;
+    if (c->adapt_window <= 0 || c->adapt_n_win != c->adapt_window || at > c->adapt_last) return 0;
+    ++c->adapt_k;
+    const int n = (c->oy1 - c->oy0) * (c->ox1 - c->ox0);
+    if (n > 0) {
+        hipLaunchKernelGGL(d3d::k_mh_adapt, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
+                           c->jscale, c->jacc, c->mask, c->W, c->oy0, c->oy1, c->ox0, c->ox1,
+                           (int)c->adapt_n_win, c->adapt_gain / sqrt((double)c->adapt_k), c->adapt_target,
+                           c->adapt_min, c->adapt_max);
+        HIP_TRY(hipGetLastError());
+    }
+    c->adapt_n_win = 0;
+    c->props_sweep = -1;  // (a table made from the old scales)
+    return 0;
 }
 
 // The instantiation of k_mh_ws for the context's line shape: the single Gaussian's kernel for
@@ -703,6 +724,8 @@ int mh_sweeps_batch(d3d_ctx **cs, int R, int n_sweeps, int first_sweep, int64_t 
             c->props_sweep = -1;
             B.props = nullptr;
             B.ltab = nullptr;
+            B.jscale = c->adapt_on ? c->jscale : nullptr;
+            B.jacc = c->adapt_on ? c->jacc : nullptr;
             if (small) {
                 if (!c->props && hipMalloc(&c->props, (size_t)c->HW * sizeof(d3d::MHProposal)) != hipSuccess) rc = fail(D3D_ERR_HIP, "hipMalloc");
                 if (!rc && !c->ltab && hipMalloc(&c->ltab, (size_t)c->HW * 2 * c->Dp * sizeof(double)) != hipSuccess) rc = fail(D3D_ERR_HIP, "hipMalloc");
@@ -764,6 +787,7 @@ int mh_sweeps_batch(d3d_ctx **cs, int R, int n_sweeps, int first_sweep, int64_t 
                 }
             }
             if (!rc && after_sweep) rc = after_sweep(s);  // (saved sweeps: snapshots of every chain)
+            for (int r = 0; r < R && !rc; ++r) rc = adapt_after_sweep(cs[r], s);  // (each from its own counters)
             // lib/run.py:521-534, per chain
             for (int r = 0; r < R && !rc; ++r)
                 if (cs[r]->refresh_every > 0 && s % cs[r]->refresh_every == 0)

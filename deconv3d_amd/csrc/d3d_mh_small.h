@@ -160,6 +160,8 @@ __global__ __launch_bounds__(NS) void k_mh_small(MHArgs P, uint32_t sweep) {
         P.seed = B.seed;
         P.props = B.props;
         P.ltab = B.ltab;
+        P.jscale = B.jscale;
+        P.jacc = B.jacc;
     }
     // (measured and dropped: the window centre from the block index -- the grid as the launch's
     // lattice, no work-list entry to wait for: 10.87 against 10.89 us per launch at 64^3, 12.22
@@ -469,6 +471,7 @@ static __global__ __launch_bounds__(256) void k_mh_line_table(MHArgs P, uint32_t
             P.amp[k] = B.amp[k];
         }
         P.seed = B.seed;
+        P.jscale = B.jscale;
         props = const_cast<MHProposal *>(B.props);
         ltab = const_cast<double *>(B.ltab);
     }
@@ -480,7 +483,7 @@ static __global__ __launch_bounds__(256) void k_mh_line_table(MHArgs P, uint32_t
     double *gO = smem + (size_t)wave * 2 * N, *gN = gO + N;
     const MHProposal q =
         mh_propose_from(P, P.params[sp * 3 + 0], P.params[sp * 3 + 1], P.params[sp * 3 + 2],
-                        (uint32_t)((y + P.gy0) * P.Wg + (x + P.gx0)), sweep);
+                        (uint32_t)((y + P.gy0) * P.Wg + (x + P.gx0)), sweep, sp);
     if (lane == 0) props[sp] = q;
     for (int j = lane; j < N; j += 64) {
         gO[j] = (j < P.D) ? unit_line<MULTI>(P.line, (double)j, q.c_old, q.w_old) : 0.0;

@@ -35,7 +35,7 @@ from os.path import splitext
 
 import numpy as np
 
-from . import _lib, posterior as _posterior
+from . import _lib, adapt as _adapt, posterior as _posterior
 from .cube import Cube, read_fits
 from .instruments import Instrument
 from .line_models import (LineModel, SingleGaussianLineModel, SINGLE_LINE_SHAPE,
@@ -98,6 +98,23 @@ class Run:
     arrays.  A host-evaluated line model raises ``NotImplementedError``.  The accumulators are
     not part of a checkpoint: a ``resume_state=`` run starts fresh ones, scheduled in this
     segment's sweep numbering.  Costs four more cubes of device memory per chain.
+
+    ``adapt_sweeps=N`` (default ``None``: off, nothing allocated or launched, the chain is bit for
+    bit what it is without the keyword) gives every spaxel its own multiplicative jump scale: the
+    reference proposes all of them with the one ``jump_amplitude`` (lib/run.py:251-262, 570-579),
+    too wide for a bright spaxel and too narrow for a faint one.  Every ``adapt_window`` sweeps of
+    the first N each scale s moves, on the device, by
+    ``s <- clip(s * exp(adapt_gain / sqrt(k) * (rate - adapt_target)), *adapt_scale_range)``, rate
+    the spaxel's accepted share of the window and k the step's number; after the last full window
+    at or before sweep N (``run.adapted_until``) the scales are frozen and the rest is an ordinary
+    Markov chain.  ``run.jump_scale`` (H, W) holds the frozen scales, ``run.acceptance_map`` (H, W)
+    the accepted share of the sweeps after the freeze (NaN where masked, or when none followed);
+    with ``chains=R`` every chain adapts from its own counters, ``run.jump_scales[r]`` /
+    ``run.acceptance_maps[r]``.  ``posterior_burn_in`` must not lie before N; N beyond 80 % of
+    ``max_iterations`` logs a warning (``extract_parameters`` averages the last 20 %).  A
+    checkpoint records the maps, and ``resume_state=`` continues them bit for bit (a state
+    written with other ``adapt_*`` keywords is refused).  A host-evaluated line model raises
+    ``NotImplementedError``.
     """
 
     def __init__(
@@ -124,10 +141,24 @@ class Run:
         chains=1,
         posterior_burn_in=None,
         posterior_every=1,
+        adapt_sweeps=None,
+        adapt_window=50,
+        adapt_target=0.25,
+        adapt_gain=2.0,
+        adapt_scale_range=(1e-3, 1e3),
     ):
         if posterior_burn_in is not None:     # (before anything else: no device work yet)
             posterior_burn_in, posterior_every = _posterior.check_schedule(posterior_burn_in,
                                                                            posterior_every)
+        adapt_cfg = None
+        if adapt_sweeps is not None:
+            adapt_cfg = _adapt.check_keywords(adapt_sweeps, adapt_window, adapt_target, adapt_gain,
+                                              adapt_scale_range)
+            if posterior_burn_in is not None and posterior_burn_in < adapt_cfg[0]:
+                raise ValueError("posterior_burn_in=%d lies before adapt_sweeps=%d: the moments of a "
+                                 "chain that is still adapting are not posterior moments"
+                                 % (posterior_burn_in, adapt_cfg[0]))
+        self._adapt_cfg = adapt_cfg
         # lib/run.py:112-114
         assert keep_one_in > 0, "keep_one_in= MUST be a positive integer"
         assert write_every > 0, "write_every= MUST be a positive integer"
@@ -139,6 +170,10 @@ class Run:
         n_chains = int(chains)
         assert n_chains >= 1, "chains= MUST be a positive integer"
         self.n_chains = n_chains
+        if adapt_cfg is not None and adapt_cfg[0] > 0.8 * self.max_iterations:
+            logger.warning("adapt_sweeps=%d is beyond 80 %% of max_iterations=%d: extract_parameters "
+                           "averages the last 20 %% of the chain, part of which is still adapting"
+                           % (adapt_cfg[0], self.max_iterations))
 
         # ---- input cube (lib/run.py:119-143) --------------------------------
         if isinstance(cube, str):
@@ -219,6 +254,11 @@ class Run:
             raise NotImplementedError(
                 "posterior_burn_in=: the line model %s is evaluated on the host; the device "
                 "accumulates posterior moments only for the models it evaluates itself"
+                % type(self.model).__name__)
+        if adapt_cfg is not None and self._host_model:
+            raise NotImplementedError(
+                "adapt_sweeps=: the line model %s is evaluated on the host; the device "
+                "adapts jump scales only for the models it evaluates itself"
                 % type(self.model).__name__)
         # (offsets, ratios) of the device's unit line; None for a host-evaluated model
         self.line_shape = None if self._host_model else device_line_shape(self.model)
@@ -312,6 +352,7 @@ class Run:
         self.sweep_origin = 0
         resumed_accepted = None
         resumed_per_chain = None
+        resumed_adapt = None
         if resume_state is not None:
             state = np.load(resume_state) if isinstance(resume_state, str) else resume_state
             files = getattr(state, "files", state)
@@ -323,6 +364,8 @@ class Run:
                 self.logger.warning("resume_state was written with seed %d, this run uses %d"
                                     % (int(state["seed"]), self.seed))
             self.sweep_origin = int(state["sweep_origin"]) + int(state["iteration"]) - 1
+            resumed_adapt = _adapt.check_resume(state, files, adapt_cfg, n_chains,
+                                                (cube_height, cube_width))
             # totals over every earlier segment (older checkpoints hold one segment's)
             resumed_accepted = (
                 int(state["total_accepted"] if "total_accepted" in files else state["accepted_count"]),
@@ -373,6 +416,12 @@ class Run:
                 if posterior_burn_in is not None:
                     eng.post_begin()
                     eng.post_schedule(posterior_burn_in, posterior_every)
+                if adapt_cfg is not None:
+                    # (the last adapted sweep in the numbering of the whole run: a resumed
+                    # segment counts from its sweep origin)
+                    eng.adapt_begin(adapt_cfg[2], adapt_cfg[1], adapt_cfg[0], adapt_cfg[3], adapt_cfg[4])
+                    if resumed_adapt is not None:
+                        eng.adapt_set(*resumed_adapt[r])
         if resume_state is not None:
             if host_chain is None:
                 for eng in self.engines:
@@ -463,6 +512,20 @@ class Run:
                 lk[n_valid:] = np.nan
                 ch.flush()
                 lk.flush()
+
+        # ---- jump scales and acceptance-rate maps (adapt_sweeps=) ----------------
+        self.jump_scales = self.acceptance_maps = None
+        self.jump_scale = self.acceptance_map = self.adapted_until = None
+        if adapt_cfg is not None:
+            self.jump_scales, self.acceptance_maps = [], []
+            for eng in self.engines:
+                scale, acc, n_win, k = eng.adapt_get()
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    rate = acc / float(n_win) if n_win > 0 else np.full(scale.shape, np.nan)
+                self.jump_scales.append(scale)
+                self.acceptance_maps.append(np.where(self.mask == 1, rate, np.nan))
+                self.adapted_until = int(k) * adapt_cfg[1]
+            self.jump_scale, self.acceptance_map = self.jump_scales[0], self.acceptance_maps[0]
 
         # ---- outputs (lib/run.py:539-549) ------------------------------------
         self.likelihoods = likelihoods
@@ -556,6 +619,13 @@ class Run:
         if self.line_shape is not None:     # (resume_state= checks it)
             state["line_offsets"] = np.array(self.line_shape[0], dtype=np.float64)
             state["line_ratios"] = np.array(self.line_shape[1], dtype=np.float64)
+        if self._adapt_cfg is not None:     # (resume_state= checks the keywords, restores the rest)
+            got = [eng.adapt_get() for eng in self.engines]
+            state["adapt_keywords"] = _adapt.keyword_record(self._adapt_cfg)
+            state["adapt_scale"] = np.stack([g[0] for g in got])
+            state["adapt_accepted"] = np.stack([g[1] for g in got])
+            state["adapt_n_win"] = np.array([g[2] for g in got], dtype=np.int64)
+            state["adapt_k"] = np.array([g[3] for g in got], dtype=np.int64)
         np.savez("%s_state.npz" % name, **state)
         if self._host_model:
             maps = [hc.params for hc in self._host_chains]
@@ -661,8 +731,11 @@ class Run:
         self.plot_chain(filepath="%s_chain.png" % name)
         self.convolved_cube.to_fits("%s_convolved_cube.fits" % name, clobber)
         self.clean_cube.to_fits("%s_clean_cube.fits" % name, clobber)
+        maps = {}
+        if self.jump_scale is not None:
+            maps = dict(jump_scale=self.jump_scale, acceptance_map=self.acceptance_map)
         np.savez("%s_result.npz" % name, chain=self.chain, likelihoods=self.likelihoods,
-                 fsf=self.fsf, lsf=self.lsf if self.lsf is not None else np.zeros(0))
+                 fsf=self.fsf, lsf=self.lsf if self.lsf is not None else np.zeros(0), **maps)
 
     def save_parameters_npy(self, filepath):
         """lib/run.py:790-797; reusable as ``initial_parameters``."""

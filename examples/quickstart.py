@@ -74,6 +74,22 @@ print("bright spaxels (%d): median |centre - truth| = %.2f channels, |width - tr
     np.median(np.abs(post[..., 2] - truth[..., 2])[bright])))
 
 
+# ---- per-spaxel jump scales: adapt_sweeps=N ----------------------------------------------------
+# One jump amplitude for every spaxel is too wide for the bright ones and too narrow for the faint
+# ones.  adapt_sweeps=N adapts a scale per spaxel on the device during the first N sweeps and freezes
+# it; run.acceptance_map is the accepted share of the sweeps after the freeze.  With the scale range
+# pinned at (1, 1) nothing adapts: the chain of a run without the keyword, counted alike.
+short = dict(variance=np.full(clean.shape, sigma ** 2), max_iterations=min(iterations, 1000), keep_one_in=10,
+             min_acceptance_rate=0., gibbs_apriori_variance=100., seed=1,
+             adapt_sweeps=min(iterations, 1000) // 2, adapt_window=min(50, min(iterations, 1000) // 2))
+for label, more in (("adapted", {}), ("one amplitude", dict(adapt_scale_range=(1., 1.)))):
+    r = Run(cube, inst, **dict(short, **more))
+    rate = r.acceptance_map[r.mask == 1]
+    print("acceptance rate per spaxel after sweep %d, %s: 5th / 50th / 95th percentile %s "
+          "(jump scales %s)" % (r.adapted_until, label, np.round(np.percentile(rate, [5, 50, 95]), 3),
+                                np.round(np.percentile(r.jump_scale, [5, 50, 95]), 3)))
+
+
 # ---- several chains at once: chains=R ----------------------------------------------------------
 # The reference's own science fixture (tests/input/data14forAntoine.mat: 24 x 30 spaxels x 21
 # channels, settings of its tests/read_mat.py:94-121).  A colour launch of so small a cube holds

@@ -278,6 +278,45 @@ int d3d_post_get(d3d_ctx *ctx, int which, double *mean, double *m2);
 /* Free the accumulators and drop the schedule (d3d_ctx_destroy does it too). */
 int d3d_post_end(d3d_ctx *ctx);
 
+/* ---- per-spaxel jump scales ---------------------------------------------- */
+/* The reference proposes (c, w) of every spaxel with ONE Cauchy amplitude, jump_amplitude
+ * (lib/run.py:251-262, 570-579), and its only acceptance feature is the stop rule on the pooled
+ * rate (lib/run.py:344-364).  These entries keep one multiplicative scale per spaxel -- the
+ * amplitudes of spaxel (y,x) are amp[] * scale[y,x] in every device kernel -- count every
+ * spaxel's accepted proposals on the device, and, during burn-in, move each scale towards a
+ * target acceptance rate.  Off until begun: a ctx that never calls d3d_adapt_begin allocates and
+ * launches nothing for them and runs the chain it always ran, bit for bit. */
+
+/* Allocate the scale map (all 1) and the counters (all 0).  After every `window`-th counted sweep
+ * s of d3d_mh_sweeps / d3d_mh_sweeps_batch with s + sweep origin <= last_sweep (the run's
+ * numbering, lib/run.py:344-353 cur_iteration; d3d_mh_set_sweep_origin), with k the number of
+ * steps so far including this one, on the device:
+ *     rate  = accepted[y,x] / window
+ *     scale = clamp(scale * exp(gain / sqrt(k) * (rate - target)), scale_min, scale_max)
+ *     accepted[y,x] = 0
+ * Masked spaxels keep their scale.  After the last step the counters go on counting, so that
+ * accepted / n_win (d3d_adapt_get) is the acceptance-rate map of the frozen chain.  window = 0:
+ * a fixed map (d3d_adapt_set) that never adapts.  Calling it again starts afresh.
+ * D3D_ERR_INVALID: target outside (0,1), window < 0, gain not positive, a scale range that is
+ * not finite and positive or has scale_min > scale_max.  D3D_ERR_UNSUPPORTED: a tile ctx
+ * (d3d_set_tile), or -- EXPERIMENTS builds -- option mh_chain, mh_flow or mh_pair, whose kernels keep
+ * their proposals' inputs across sweeps (setting one later is refused alike).
+ * d3d_mh_colour_lines draws its proposals on the host (lib/run.py:570-579 there): untouched. */
+int d3d_adapt_begin(d3d_ctx *ctx, double target, int window, int64_t last_sweep, double gain,
+                    double scale_min, double scale_max);
+/* The (H,W) scale map, the (H,W) counters, the sweeps counted since the counters were last
+ * cleared and the steps taken so far: accepted / n_win is the per-spaxel form of the rate the
+ * reference pools over the cube (lib/run.py:344-364).  Any pointer may be NULL. */
+int d3d_adapt_get(d3d_ctx *ctx, double *scale_hw, uint32_t *accepted_hw, int64_t *n_win, int64_t *k);
+/* Install them (a resumed run continues the jump scales of lib/run.py:570-579 where the
+ * checkpoint left them; with window = 0 a caller-given fixed map).  Either map may be NULL: kept.
+ * A scale that is not finite and positive, or a negative n_win / k: D3D_ERR_INVALID. */
+int d3d_adapt_set(d3d_ctx *ctx, const double *scale_hw, const uint32_t *accepted_hw, int64_t n_win,
+                  int64_t k);
+/* Free the maps: the ctx proposes with the one amplitude of lib/run.py:251-262 again
+ * (d3d_ctx_destroy does it too). */
+int d3d_adapt_end(d3d_ctx *ctx);
+
 /* ---- spatial tiling (one chain over several GPUs) --------- */
 /* The reference has no counterpart (single process).  What makes tiling possible is
  * that an update at (y,x) touches only its FSF window (lib/run.py:404-419), and that
