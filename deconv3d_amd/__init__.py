@@ -7,12 +7,14 @@ reference's own ``Run / Instrument / SpreadFunction / LineModel`` API
 from .cube import Axis, Cube, HyperspectralCube  # noqa: F401
 from .instruments import MUSE, Instrument  # noqa: F401
 from .line_models import GaussianMultipletLineModel, LineModel, SingleGaussianLineModel  # noqa: F401
-from .masks import above_percentile  # noqa: F401
+from .masks import above_percentile, above_snr  # noqa: F401
 from .math_utils import median_clip  # noqa: F401
 from . import adapt  # noqa: F401
 from . import posterior  # noqa: F401
 from .posterior import PosteriorMoments  # noqa: F401
 from .run import Run, logger  # noqa: F401
+from . import search  # noqa: F401
+from .search import LineSearch, line_search  # noqa: F401
 from .spread_functions import (  # noqa: F401
     FieldSpreadFunction, GaussianFieldSpreadFunction, GaussianLineSpreadFunction,
     ImageFieldSpreadFunction, LineSpreadFunction, MoffatFieldSpreadFunction,

@@ -39,6 +39,7 @@ SYMBOLS = [
     "d3d_post_begin", "d3d_post_schedule", "d3d_post_accumulate", "d3d_post_count", "d3d_post_get",
     "d3d_post_end",
     "d3d_adapt_begin", "d3d_adapt_get", "d3d_adapt_set", "d3d_adapt_end",
+    "d3d_line_search",
 ]
 
 # posterior moments (a table, so that tools/posterior_time.py can load the PARENT commit's library,
@@ -58,6 +59,11 @@ ADAPT_PROTOTYPES = {
                       C.POINTER(C.c_int64)],
     "d3d_adapt_set": [C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_int64, C.c_int64],
     "d3d_adapt_end": [],
+}
+# matched-filter line search (a table for the same reason)
+SEARCH_PROTOTYPES = {
+    "d3d_line_search": [C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double),
+                        C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)],
 }
 POST_CLEAN, POST_CONVOLVED = 1, 2                     # d3d_post_begin: bits of `what`
 POST_PARAMETERS, POST_CLEAN_CUBE, POST_CONVOLVED_CUBE = 0, 1, 2   # d3d_post_get: `which`
@@ -168,7 +174,8 @@ def load():
     lib.d3d_mh_colour.argtypes = [ctx_p, C.c_int, C.c_int]
     lib.d3d_export_updates.argtypes = [ctx_p, C.c_int, C.POINTER(C.c_int), dbl_p]
     lib.d3d_apply_updates.argtypes = [ctx_p, C.c_int, dbl_p]
-    for name, argtypes in list(POST_PROTOTYPES.items()) + list(ADAPT_PROTOTYPES.items()):
+    for name, argtypes in (list(POST_PROTOTYPES.items()) + list(ADAPT_PROTOTYPES.items())
+                           + list(SEARCH_PROTOTYPES.items())):
         getattr(lib, name).argtypes = [ctx_p] + argtypes
     for name in SYMBOLS:
         fn = getattr(lib, name)
@@ -693,3 +700,22 @@ class Engine(object):
 
     def adapt_end(self):
         _check(self._lib.d3d_adapt_end(self._ctx))
+
+    # -- matched-filter line search ---------------------------------------------------
+    def line_search(self, centres, widths, bank=None):
+        """(best, stat) of include/deconv3d_hip.h: d3d_line_search -- per spaxel the index
+        ``i_w * n_c + i_c`` of the best template over ``widths`` x ``centres`` (-1: none, or
+        masked) and ``{N, Q, s(i_c - 1), s(i_c + 1)}``.  ``bank``: ``(n_w * n_c, D)`` templates
+        evaluated on the host, used instead of the device's."""
+        centres = np.ascontiguousarray(centres, dtype=np.float64).reshape(-1)
+        widths = np.ascontiguousarray(widths, dtype=np.float64).reshape(-1)
+        bank_p = None
+        if bank is not None:
+            bank = _c64(bank, (centres.size * widths.size, self.shape[0]))
+            bank_p = _dp(bank)
+        best = np.empty(self.shape[1:], dtype=np.int32)
+        stat = np.empty(self.shape[1:] + (4,), dtype=np.float64)
+        _check(self._lib.d3d_line_search(self._ctx, int(centres.size), _dp(centres), int(widths.size),
+                                         _dp(widths), bank_p,
+                                         best.ctypes.data_as(C.POINTER(C.c_int32)), _dp(stat)))
+        return best, stat

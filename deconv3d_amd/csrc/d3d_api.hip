@@ -680,6 +680,7 @@ int d3d_ctx_create(d3d_ctx **out, int device, int D, int H, int W, int fh, int f
     CTX_TRY(hipStreamSynchronize(c->stream));
 #undef CTX_TRY
     c->h_mask.assign((size_t)c->HW, 1);
+    c->h_user_mask.assign((size_t)c->HW, 1);
     *out = c;
     return D3D_OK;
 }
@@ -795,6 +796,10 @@ int d3d_ctx_get_option(d3d_ctx *c, const char *key, long *value) {
         long n = 0;
         for (const d3d_ctx::Part &pt : c->parts) n += pt.chain ? 1 : 0;
         *value = c->have_data ? n : 0;
+        return D3D_OK;
+    }
+    if (!strcmp(key, "search_bank_ns") || !strcmp(key, "search_kernel_ns")) {  // read-only: the last d3d_line_search
+        *value = key[7] == 'b' ? c->search_bank_ns : c->search_kernel_ns;
         return D3D_OK;
     }
     // read-only, derived: what the context actually runs
@@ -1048,6 +1053,7 @@ int d3d_set_data(d3d_ctx *c, const double *data, const double *var, double var_s
     const size_t n = (size_t)c->D * c->HW;
     // mask: user mask AND no NaN anywhere in the spectrum (lib/run.py:153-162)
     for (long s = 0; s < c->HW; ++s) c->h_mask[s] = mask ? (mask[s] == 1) : 1;
+    c->h_user_mask = c->h_mask;
     bool any_nan = false;
     for (int z = 0; z < c->D; ++z) {
         const double *pl = data + (size_t)z * c->HW;
@@ -1860,6 +1866,22 @@ int d3d_post_end(d3d_ctx *c) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     post_free(c);
     return D3D_OK;
+}
+
+int d3d_line_search(d3d_ctx *c, int n_c, const double *centres, int n_w, const double *widths,
+                    const double *host_bank, int32_t *best_out, double *stat_out) {
+    NEED(c && centres && widths && best_out && stat_out, D3D_ERR_INVALID, "NULL argument");
+    NEED(n_c >= 1 && n_w >= 1, D3D_ERR_INVALID, "line search: %d centres and %d widths (at least one of each)",
+         n_c, n_w);
+    for (int i = 0; i < n_c; ++i)
+        NEED(std::isfinite(centres[i]), D3D_ERR_INVALID, "line search: centres[%d] is not finite", i);
+    for (int i = 0; i < n_w; ++i)
+        NEED(std::isfinite(widths[i]) && widths[i] > 0.0, D3D_ERR_INVALID,
+             "line search: widths[%d] = %g is not a positive number", i, widths[i]);
+    NEED(!c->tiled, D3D_ERR_UNSUPPORTED,
+         "line search on a tile: search the whole cube on one context and cut the map");
+    NEED(c->have_taps && c->have_data, D3D_ERR_STATE, "taps/data not set");
+    return line_search(c, n_c, centres, n_w, widths, host_bank, best_out, stat_out);
 }
 
 int d3d_adapt_begin(d3d_ctx *c, double target, int window, int64_t last_sweep, double gain,

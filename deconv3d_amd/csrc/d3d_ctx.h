@@ -1,7 +1,8 @@
 // Internal header of libdeconv3d_hip.so: the context struct and the launch
 // functions shared by the library's translation units (d3d_api.hip: C ABI and host
 // logic; d3d_spatial.hip: line / LSF / FSF kernels; d3d_mh.hip: the MH-within-Gibbs
-// kernels).  Not installed: the public interface is include/deconv3d_hip.h.
+// kernels; d3d_post.hip: posterior moments; d3d_search.hip: the matched-filter line search).
+// Not installed: the public interface is include/deconv3d_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: the library is dlopen()ed by d3d_comm_init
@@ -133,6 +134,7 @@ struct d3d_ctx {
     double halo_ms = 0.0;              // summed at the end of each d3d_mh_sweeps call
     long halo_count = 0;
     std::vector<uint8_t> h_mask;
+    std::vector<uint8_t> h_user_mask;  // the caller's mask alone, without the NaN rule (d3d_line_search)
 
     d3d::LineShape line = {1, {0.0, 0.0, 0.0, 0.0}, {1.0, 0.0, 0.0, 0.0}};  // d3d_set_line_shape
     bool have_taps = false, have_data = false, have_params = false, have_cfg = false;
@@ -284,6 +286,10 @@ struct d3d_ctx {
     int64_t adapt_last = 0;        // no step after this sweep (the run's numbering: s + sweep_origin)
     int64_t adapt_n_win = 0;       // sweeps counted since the counters were last cleared
     int64_t adapt_k = 0;           // adaptation steps taken
+    // d3d_line_search: device time of the last call's bank build (lines + transpose, or the transpose
+    // of a host bank) and of its search kernel, by HIP events (read-only options search_bank_ns /
+    // search_kernel_ns)
+    long search_bank_ns = 0, search_kernel_ns = 0;
 };
 
 namespace d3dh {
@@ -307,6 +313,11 @@ int launch_post_accum(d3d_ctx *c);
 // d3d_mh.hip: after sweep `s` of a d3d_mh_sweeps call (d3d_adapt_begin): the sweep is counted and,
 // where it fills a window at or before the last adapted sweep, the jump scales take a step
 int adapt_after_sweep(d3d_ctx *c, int s);
+// d3d_search.hip: the matched-filter search of d3d_line_search (arguments already validated).  The
+// template bank is refused above this many bytes of device memory.
+constexpr size_t SEARCH_BANK_BUDGET = (size_t)256 << 20;
+int line_search(d3d_ctx *c, int n_c, const double *centres, int n_w, const double *widths,
+                const double *host_bank, int *best_out, double *stat_out);
 bool zmajor_ok(const d3d_ctx *c);
 // LSF (x) FSF of c->stage in the reference layout (D,H,W), in place (zmajor_ok())
 int launch_zmajor_convolve(d3d_ctx *c);

@@ -35,7 +35,7 @@ from os.path import splitext
 
 import numpy as np
 
-from . import _lib, adapt as _adapt, posterior as _posterior
+from . import _lib, adapt as _adapt, posterior as _posterior, search as _search
 from .cube import Cube, read_fits
 from .instruments import Instrument
 from .line_models import (LineModel, SingleGaussianLineModel, SINGLE_LINE_SHAPE,
@@ -115,6 +115,16 @@ class Run:
     checkpoint records the maps, and ``resume_state=`` continues them bit for bit (a state
     written with other ``adapt_*`` keywords is refused).  A host-evaluated line model raises
     ``NotImplementedError``.
+
+    ``initial_search=True`` (or a dict of :func:`deconv3d_amd.search.line_search` keywords
+    ``centres`` / ``widths`` plus ``jitter``; default ``None``: off, nothing allocated or launched,
+    the chain is bit for bit what it is without the keyword) starts the chain from a matched-filter
+    search of the cube instead of the reference's uniform draw (lib/run.py:310-314): chain 0 from
+    the searched ``(a, c, w)`` map, chains r > 0 from copies whose ``(c, w)`` are jittered by the
+    generator of ``seed + r`` (Gaussian, ``jitter = (0.5 channel, 10 %)``, clipped to the bounds) so
+    that R-hat still sees dispersed starts; spaxels without a detection keep their uniform draw.
+    ``run.search`` is the :class:`deconv3d_amd.search.LineSearch` (``snr``, ``parameters``,
+    ``mask(threshold)``).  Refused with ``initial_parameters=`` or ``resume_state=``.
     """
 
     def __init__(
@@ -146,7 +156,10 @@ class Run:
         adapt_target=0.25,
         adapt_gain=2.0,
         adapt_scale_range=(1e-3, 1e3),
+        initial_search=None,
     ):
+        # (before anything else: no device work yet)
+        search_cfg = _search.check_keywords(initial_search, initial_parameters, resume_state)
         if posterior_burn_in is not None:     # (before anything else: no device work yet)
             posterior_burn_in, posterior_every = _posterior.check_schedule(posterior_burn_in,
                                                                            posterior_every)
@@ -342,9 +355,10 @@ class Run:
             for r in range(n_chains):
                 self.chains[r][0] = initial_parameters[r] if per_chain else initial_parameters
         else:
+            start_rngs = []
             for r in range(n_chains):
-                draws = np.random.default_rng(self.seed + r).random(
-                    (cube_height, cube_width, parameters_count))
+                start_rngs.append(np.random.default_rng(self.seed + r))
+                draws = start_rngs[r].random((cube_height, cube_width, parameters_count))
                 self.chains[r][0] = min_boundaries + (max_boundaries - min_boundaries) * draws
 
         # a resumed run continues the checkpointed run's sweep numbering: sweep s of
@@ -396,6 +410,18 @@ class Run:
             if self.line_shape is not None:
                 eng.set_line_shape(*self.line_shape)
         self.engine = self.engines[0]
+        # ---- searched start (initial_search=): chain 0 from the matched-filter map, chains
+        # r > 0 from jittered copies; spaxels without a detection keep their uniform draw
+        self.search = None
+        if search_cfg is not None:
+            self.search = _search.search_engine(self.engine, self.model, self, search_cfg["centres"],
+                                                search_cfg["widths"], self.lsf)
+            found = self.search.detected & (self.mask == 1)
+            for r in range(n_chains):
+                start = self.search.parameters if r == 0 else _search.jittered_start(
+                    self.search.parameters, search_cfg["jitter"], start_rngs[r],
+                    min_boundaries, max_boundaries)
+                self.chains[r][0][found] = start[found]
         host_chain = None
         if self._host_model:
             from .host_model import HostModelChain

@@ -12,7 +12,8 @@ of irap-omp/deconv3d would write (lib/run.py:95-109), and prints how well the
 posterior means recover the line centres and widths.  With a FITS file:
 
     cube = Cube.from_fits('my_cube.fits')
-    run = Run(cube, MUSE(fsf_fwhm=0.8841), mask=above_percentile(cube, 60), max_iterations=40000)
+    run = Run(cube, MUSE(fsf_fwhm=0.8841), mask=above_snr(cube, MUSE(fsf_fwhm=0.8841), 5.),
+              initial_search=True, max_iterations=4000)
     run.save('my_run')
 """
 import os
@@ -88,6 +89,25 @@ for label, more in (("adapted", {}), ("one amplitude", dict(adapt_scale_range=(1
     print("acceptance rate per spaxel after sweep %d, %s: 5th / 50th / 95th percentile %s "
           "(jump scales %s)" % (r.adapted_until, label, np.round(np.percentile(rate, [5, 50, 95]), 3),
                                 np.round(np.percentile(r.jump_scale, [5, 50, 95]), 3)))
+
+
+# ---- matched-filter line search: S/N map, mask and starting map --------------------------------
+# A uniform start (the reference's, lib/run.py:310-314) leaves a spaxel tens of channels from its
+# line.  line_search correlates every spectrum with the LSF-convolved line over a grid of centres and
+# widths on the device; Run(initial_search=True) starts chain 0 from that map.
+from deconv3d_amd import above_snr, line_search  # noqa: E402
+
+var = np.full(clean.shape, sigma ** 2)
+found = line_search(cube, inst, variance=var)
+strong = found.snr >= 5.
+print("line search: %d of %d spaxels at S/N >= 5 (above_snr agrees: %s); their centres lie within %.2f channels "
+      "of the truth (median)" % (strong.sum(), H * W, bool(np.array_equal(above_snr(cube, inst, 5., variance=var), found.mask(5.))),
+                                 np.median(np.abs(found.parameters[..., 1] - truth[..., 1])[strong])))
+few = dict(variance=var, max_iterations=min(iterations, 200), min_acceptance_rate=0., gibbs_apriori_variance=100., seed=1)
+for label, more in (("searched start", dict(initial_search=True)), ("uniform start", {})):
+    r = Run(cube, inst, **dict(few, **more))
+    print("%s: reduced chi2 of the last sample after %d sweeps %.3f" % (
+        label, few["max_iterations"], np.mean(((cube.data - r.simulate_convolved(cube.data.shape, r.chain[-1])) / sigma) ** 2)))
 
 
 # ---- several chains at once: chains=R ----------------------------------------------------------

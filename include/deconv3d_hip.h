@@ -99,7 +99,9 @@ int d3d_timer_stop(d3d_ctx *ctx, double *elapsed_ms);
  * `make EXPERIMENTS=1` adds mh_chain, mh_prio, mh_maxit, mh_flow, mh_pair, spectral_shfl, fuse_lsf, march_pf,
  * march_one, march_stamp.  Unknown key or value out of range: D3D_ERR_INVALID.
  * d3d_ctx_get_option also answers the read-only key "chain_parts": how many of the
- * ctx's parts run their sweeps as one launch of persistent workgroups (k_mh_chain). */
+ * ctx's parts run their sweeps as one launch of persistent workgroups (k_mh_chain), and
+ * "search_bank_ns" / "search_kernel_ns": device time of the last d3d_line_search call's bank build
+ * and of its search kernel. */
 int d3d_ctx_set_option(d3d_ctx *ctx, const char *key, long value);
 int d3d_ctx_get_option(d3d_ctx *ctx, const char *key, long *value);
 /* 1 when the library was built with `make EXPERIMENTS=1` (the measured-but-not-faster
@@ -277,6 +279,27 @@ int d3d_post_count(d3d_ctx *ctx, int64_t *n);
 int d3d_post_get(d3d_ctx *ctx, int which, double *mean, double *m2);
 /* Free the accumulators and drop the schedule (d3d_ctx_destroy does it too). */
 int d3d_post_end(d3d_ctx *ctx);
+
+/* ---- matched-filter line search ------------------------------------------ */
+/* The reference starts every spaxel from a uniform draw inside the bounds (lib/run.py:310-314) and
+ * its only mask helper thresholds the spectrally summed flux (lib/masks.py:17-29).  This entry
+ * contracts every spaxel's prepared data d and 1/variance iv (as d3d_set_data leaves them: a NaN
+ * voxel has d = 0, iv = 0) against a bank of templates T_k, k = i_w * n_c + i_c: the LSF-convolved
+ * unit line of the ctx's line shape at (c, w) = (centres[i_c], widths[i_w]) -- the spectrum the
+ * line kernels write for the parameters (1, c, w); the FSF is not involved --
+ *     N_k = sum_z T_k[z] d[z] iv[z]    Q_k = sum_z T_k[z]^2 iv[z]    s_k = N_k / sqrt(Q_k) (0 if Q_k = 0)
+ * best_out[y*W+x] = the lowest k attaining the maximum of s_k over the candidates with Q_k > 0 and
+ * N_k > 0, or -1 when there is none or the spaxel is masked (the mask given to d3d_set_data; the
+ * NaN rule is in iv); stat_out[(y*W+x)*4 ..] = {N_best, Q_best, s(i_w, i_c - 1), s(i_w, i_c + 1)},
+ * NaN for a neighbour beyond the grid, four zeros where best = -1.  a = N/Q is the amplitude of the
+ * best template, s the detection S/N.  host_bank (may be NULL): [n_w*n_c][D] templates evaluated by
+ * the caller (a host LineModel), used instead of the device's; centres and widths then only give
+ * the grid's shape.  The bank is built, used and freed inside the call; nothing of the chain's
+ * state is written.  D3D_ERR_STATE before taps and data are set; D3D_ERR_UNSUPPORTED on a tile ctx
+ * (d3d_set_tile) and for a bank above 256 MiB (n_w * n_c * D * 8 bytes: search fewer centres at a
+ * time); D3D_ERR_INVALID for an empty grid, a width that is not positive, a value not finite. */
+int d3d_line_search(d3d_ctx *ctx, int n_c, const double *centres, int n_w, const double *widths,
+                    const double *host_bank, int32_t *best_out, double *stat_out);
 
 /* ---- per-spaxel jump scales ---------------------------------------------- */
 /* The reference proposes (c, w) of every spaxel with ONE Cauchy amplitude, jump_amplitude
