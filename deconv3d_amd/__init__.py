@@ -12,6 +12,8 @@ from .math_utils import median_clip  # noqa: F401
 from . import adapt  # noqa: F401
 from . import posterior  # noqa: F401
 from .posterior import PosteriorMoments  # noqa: F401
+from . import prepare  # noqa: F401
+from .prepare import Prepared, prepare_cube  # noqa: F401
 from .run import Run, logger  # noqa: F401
 from . import search  # noqa: F401
 from .search import LineSearch, line_search  # noqa: F401

@@ -40,6 +40,7 @@ SYMBOLS = [
     "d3d_post_end",
     "d3d_adapt_begin", "d3d_adapt_get", "d3d_adapt_set", "d3d_adapt_end",
     "d3d_line_search",
+    "d3d_running_median", "d3d_channel_stats", "d3d_prepare",
 ]
 
 # posterior moments (a table, so that tools/posterior_time.py can load the PARENT commit's library,
@@ -64,6 +65,14 @@ ADAPT_PROTOTYPES = {
 SEARCH_PROTOTYPES = {
     "d3d_line_search": [C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double),
                         C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)],
+}
+# preparation of a raw cube (a table for the same reason)
+PREP_PROTOTYPES = {
+    "d3d_running_median": [C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.c_int, C.POINTER(C.c_double)],
+    "d3d_channel_stats": [C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_double),
+                          C.POINTER(C.c_double), C.POINTER(C.c_int64)],
+    "d3d_prepare": [C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.c_int, C.c_double,
+                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
 }
 POST_CLEAN, POST_CONVOLVED = 1, 2                     # d3d_post_begin: bits of `what`
 POST_PARAMETERS, POST_CLEAN_CUBE, POST_CONVOLVED_CUBE = 0, 1, 2   # d3d_post_get: `which`
@@ -175,7 +184,7 @@ def load():
     lib.d3d_export_updates.argtypes = [ctx_p, C.c_int, C.POINTER(C.c_int), dbl_p]
     lib.d3d_apply_updates.argtypes = [ctx_p, C.c_int, dbl_p]
     for name, argtypes in (list(POST_PROTOTYPES.items()) + list(ADAPT_PROTOTYPES.items())
-                           + list(SEARCH_PROTOTYPES.items())):
+                           + list(SEARCH_PROTOTYPES.items()) + list(PREP_PROTOTYPES.items())):
         getattr(lib, name).argtypes = [ctx_p] + argtypes
     for name in SYMBOLS:
         fn = getattr(lib, name)
@@ -719,3 +728,49 @@ class Engine(object):
                                          _dp(widths), bank_p,
                                          best.ctypes.data_as(C.POINTER(C.c_int32)), _dp(stat)))
         return best, stat
+
+    # -- preparation of a raw cube ------------------------------------------------------
+    def _bytes(self, a, shape, what):
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(np.asarray(a) != 0, dtype=np.uint8)
+        if a.shape != tuple(shape):
+            raise ValueError("%s: expected shape %s, got %s" % (what, tuple(shape), a.shape))
+        return a, a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+    def running_median(self, cube, half_window, valid=None):
+        """include/deconv3d_hip.h: d3d_running_median -- the median along z of every voxel's
+        ``2 half_window + 1`` window over the valid voxels (``valid``: (D,H,W), non-zero = valid;
+        default the finite ones)."""
+        cube = _c64(cube, self.shape)
+        valid, valid_p = self._bytes(valid, self.shape, "valid")
+        out = np.empty(self.shape, dtype=np.float64)
+        _check(self._lib.d3d_running_median(self._ctx, _dp(cube), valid_p, int(half_window), _dp(out)))
+        return out
+
+    def channel_stats(self, cube, select=None):
+        """include/deconv3d_hip.h: d3d_channel_stats -- ``(median, mad, count)`` of every channel
+        plane over the finite voxels of the spaxels ``select`` (H,W) marks (default all)."""
+        cube = _c64(cube, self.shape)
+        select, select_p = self._bytes(select, self.shape[1:], "select")
+        depth = self.shape[0]
+        m, mad = np.empty(depth), np.empty(depth)
+        n = np.empty(depth, dtype=np.int64)
+        _check(self._lib.d3d_channel_stats(self._ctx, _dp(cube), select_p, _dp(m), _dp(mad),
+                                           n.ctypes.data_as(C.POINTER(C.c_int64))))
+        return m, mad, n
+
+    def prepare(self, cube, half_window, reject=None, select=None):
+        """include/deconv3d_hip.h: d3d_prepare -- ``(continuum, residual, median, sigma, count)``:
+        the running-median continuum, ``cube - continuum`` and per channel the residual's median,
+        ``1.4826 MAD`` (NaN: no information) and count; ``reject``: sigmas of the one rejection
+        pass, ``None`` for none."""
+        cube = _c64(cube, self.shape)
+        select, select_p = self._bytes(select, self.shape[1:], "select")
+        cont = np.empty(self.shape, dtype=np.float64)
+        res = np.empty(self.shape, dtype=np.float64)
+        chan = np.empty((self.shape[0], 3), dtype=np.float64)
+        _check(self._lib.d3d_prepare(self._ctx, _dp(cube), select_p, int(half_window),
+                                     float("nan") if reject is None else float(reject),
+                                     _dp(cont), _dp(res), _dp(chan)))
+        return cont, res, chan[:, 0].copy(), chan[:, 1].copy(), chan[:, 2].astype(np.int64)

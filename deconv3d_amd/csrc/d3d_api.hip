@@ -802,6 +802,10 @@ int d3d_ctx_get_option(d3d_ctx *c, const char *key, long *value) {
         *value = key[7] == 'b' ? c->search_bank_ns : c->search_kernel_ns;
         return D3D_OK;
     }
+    if (!strcmp(key, "prep_median_ns") || !strcmp(key, "prep_stats_ns")) {  // read-only: the last d3d_prepare etc.
+        *value = key[5] == 'm' ? c->prep_median_ns : c->prep_stats_ns;
+        return D3D_OK;
+    }
     // read-only, derived: what the context actually runs
     if (!strcmp(key, "mh_nt_ivar_on")) {  // the beyond-the-Infinity-Cache policy of k_mh_ws is in effect
         *value = c->mh_nt_ivar ? 1 : 0;
@@ -1882,6 +1886,32 @@ int d3d_line_search(d3d_ctx *c, int n_c, const double *centres, int n_w, const d
          "line search on a tile: search the whole cube on one context and cut the map");
     NEED(c->have_taps && c->have_data, D3D_ERR_STATE, "taps/data not set");
     return line_search(c, n_c, centres, n_w, widths, host_bank, best_out, stat_out);
+}
+
+int d3d_running_median(d3d_ctx *c, const double *cube, const uint8_t *valid, int half_window, double *out) {
+    NEED(c && cube && out, D3D_ERR_INVALID, "NULL argument");
+    NEED(half_window >= 1 && half_window <= 128, D3D_ERR_INVALID,
+         "running median: half_window = %d is outside 1 .. 128", half_window);
+    NEED(!c->tiled, D3D_ERR_UNSUPPORTED, "running median on a tile: prepare the whole cube on one context");
+    return prep_running_median(c, cube, valid, half_window, out);
+}
+
+int d3d_channel_stats(d3d_ctx *c, const double *cube, const uint8_t *select, double *m_out, double *mad_out,
+                      int64_t *n_out) {
+    NEED(c && cube && m_out && mad_out && n_out, D3D_ERR_INVALID, "NULL argument");
+    NEED(!c->tiled, D3D_ERR_UNSUPPORTED, "channel statistics on a tile: prepare the whole cube on one context");
+    return prep_channel_stats(c, cube, select, m_out, mad_out, n_out);
+}
+
+int d3d_prepare(d3d_ctx *c, const double *cube, const uint8_t *select, int half_window, double reject,
+                double *continuum_out, double *residual_out, double *chan_out) {
+    NEED(c && cube && continuum_out && residual_out && chan_out, D3D_ERR_INVALID, "NULL argument");
+    NEED(half_window >= 1 && half_window <= 128, D3D_ERR_INVALID,
+         "prepare: half_window = %d is outside 1 .. 128", half_window);
+    NEED(reject != reject || reject > 0.0, D3D_ERR_INVALID,
+         "prepare: reject = %g is not a positive number of sigmas (NaN: no rejection pass)", reject);
+    NEED(!c->tiled, D3D_ERR_UNSUPPORTED, "prepare on a tile: prepare the whole cube on one context and cut it");
+    return prep_prepare(c, cube, select, half_window, reject, continuum_out, residual_out, chan_out);
 }
 
 int d3d_adapt_begin(d3d_ctx *c, double target, int window, int64_t last_sweep, double gain,

@@ -1,7 +1,8 @@
 // Internal header of libdeconv3d_hip.so: the context struct and the launch
 // functions shared by the library's translation units (d3d_api.hip: C ABI and host
 // logic; d3d_spatial.hip: line / LSF / FSF kernels; d3d_mh.hip: the MH-within-Gibbs
-// kernels; d3d_post.hip: posterior moments; d3d_search.hip: the matched-filter line search).
+// kernels; d3d_post.hip: posterior moments; d3d_search.hip: the matched-filter line search;
+// d3d_prep.hip: continuum removal and channel noise of a raw cube).
 // Not installed: the public interface is include/deconv3d_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -290,6 +291,10 @@ struct d3d_ctx {
     // of a host bank) and of its search kernel, by HIP events (read-only options search_bank_ns /
     // search_kernel_ns)
     long search_bank_ns = 0, search_kernel_ns = 0;
+    // d3d_running_median / d3d_channel_stats / d3d_prepare: device time of the last call's
+    // running-median and channel-statistics kernels (both passes of a rejecting d3d_prepare summed),
+    // by HIP events (read-only options prep_median_ns / prep_stats_ns)
+    long prep_median_ns = 0, prep_stats_ns = 0;
 };
 
 namespace d3dh {
@@ -318,6 +323,13 @@ int adapt_after_sweep(d3d_ctx *c, int s);
 constexpr size_t SEARCH_BANK_BUDGET = (size_t)256 << 20;
 int line_search(d3d_ctx *c, int n_c, const double *centres, int n_w, const double *widths,
                 const double *host_bank, int *best_out, double *stat_out);
+// d3d_prep.hip: d3d_running_median, d3d_channel_stats and d3d_prepare (arguments already validated);
+// every buffer lives inside the call
+int prep_running_median(d3d_ctx *c, const double *cube, const uint8_t *valid, int half_window, double *out);
+int prep_channel_stats(d3d_ctx *c, const double *cube, const uint8_t *select, double *m_out, double *mad_out,
+                       int64_t *n_out);
+int prep_prepare(d3d_ctx *c, const double *cube, const uint8_t *select, int half_window, double reject,
+                 double *continuum_out, double *residual_out, double *chan_out);
 bool zmajor_ok(const d3d_ctx *c);
 // LSF (x) FSF of c->stage in the reference layout (D,H,W), in place (zmajor_ok())
 int launch_zmajor_convolve(d3d_ctx *c);

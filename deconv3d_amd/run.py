@@ -35,7 +35,7 @@ from os.path import splitext
 
 import numpy as np
 
-from . import _lib, adapt as _adapt, posterior as _posterior, search as _search
+from . import _lib, adapt as _adapt, posterior as _posterior, prepare as _prepare, search as _search
 from .cube import Cube, read_fits
 from .instruments import Instrument
 from .line_models import (LineModel, SingleGaussianLineModel, SINGLE_LINE_SHAPE,
@@ -125,6 +125,17 @@ class Run:
     that R-hat still sees dispersed starts; spaxels without a detection keep their uniform draw.
     ``run.search`` is the :class:`deconv3d_amd.search.LineSearch` (``snr``, ``parameters``,
     ``mask(threshold)``).  Refused with ``initial_parameters=`` or ``resume_state=``.
+
+    ``prepare=True`` (or a dict of :func:`deconv3d_amd.prepare.prepare_cube` keywords
+    ``continuum_window`` / ``reject`` / ``noise_mask`` / ``rescale``; default ``None``: off, nothing
+    allocated or launched, the chain is bit for bit what it is without the keyword) runs
+    ``prepare_cube`` on the raw cube first: the run then fits the continuum-free cube
+    (``run.cube``) and, when ``variance=`` is None, uses the per-channel variance estimated from
+    it instead of the one constant of lib/run.py:171-178; with ``rescale=True`` the given variance
+    is rescaled channel by channel instead.  ``run.prepared`` is the
+    :class:`deconv3d_amd.prepare.Prepared` (``continuum``, ``sigma``, ...).  ``initial_search=``
+    sees the prepared cube.  The checkpoint records the settings; ``resume_state=`` runs the
+    preparation again and refuses a state written with other settings.
     """
 
     def __init__(
@@ -157,8 +168,10 @@ class Run:
         adapt_gain=2.0,
         adapt_scale_range=(1e-3, 1e3),
         initial_search=None,
+        prepare=None,
     ):
         # (before anything else: no device work yet)
+        prepare_cfg = _prepare.check_keywords(prepare)
         search_cfg = _search.check_keywords(initial_search, initial_parameters, resume_state)
         if posterior_burn_in is not None:     # (before anything else: no device work yet)
             posterior_burn_in, posterior_every = _posterior.check_schedule(posterior_burn_in,
@@ -195,6 +208,19 @@ class Run:
             raise TypeError("Provided cube is not a HyperspectralCube")
         if cube.is_empty():
             raise ValueError("Provided cube is empty")
+        # ---- prepare=: the continuum-free cube and its per-channel variance take the place of
+        # the raw cube and of a variance that was not given (or, rescale=True, of the given one)
+        self.prepared = None
+        if prepare_cfg is not None:
+            given = variance if prepare_cfg["rescale"] else None
+            if prepare_cfg["rescale"] and variance is None:
+                raise ValueError("prepare=dict(rescale=True) needs the variance= cube it rescales")
+            self.prepared = _prepare.prepare_cube(
+                cube, prepare_cfg["continuum_window"], prepare_cfg["reject"], prepare_cfg["noise_mask"],
+                variance=given, rescale=prepare_cfg["rescale"], device=device)
+            cube = self.prepared.cube
+            if variance is None or prepare_cfg["rescale"]:
+                variance = self.prepared.variance
         self.cube = cube
         signal_max = np.nanmax(self.cube.data)
         assert signal_max > 1e-10, \
@@ -380,6 +406,8 @@ class Run:
             self.sweep_origin = int(state["sweep_origin"]) + int(state["iteration"]) - 1
             resumed_adapt = _adapt.check_resume(state, files, adapt_cfg, n_chains,
                                                 (cube_height, cube_width))
+            _prepare.check_resume(state, files,
+                                  None if self.prepared is None else self.prepared.settings)
             # totals over every earlier segment (older checkpoints hold one segment's)
             resumed_accepted = (
                 int(state["total_accepted"] if "total_accepted" in files else state["accepted_count"]),
@@ -645,6 +673,8 @@ class Run:
         if self.line_shape is not None:     # (resume_state= checks it)
             state["line_offsets"] = np.array(self.line_shape[0], dtype=np.float64)
             state["line_ratios"] = np.array(self.line_shape[1], dtype=np.float64)
+        if self.prepared is not None:       # (resume_state= checks them)
+            state["prepare_settings"] = _prepare.settings_record(self.prepared.settings)
         if self._adapt_cfg is not None:     # (resume_state= checks the keywords, restores the rest)
             got = [eng.adapt_get() for eng in self.engines]
             state["adapt_keywords"] = _adapt.keyword_record(self._adapt_cfg)

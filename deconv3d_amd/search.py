@@ -215,19 +215,33 @@ class _Runner(object):
 
 
 def line_search(cube, instrument, variance=None, mask=None, model=SingleGaussianLineModel,
-                centres=None, widths=None, device=0):
+                centres=None, widths=None, device=0, prepare=None):
     """
     Matched-filter search of ``cube`` (FITS path or Cube) for the line of ``model`` as
     ``instrument`` sees it; ``variance``, ``mask``, ``model`` as :class:`Run` takes them
     (without a variance: the clipped noise estimate of lib/run.py:171-178).  ``centres``:
     uniformly spaced channels (default every integer channel); ``widths``: channels (default 8
     geometric steps from 0.75 to max(D / 6, 1.5)).  Returns a :class:`LineSearch`.  Masked
-    spaxels are not detected; a NaN voxel only loses its weight.
+    spaxels are not detected; a NaN voxel only loses its weight.  ``prepare``: ``True`` or a dict
+    of :func:`deconv3d_amd.prepare.prepare_cube` keywords -- search the continuum-free cube with
+    its per-channel variance (or, ``rescale=True``, the given variance rescaled) instead.
     """
+    from . import prepare as _prepare
     from .cube import Cube, read_fits
     from .masks import read_hyperspectral_cube
     centres, widths, _ = check_grid(centres, widths)          # (before any device work)
+    prepare_cfg = _prepare.check_keywords(prepare)
     cube = read_hyperspectral_cube(cube)
+    if prepare_cfg is not None:
+        if prepare_cfg["rescale"] and variance is None:
+            raise ValueError("prepare=dict(rescale=True) needs the variance= cube it rescales")
+        prepared = _prepare.prepare_cube(
+            cube, prepare_cfg["continuum_window"], prepare_cfg["reject"], prepare_cfg["noise_mask"],
+            variance=variance if prepare_cfg["rescale"] else None, rescale=prepare_cfg["rescale"],
+            device=device)
+        cube = prepared.cube
+        if variance is None or prepare_cfg["rescale"]:
+            variance = prepared.variance
     if not isinstance(instrument, Instrument):
         raise TypeError("Provided instrument is not an Instrument")
     depth, height, width = cube.data.shape

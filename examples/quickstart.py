@@ -110,6 +110,35 @@ for label, more in (("searched start", dict(initial_search=True)), ("uniform sta
         label, few["max_iterations"], np.mean(((cube.data - r.simulate_convolved(cube.data.shape, r.chain[-1])) / sigma) ** 2)))
 
 
+# ---- a raw cube: continuum removal and channel noise --------------------------------------------
+# An archive cube has stellar continuum under the line and a noise that changes with the channel
+# (sky lines).  prepare_cube takes the running median of every spectrum as the continuum and
+# 1.4826 MAD of every channel of the residual as its noise, both on the device; Run(prepare=True)
+# and line_search(prepare=True) do it first and use the prepared cube and its variance.
+from deconv3d_amd import prepare_cube  # noqa: E402
+
+true_sigma = sigma * (1. + 2. * rng.random(D))                     # channel-dependent noise
+continuum = (20. * sigma * rng.random((H, W))[None]
+             + (rng.random((H, W))[None] - 0.5) * 0.5 * sigma * np.arange(float(D))[:, None, None])
+raw = inst.build_cube(clean + rng.normal(0., 1., clean.shape) * true_sigma[:, None, None] + continuum)
+sky = r2 > (H / 3.) ** 2
+prep = prepare_cube(raw, continuum_window=31, reject=3.0, noise_mask=sky)
+print("prepared cube: per-channel sigma / truth, median %.3f; continuum error %.2f sigma rms" % (
+    np.median(prep.sigma / true_sigma),
+    np.sqrt(np.mean(((prep.continuum - continuum) / true_sigma[:, None, None]) ** 2))))
+for label, kw in (("raw cube, true variance", dict(variance=np.ones(clean.shape) * (true_sigma ** 2)[:, None, None])),
+                  ("prepared", dict(prepare=dict(continuum_window=31, noise_mask=sky)))):
+    f = line_search(raw, inst, **kw)
+    ok = f.snr >= 5.
+    print("line search on the %s: %d spaxels at S/N >= 5, %d of them within one channel of the truth" % (
+        label, ok.sum(), (np.abs(f.parameters[..., 1] - truth[..., 1])[ok] <= 1.).sum()))
+r = Run(raw, inst, prepare=dict(continuum_window=31, noise_mask=sky), initial_search=True, **{
+    k: v for k, v in few.items() if k != "variance"})
+print("Run(prepare=...): %d channels with a noise estimate; reduced chi2 of the last sample against the prepared "
+      "cube %.3f" % (np.isfinite(r.prepared.sigma).sum(),
+                     np.mean((r.cube.data - r.simulate_convolved(r.cube.data.shape, r.chain[-1])) ** 2 / r.variance_cube)))
+
+
 # ---- several chains at once: chains=R ----------------------------------------------------------
 # The reference's own science fixture (tests/input/data14forAntoine.mat: 24 x 30 spaxels x 21
 # channels, settings of its tests/read_mat.py:94-121).  A colour launch of so small a cube holds

@@ -101,7 +101,8 @@ int d3d_timer_stop(d3d_ctx *ctx, double *elapsed_ms);
  * d3d_ctx_get_option also answers the read-only key "chain_parts": how many of the
  * ctx's parts run their sweeps as one launch of persistent workgroups (k_mh_chain), and
  * "search_bank_ns" / "search_kernel_ns": device time of the last d3d_line_search call's bank build
- * and of its search kernel. */
+ * and of its search kernel, and "prep_median_ns" / "prep_stats_ns": device time of the running-median
+ * and channel-statistics kernels of the last d3d_running_median / d3d_channel_stats / d3d_prepare. */
 int d3d_ctx_set_option(d3d_ctx *ctx, const char *key, long value);
 int d3d_ctx_get_option(d3d_ctx *ctx, const char *key, long *value);
 /* 1 when the library was built with `make EXPERIMENTS=1` (the measured-but-not-faster
@@ -300,6 +301,43 @@ int d3d_post_end(d3d_ctx *ctx);
  * time); D3D_ERR_INVALID for an empty grid, a width that is not positive, a value not finite. */
 int d3d_line_search(d3d_ctx *ctx, int n_c, const double *centres, int n_w, const double *widths,
                     const double *host_bank, int32_t *best_out, double *stat_out);
+
+/* ---- preparing a raw cube: continuum removal and channel noise ------------ */
+/* The chain and d3d_line_search fit one line on a zero baseline, and without a variance cube the
+ * reference takes ONE constant for the whole cube, median_clip(data[2:-2, 2:-4, 2:4], 2.5)
+ * (lib/run.py:171-192; 1e12 is its "no information" variance, lib/run.py:180).  These entries remove
+ * the continuum under the line and estimate the noise of every channel.  Host layout (D,H,W), fp64;
+ * finite(v): neither NaN nor +-inf.  Both selections are exact; an even count n gives
+ * (lo + hi) * 0.5 of the two middle order statistics, an odd one the middle one, n = 0 NaN
+ * (numpy.nanmedian, bit for bit; -0.0 and 0.0 may come out as either).
+ *
+ * d3d_running_median: out[z,y,x] = the median of {cube[z',y,x] : max(0, z - half_window) <= z' <=
+ * min(D - 1, z + half_window), valid[z',y,x]} -- the window shrinks at the ends and skips invalid
+ * voxels; defined at every voxel, invalid ones included.  valid (may be NULL: finite(cube)):
+ * (D,H,W) bytes, non-zero = valid; a NaN voxel is never valid.  1 <= half_window <= 128; a half
+ * window of D or more is the whole spectrum.  The kernel counts ranks: O((2 half_window + 1)^2)
+ * comparisons per voxel.
+ *
+ * d3d_channel_stats: over the spaxels with select[y*W+x] != 0 (NULL: all) and finite(cube[z,y,x]):
+ * n_out[z] their count, m_out[z] their median, mad_out[z] the median of |cube[z,y,x] - m_out[z]|;
+ * NaN, NaN, 0 where there is none.
+ *
+ * d3d_prepare: (1) valid0 = finite(cube), cont = running median of (cube, valid0), res = cube - cont;
+ * (2) (m, mad, n) = channel statistics of (res, select), sigma_z = 1.4826 mad_z, NaN where n_z < 2
+ * or mad_z == 0; (3) unless reject is NaN, ONE rejection pass: valid1 = valid0 & (|res| <= reject *
+ * sigma_z) (a channel whose sigma is NaN rejects nothing), cont and res again with valid1, and (2)
+ * again.  continuum_out, residual_out: (D,H,W); chan_out[z*3 ..] = {m_z, sigma_z, n_z}.  No cube
+ * crosses to the host in between (the [D][3] statistics do).
+ *
+ * All three allocate and free everything inside the call, need neither taps nor data, and write
+ * nothing of the chain's state (DATA, IVAR, ERR, SIM, parameters, RNG counters).
+ * D3D_ERR_INVALID: half_window outside 1..128, reject zero or negative; D3D_ERR_UNSUPPORTED on a
+ * tile ctx (d3d_set_tile). */
+int d3d_running_median(d3d_ctx *ctx, const double *cube, const uint8_t *valid, int half_window, double *out);
+int d3d_channel_stats(d3d_ctx *ctx, const double *cube, const uint8_t *select, double *m_out, double *mad_out,
+                      int64_t *n_out);
+int d3d_prepare(d3d_ctx *ctx, const double *cube, const uint8_t *select, int half_window, double reject,
+                double *continuum_out, double *residual_out, double *chan_out);
 
 /* ---- per-spaxel jump scales ---------------------------------------------- */
 /* The reference proposes (c, w) of every spaxel with ONE Cauchy amplitude, jump_amplitude
