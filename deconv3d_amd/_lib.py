@@ -39,6 +39,7 @@ SYMBOLS = [
     "d3d_post_begin", "d3d_post_schedule", "d3d_post_accumulate", "d3d_post_count", "d3d_post_get",
     "d3d_post_end",
     "d3d_adapt_begin", "d3d_adapt_get", "d3d_adapt_set", "d3d_adapt_end",
+    "d3d_prior_begin", "d3d_prior_get", "d3d_prior_end", "d3d_prior_energy",
     "d3d_line_search",
     "d3d_running_median", "d3d_channel_stats", "d3d_prepare",
 ]
@@ -60,6 +61,13 @@ ADAPT_PROTOTYPES = {
                       C.POINTER(C.c_int64)],
     "d3d_adapt_set": [C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_int64, C.c_int64],
     "d3d_adapt_end": [],
+}
+# smoothness prior between neighbouring spaxels (a table for the same reason)
+PRIOR_PROTOTYPES = {
+    "d3d_prior_begin": [C.POINTER(C.c_double)],
+    "d3d_prior_get": [C.POINTER(C.c_double), C.POINTER(C.c_int)],
+    "d3d_prior_end": [],
+    "d3d_prior_energy": [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)],
 }
 # matched-filter line search (a table for the same reason)
 SEARCH_PROTOTYPES = {
@@ -184,7 +192,8 @@ def load():
     lib.d3d_export_updates.argtypes = [ctx_p, C.c_int, C.POINTER(C.c_int), dbl_p]
     lib.d3d_apply_updates.argtypes = [ctx_p, C.c_int, dbl_p]
     for name, argtypes in (list(POST_PROTOTYPES.items()) + list(ADAPT_PROTOTYPES.items())
-                           + list(SEARCH_PROTOTYPES.items()) + list(PREP_PROTOTYPES.items())):
+                           + list(SEARCH_PROTOTYPES.items()) + list(PREP_PROTOTYPES.items())
+                           + list(PRIOR_PROTOTYPES.items())):
         getattr(lib, name).argtypes = [ctx_p] + argtypes
     for name in SYMBOLS:
         fn = getattr(lib, name)
@@ -709,6 +718,40 @@ class Engine(object):
 
     def adapt_end(self):
         _check(self._lib.d3d_adapt_end(self._ctx))
+
+    # -- smoothness prior between neighbouring spaxels ----------------------------------
+    def prior_begin(self, lam):
+        """Turn the pairwise Gaussian prior between 4-neighbours on with ``lam = 1 / sigma^2`` of
+        (a, c, w) (include/deconv3d_hip.h: d3d_prior_begin)."""
+        lam = np.ascontiguousarray(lam, dtype=np.float64).reshape(-1)
+        if lam.size != 3:
+            raise ValueError("lam MUST hold the 3 values of (a, c, w), got %d" % lam.size)
+        _check(self._lib.d3d_prior_begin(self._ctx, _dp(lam)))
+
+    def prior_get(self):
+        """(lam, on): the prior's weights as begun (zeros when off) and whether it is on."""
+        lam = np.zeros(3, dtype=np.float64)
+        on = C.c_int(0)
+        _check(self._lib.d3d_prior_get(self._ctx, _dp(lam), C.byref(on)))
+        return lam, bool(on.value)
+
+    def prior_end(self):
+        _check(self._lib.d3d_prior_end(self._ctx))
+
+    def prior_energy(self, params=None):
+        """(E_a, E_c, E_w, pairs): the sums of squared differences between unmasked 4-neighbours
+        of an (H,W,3) map (None: the current parameters), summed on the device."""
+        pp = None
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=np.float64)
+            if params.shape != tuple(self.shape[1:]) + (3,):
+                raise ValueError("parameter map MUST have shape %s, got %s"
+                                 % (tuple(self.shape[1:]) + (3,), params.shape))
+            pp = _dp(params)
+        energy = np.zeros(3, dtype=np.float64)
+        pairs = C.c_int64(0)
+        _check(self._lib.d3d_prior_energy(self._ctx, pp, _dp(energy), C.byref(pairs)))
+        return float(energy[0]), float(energy[1]), float(energy[2]), int(pairs.value)
 
     # -- matched-filter line search ---------------------------------------------------
     def line_search(self, centres, widths, bank=None):

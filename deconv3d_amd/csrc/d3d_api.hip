@@ -430,6 +430,23 @@ int adapt_kernels_ok(const d3d_ctx *c) {
     return 0;
 }
 
+// The smoothness prior reads a spaxel's neighbours as they are when it is decided.  That holds
+// where a launch decides ONE colour class from the parameters in memory: the kernels that decide
+// several classes in a launch, or keep parameters on chip across colours (EXPERIMENTS builds),
+// and the contexts whose parts or tiles run beside each other are refused, never ignored.
+int prior_kernels_ok(const d3d_ctx *c) {
+    NEED(!c->mh_chain_opt && !c->mh_flow && !c->mh_pair, D3D_ERR_UNSUPPORTED,
+         "smoothness prior (d3d_prior_begin) with option %s: k_mh_chain, k_mh_flow and k_mh_pair decide "
+         "more than one colour class in a launch",
+         c->mh_chain_opt ? "mh_chain" : c->mh_flow ? "mh_flow" : "mh_pair");
+    NEED(!c->tiled, D3D_ERR_UNSUPPORTED,
+         "smoothness prior on a tile: the neighbours across its edge belong to other ranks");
+    NEED(c->part_rects.size() <= 1 && c->parts.size() <= 1, D3D_ERR_UNSUPPORTED,
+         "smoothness prior on a context cut into %zu parts (d3d_set_parts): parts of one phase are "
+         "not ordered against each other", std::max(c->part_rects.size(), c->parts.size()));
+    return 0;
+}
+
 // count 0, accumulators zero (Welford's first sample starts from mean = M2 = 0)
 int post_reset(d3d_ctx *c) {
     if (!c->post_on) return 0;
@@ -704,6 +721,7 @@ int d3d_ctx_destroy(d3d_ctx *c) {
         if (p) (void)hipFree(p);
     if (c->post_map) (void)hipFree(c->post_map);
     adapt_free(c);
+    if (c->prior_part) (void)hipFree(c->prior_part);
     for (hipEvent_t e : c->halo_ev) (void)hipEventDestroy(e);
     for (int s = 0; s < D3D_SLOT_COUNT; ++s)
         if (c->slot[s]) (void)hipFree(c->slot[s]);
@@ -778,6 +796,11 @@ int d3d_ctx_set_option(d3d_ctx *c, const char *key, long value) {
         return fail(D3D_ERR_UNSUPPORTED,
                     "option %s with per-spaxel jump scales on (d3d_adapt_begin): the kernel keeps its "
                     "proposals' inputs across sweeps", key);
+    if (c->prior_on && value != 0 &&
+        (!strcmp(key, "mh_chain") || !strcmp(key, "mh_flow") || !strcmp(key, "mh_pair")))
+        return fail(D3D_ERR_UNSUPPORTED,
+                    "option %s with the smoothness prior on (d3d_prior_begin): the kernel decides more "
+                    "than one colour class in a launch", key);
     if (o->kind == OPT_MH)  // pending layers belong to the old kernel selection
         if (int rc = flush_pending(c)) return rc;
     c->*(o->field) = (int)value;
@@ -1721,6 +1744,9 @@ int d3d_mh_sweeps_batch(d3d_ctx **ctxs, int n_ctx, int n_sweeps, int first_sweep
              "ctx %d: another line shape than ctx 0 (the chains share the launch's arguments)", r);
         // (the chains share the leader's pending-layer state, and a from-scratch residual
         // clears a chain's own: they must all be rebuilt at the same sweeps)
+        NEED(c->prior_on == L->prior_on, D3D_ERR_INVALID,
+             "ctx %d: the smoothness prior (d3d_prior_begin) is %s, on ctx 0 it is %s (the chains share the "
+             "launch's kernel; their weights may differ)", r, c->prior_on ? "on" : "off", L->prior_on ? "on" : "off");
         NEED(c->refresh_every == L->refresh_every, D3D_ERR_INVALID,
              "ctx %d: refresh_every %d differs from ctx 0's %d (batched chains rebuild their residuals together)",
              r, c->refresh_every, L->refresh_every);
@@ -1992,6 +2018,65 @@ int d3d_adapt_end(d3d_ctx *c) {
     return D3D_OK;
 }
 
+int d3d_prior_begin(d3d_ctx *c, const double lam[3]) {
+    NEED(c && lam, D3D_ERR_INVALID, "NULL argument");
+    for (int k = 0; k < 3; ++k)
+        NEED(std::isfinite(lam[k]) && lam[k] >= 0.0, D3D_ERR_INVALID,
+             "lam[%d] = %g: finite and >= 0 (1 / sigma^2 of the neighbour differences)", k, lam[k]);
+    NEED(c->fh > 1 && c->fw > 1, D3D_ERR_INVALID,
+         "smoothness prior with a %d x %d FSF: adjacent spaxels would share a colour class", c->fh, c->fw);
+    if (int rc = prior_kernels_ok(c)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 3; ++k) c->prior_lam[k] = lam[k];
+    c->prior_on = true;
+    c->props_sweep = -1;
+    return D3D_OK;
+}
+
+int d3d_prior_get(d3d_ctx *c, double lam[3], int *on) {
+    NEED(c && lam && on, D3D_ERR_INVALID, "NULL argument");
+    for (int k = 0; k < 3; ++k) lam[k] = c->prior_on ? c->prior_lam[k] : 0.0;
+    *on = c->prior_on ? 1 : 0;
+    return D3D_OK;
+}
+
+int d3d_prior_end(d3d_ctx *c) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->prior_on = false;
+    c->prior_lam[0] = c->prior_lam[1] = c->prior_lam[2] = 0.0;
+    c->props_sweep = -1;
+    return D3D_OK;
+}
+
+int d3d_prior_energy(d3d_ctx *c, const double *params, double energy[3], int64_t *pairs) {
+    NEED(c && energy && pairs, D3D_ERR_INVALID, "NULL argument");
+    NEED(params || c->have_params, D3D_ERR_STATE, "parameters not set");
+    HIP_TRY(hipSetDevice(c->device));
+    double *tmp = nullptr;
+    if (params) {
+        HIP_TRY(hipMalloc(&tmp, (size_t)c->HW * 3 * sizeof(double)));
+        hipError_t e = hipMemcpyAsync(tmp, params, (size_t)c->HW * 3 * sizeof(double), hipMemcpyHostToDevice,
+                                      c->stream);
+        if (e != hipSuccess) {
+            (void)hipFree(tmp);
+            HIP_TRY(e);
+        }
+    }
+    double out4[4] = {0.0, 0.0, 0.0, 0.0};
+    const int rc = d3dh::prior_energy(c, tmp ? tmp : c->params, out4);
+    if (tmp) {
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(tmp);
+    }
+    if (rc) return rc;
+    for (int k = 0; k < 3; ++k) energy[k] = out4[k];
+    *pairs = (int64_t)out4[3];
+    return D3D_OK;
+}
+
 int d3d_get_dlog(d3d_ctx *c, double *out_hw) {
     NEED(c && out_hw, D3D_ERR_INVALID, "NULL argument");
     HIP_TRY(hipMemcpyAsync(out_hw, c->dlog, (size_t)c->HW * sizeof(double), hipMemcpyDeviceToHost,
@@ -2072,6 +2157,8 @@ int d3d_set_tile(d3d_ctx *c, int gy0, int gx0, int Wg, int oy0, int oy1, int ox0
          D3D_ERR_INVALID, "owned rectangle [%d,%d)x[%d,%d) outside the tile", oy0, oy1, ox0, ox1);
     NEED(!c->adapt_on, D3D_ERR_UNSUPPORTED,
          "per-spaxel jump scales are on (d3d_adapt_begin): not on a tile; call d3d_adapt_end first");
+    NEED(!c->prior_on, D3D_ERR_UNSUPPORTED,
+         "the smoothness prior is on (d3d_prior_begin): not on a tile; call d3d_prior_end first");
     c->gy0 = gy0;
     c->gx0 = gx0;
     c->Wg = Wg;
@@ -2091,6 +2178,9 @@ int d3d_set_parts(d3d_ctx *c, int nparts, const int *rects, const int *phases) {
     NEED(c, D3D_ERR_INVALID, "ctx is NULL");
     NEED(nparts >= 0 && nparts <= 4096 && (nparts == 0 || (rects && phases)), D3D_ERR_INVALID,
          "bad part list");
+    NEED(!c->prior_on || nparts <= 1, D3D_ERR_UNSUPPORTED,
+         "the smoothness prior is on (d3d_prior_begin): not on a context cut into parts; call "
+         "d3d_prior_end first");
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = flush_pending(c)) return rc;
     std::vector<int4> rr;
@@ -2188,6 +2278,9 @@ int d3d_mh_colour_lines(d3d_ctx *c, int sweep, int n, const int *spaxels, const 
     NEED(n >= 0 && sweep >= 0, D3D_ERR_INVALID, "bad count / sweep");
     if (n == 0) return D3D_OK;
     NEED(spaxels && in3 && lines && out3, D3D_ERR_INVALID, "NULL argument");
+    NEED(!c->prior_on, D3D_ERR_UNSUPPORTED,
+         "the smoothness prior is on (d3d_prior_begin): a host-evaluated model's parameters are not the "
+         "context's (a, c, w); call d3d_prior_end first");
     NEED(c->have_taps && c->have_data && c->have_cfg && c->err_valid, D3D_ERR_STATE,
          "taps/data/mh_config/residual not set");
     NEED(n <= c->HW, D3D_ERR_INVALID, "too many spaxels");

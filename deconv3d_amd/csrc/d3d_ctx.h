@@ -287,6 +287,11 @@ struct d3d_ctx {
     int64_t adapt_last = 0;        // no step after this sweep (the run's numbering: s + sweep_origin)
     int64_t adapt_n_win = 0;       // sweeps counted since the counters were last cleared
     int64_t adapt_k = 0;           // adaptation steps taken
+    // smoothness prior between 4-neighbours (d3d_prior_*): lam[k] = 1 / sigma_k^2 of (a, c, w), read by
+    // every MH decision (MHArgs::lam).  Nothing is allocated before the first d3d_prior_energy.
+    bool prior_on = false;
+    double prior_lam[3] = {0.0, 0.0, 0.0};
+    double *prior_part = nullptr;  // [PRIOR_BLOCKS + 1][4] block partials | totals of k_prior_energy
     // d3d_line_search: device time of the last call's bank build (lines + transpose, or the transpose
     // of a host bank) and of its search kernel, by HIP events (read-only options search_bank_ns /
     // search_kernel_ns)
@@ -318,6 +323,9 @@ int launch_post_accum(d3d_ctx *c);
 // d3d_mh.hip: after sweep `s` of a d3d_mh_sweeps call (d3d_adapt_begin): the sweep is counted and,
 // where it fills a window at or before the last adapted sweep, the jump scales take a step
 int adapt_after_sweep(d3d_ctx *c, int s);
+// d3d_mh.hip: sums of squared neighbour differences of a parameter map on the device over the
+// adjacent pairs of unmasked spaxels, {E_a, E_c, E_w, pairs} (k_prior_energy)
+int prior_energy(d3d_ctx *c, const double *params_dev, double out4[4]);
 // d3d_search.hip: the matched-filter search of d3d_line_search (arguments already validated).  The
 // template bank is refused above this many bytes of device memory.
 constexpr size_t SEARCH_BANK_BUDGET = (size_t)256 << 20;

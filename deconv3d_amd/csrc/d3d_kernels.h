@@ -1747,6 +1747,10 @@ struct MHChainArgs {  // one chain of a batch: see MHArgs::batch
     // (d3d_adapt_begin: the chain's jump scales and accept counters, NULL when off)
     const double *jscale;
     unsigned *jacc;
+    // (d3d_prior_begin: the chain's weights, as MHArgs::lam; `prior` equals the leader's -- the
+    // chains of a batch share the kernel instantiation)
+    double lam[3];
+    int prior;
 };
 struct MHArgs {
     int D, Dp, HL, H, W, fh, fw, N, ntaps, npos;
@@ -1860,6 +1864,12 @@ struct MHArgs {
     // jacc[sp] (one writer per spaxel and sweep).  NULL: the one amplitude of lib/run.py:251-262.
     const double *jscale;
     unsigned *jacc;
+    // Smoothness prior between 4-neighbours (d3d_prior_begin): log p = -1/2 sum_<i,j> sum_k
+    // lam[k] (theta_i,k - theta_j,k)^2 over the adjacent pairs of unmasked spaxels, k = (a, c, w).
+    // prior == 0: the flat prior of lib/run.py:426-438, 491-496 (lam is not read).  The launchers
+    // read `prior` to pick the kernels' PRIOR = true instantiations; the kernels read lam only.
+    double lam[3];
+    int prior;
 };
 
 #ifdef D3D_EXPERIMENTS
@@ -2077,18 +2087,84 @@ __device__ __forceinline__ void mh_channel_sums(const MHArgs &P, const MHShared 
     }
 }
 
+// The unmasked 4-neighbours of spaxel sp inside the cube (MHArgs::prior): their number and the
+// sums of their parameters, in the fixed order up, down, left, right.  Two spaxels of one colour
+// class are fh rows or fw columns apart (fh, fw >= 2 with the prior on), so no neighbour is
+// updated in the launch that decides sp: read anywhere in it, these are the values at the time
+// of the decision.  (They are NOT part of the sweep's proposal table: the neighbours move
+// between the sweep's colours.)  Every calling lane loads the same addresses.
+struct MHNeigh {
+    double n, sa, sc, sw;
+};
+__device__ __forceinline__ void mh_prior_take(const MHArgs &P, int sp, bool inside, long s, MHNeigh &nb) {
+    // (an address inside the map whatever `inside` says: the load is issued unconditionally)
+    s = inside ? s : (long)sp;
+    const double a = P.params[s * 3 + 0], c = P.params[s * 3 + 1], w = P.params[s * 3 + 2];
+    if (inside && P.mask[s] == 1) {
+        nb.n += 1.0;
+        nb.sa += a;
+        nb.sc += c;
+        nb.sw += w;
+    }
+}
+__device__ __forceinline__ MHNeigh mh_prior_gather(const MHArgs &P, int sp) {
+    MHNeigh nb = {0.0, 0.0, 0.0, 0.0};
+    const int y = sp / P.W, x = sp - y * P.W;
+    mh_prior_take(P, sp, y > 0, (long)sp - P.W, nb);
+    mh_prior_take(P, sp, y + 1 < P.H, (long)sp + P.W, nb);
+    mh_prior_take(P, sp, x > 0, (long)sp - 1, nb);
+    mh_prior_take(P, sp, x + 1 < P.W, (long)sp + 1, nb);
+    return nb;
+}
+
+// What the prior adds to one update, all of it known before the window pass: d to the log
+// acceptance ratio (lib/run.py:426; c and w only: the amplitude does not move in the proposal),
+// ee and eu to the sums of the amplitude's conditional (lib/run.py:491-493).
+struct MHPrior {
+    double d, ee, eu;
+};
+__device__ __forceinline__ MHPrior mh_prior_terms(const MHArgs &P, const MHProposal &q, int sp) {
+    // (no contraction in here: a product left for the caller's addition to fuse would round
+    // differently in the kernels that take the terms from LDS and in those that form them in
+    // place, and the kernel families must stay bit-identical to each other)
+#pragma clang fp contract(off)
+    const MHNeigh N = mh_prior_gather(P, sp);
+    // sum_j lam (p_new - p_old) (p_new + p_old - 2 theta_j)
+    const double dc = (q.pn[1] - q.c_old) * (N.n * (q.pn[1] + q.c_old) - 2.0 * N.sc);
+    const double dw = (q.pn[2] - q.w_old) * (N.n * (q.pn[2] + q.w_old) - 2.0 * N.sw);
+    MHPrior T;
+    T.d = -0.5 * (P.lam[1] * dc + P.lam[2] * dw);
+    T.ee = P.lam[0] * N.n;
+    T.eu = P.lam[0] * N.sa;
+    return T;
+}
+
 // The decision proper, from the seven totals (every lane of the calling wavefront the same
 // numbers): accept, Gibbs draw; the lanes with `writes` set store the new state.
+// pt: the prior's terms (mh_prior_terms) where a prepare wavefront left them in LDS ahead of the
+// decision (NULL: computed here); read by the PRIOR = true instantiations only, each at its point
+// of use.  PRIOR = false is the code without the prior: no branch, no register, no kernel argument read.
+template <bool PRIOR = false>
 __device__ __forceinline__ void mh_decide_core(const MHArgs &P, const MHProposal &q, int sp,
                                                uint32_t sweep, const double (&tot)[7],
                                                const U2 &u_gibbs, bool writes, bool *accept_out,
-                                               double *r_out) {
-    const double delta = -tot[0] - 0.5 * tot[1];  // ar_old - ar_new, lib/run.py:426
+                                               double *r_out, const MHPrior *pt = nullptr) {
+    double delta = -tot[0] - 0.5 * tot[1];  // ar_old - ar_new, lib/run.py:426
+    // (PRIOR: the instantiations d3d_prior_begin selects; the others are the code they were)
+    MHPrior T = {0.0, 0.0, 0.0};
+    if constexpr (PRIOR) {
+        if (!pt) T = mh_prior_terms(P, q, sp);
+        delta += pt ? pt->d : T.d;
+    }
     // ---- MH accept (lib/run.py:435-445) --------------------------------
     const bool accept = (q.log_u < delta) && !q.oob;
     // after an accepted move err = ul - a_new*f*E_new, ul is unchanged
-    const double s_ee = accept ? tot[5] : tot[3];
-    const double s_eu = accept ? tot[6] : tot[4];
+    double s_ee = accept ? tot[5] : tot[3];
+    double s_eu = accept ? tot[6] : tot[4];
+    if constexpr (PRIOR) {
+        s_ee += pt ? pt->ee : T.ee;
+        s_eu += pt ? pt->eu : T.eu;
+    }
     // ---- Gibbs draw of the amplitude (lib/run.py:456-499) --------------
     double r;
     if (P.ext_lines && !P.ext_gibbs) {
@@ -2128,9 +2204,10 @@ __device__ __forceinline__ void mh_decide_core(const MHArgs &P, const MHProposal
 // {accepted, amplitude} in the spare slots behind the wave sums: the fp64
 // special functions of the truncated normal would otherwise be issued by
 // every wavefront of every resident workgroup at the same moment.
+template <bool PRIOR = false>
 __device__ __forceinline__ void mh_decide_wave(const MHArgs &P, const MHShared &S,
                                                const MHProposal &q, int sp, uint32_t sweep, int nw,
-                                               const U2 &u_gibbs) {
+                                               const U2 &u_gibbs, const MHPrior *pt = nullptr) {
     double *verdict = S.sum + 8 * nw;
     double tot[7];
 #pragma unroll
@@ -2154,7 +2231,7 @@ __device__ __forceinline__ void mh_decide_wave(const MHArgs &P, const MHShared &
     }
     bool accept;
     double r;
-    mh_decide_core(P, q, sp, sweep, tot, u_gibbs, lead, &accept, &r);
+    mh_decide_core<PRIOR>(P, q, sp, sweep, tot, u_gibbs, lead, &accept, &r, pt);
     if (lead) {
         verdict[0] = accept ? 1.0 : 0.0;
         verdict[1] = r;
@@ -2175,21 +2252,24 @@ __device__ __forceinline__ double mh_update_coeff(const MHArgs &P, const MHShare
 // first of the nw wavefronts that call this (they are consecutive).  Contains two block
 // barriers that every thread of the workgroup must reach.  Returns false in probe mode
 // and to non-callers.
+template <bool PRIOR = false>
 __device__ __forceinline__ bool mh_finish(const MHArgs &P, const MHShared &S, const MHProposal &q,
                                           int sp, uint32_t sweep, int ch, int G, double EO,
                                           double EN, int first, int nw, bool caller,
                                           double *Gz_out, const U2 *u_pre = nullptr,
-                                          long stamp_at = -1) {
+                                          long stamp_at = -1, const MHPrior *pt = nullptr) {
     // the uniforms of the Gibbs draw depend on nothing the window pass produces:
     // drawn here, ahead of the barrier, they are off the critical tail
     U2 u_gibbs = {0.5, 0.5};
+    // (pt: the smoothness prior's terms where a prepare wavefront left them in LDS with the
+    // proposal; NULL: the deciding wavefront computes them)
     if (caller) {
         u_gibbs = u_pre ? *u_pre : philox_pair(P.seed, q.gsp, sweep, BLK_GIBBS);
         mh_channel_sums(P, S, q, ch, G, EO, EN, first);
     }
     __syncthreads();
     if (stamp_at >= 0) D3D_MH_STAMP(stamp_at, 6, 0);  // channel sums in LDS
-    if (caller && (int)(threadIdx.x >> 6) == first) mh_decide_wave(P, S, q, sp, sweep, nw, u_gibbs);
+    if (caller && (int)(threadIdx.x >> 6) == first) mh_decide_wave<PRIOR>(P, S, q, sp, sweep, nw, u_gibbs, pt);
     __syncthreads();
     if (stamp_at >= 0) D3D_MH_STAMP(stamp_at, 7, 0);  // verdict in LDS
     if (!caller || P.probe) {
@@ -2203,7 +2283,7 @@ __device__ __forceinline__ bool mh_finish(const MHArgs &P, const MHShared &S, co
 // The whole decision with every thread of an NT-thread block taking part
 // (thread t <-> channel t); group partial sums must be in S.red (no barrier
 // needed before the call).
-template <int NT, bool MULTI = false>
+template <int NT, bool MULTI = false, bool PRIOR = false>
 __device__ __forceinline__ bool mh_decide(const MHArgs &P, const MHShared &S, int sp,
                                           uint32_t sweep, double *Gz_out) {
     const int tid = threadIdx.x;
@@ -2221,7 +2301,7 @@ __device__ __forceinline__ bool mh_decide(const MHArgs &P, const MHShared &S, in
     __syncthreads();
     double EO, EN;
     mh_lsf(P, S.gO, S.gN, tid, &EO, &EN);
-    return mh_finish(P, S, q, sp, sweep, tid, NT / P.HL, EO, EN, 0, NT / 64, true, Gz_out);
+    return mh_finish<PRIOR>(P, S, q, sp, sweep, tid, NT / P.HL, EO, EN, 0, NT / 64, true, Gz_out);
 }
 
 #define D3D_ACCUM(e, v, f)                  \
@@ -2238,7 +2318,7 @@ __device__ __forceinline__ bool mh_decide(const MHArgs &P, const MHShared &S, in
 
 // Immediate write-back.  MAXIT > 0: the err window stays in MAXIT double2
 // registers per thread between the passes; MAXIT == 0: pass 2 re-reads it.
-template <int NT, int MAXIT, bool MULTI = false>
+template <int NT, int MAXIT, bool MULTI = false, bool PRIOR = false>
 __global__ __launch_bounds__(NT) void k_mh(MHArgs P, uint32_t sweep) {
     extern __shared__ double smem[];
     const int tid = threadIdx.x;
@@ -2312,7 +2392,7 @@ __global__ __launch_bounds__(NT) void k_mh(MHArgs P, uint32_t sweep) {
     }
 
     double Gt;
-    if (!mh_decide<NT, MULTI>(P, S, sp, sweep, &Gt)) return;
+    if (!mh_decide<NT, MULTI, PRIOR>(P, S, sp, sweep, &Gt)) return;
     if (tid < Dp) S.G[tid] = Gt;
     __syncthreads();
 
@@ -2366,7 +2446,7 @@ __device__ __forceinline__ int covering_coord(int q, int c, int per, int hw, int
 // window position p: [0] local spaxel index of the voxel column (-1 = outside
 // the cube), [1] tap index of the pending update there (-1 = none), [2] which
 // of the <= 4 staged pending G rows.
-template <int NT, bool MULTI = false>
+template <int NT, bool MULTI = false, bool PRIOR = false>
 __global__ __launch_bounds__(NT) void k_mh_defer(MHArgs P, uint32_t sweep) {
     extern __shared__ double smem[];
     const int tid = threadIdx.x;
@@ -2459,7 +2539,7 @@ __global__ __launch_bounds__(NT) void k_mh_defer(MHArgs P, uint32_t sweep) {
 
     if (!real) return;
     double Gt;
-    if (!mh_decide<NT, MULTI>(P, S, sp, sweep, &Gt)) return;
+    if (!mh_decide<NT, MULTI, PRIOR>(P, S, sp, sweep, &Gt)) return;
     if (tid < Dp) P.Gcur[((long)(y / P.fh) * P.slots_x + x / P.fw) * Dp + tid] = Gt;
 }
 
@@ -2761,7 +2841,7 @@ __device__ __forceinline__ void mh_lsf_block(const MHArgs &P, const MHZ &Z, cons
 // with the block's wave sums and its lines handed to k_mh_zdecide (item = the window's index
 // in the launch).
 template <int NS, bool UV, bool COH, int U, int M, bool COHG = COH, bool PRE = false, bool NTV = false,
-          bool PROPS = false, bool ZBK = false, bool MULTI = false>
+          bool PROPS = false, bool ZBK = false, bool MULTI = false, bool PRIOR = false>
 __device__ __forceinline__ void mh_ws_run(const MHArgs &P, const MHShared &S, const MHWsItem &I,
                                           uint32_t sweep, long stamp_at,
                                           const MHPre<U> *pre = nullptr, const MHZ *Zp = nullptr,
@@ -2775,7 +2855,11 @@ __device__ __forceinline__ void mh_ws_run(const MHArgs &P, const MHShared &S, co
     // the LSF-convolved lines per channel; sq: the proposal
     double *sEN = S.sum + 8 * (NS / 64) + 8;
     MHProposal *sq = reinterpret_cast<MHProposal *>(sEN + Dp);
-    static_assert(sizeof(MHProposal) <= 16 * sizeof(double), "proposal does not fit its LDS slot");
+    // ... and, behind it (8 + 3 of the 16 doubles mh_ws_lds_doubles adds), the terms of the
+    // smoothness prior: the prepare wavefront loads the four neighbours with the proposal, long
+    // before the stream ends, so that the deciding wavefront never waits for them
+    MHPrior *spt = reinterpret_cast<MHPrior *>(sq + 1);
+    static_assert(sizeof(MHProposal) + sizeof(MHPrior) <= 16 * sizeof(double), "LDS behind the lines");
     const bool real = I.real != 0;
     const int sp = I.y * P.W + I.x;
     const bool streamer = tid < NS;
@@ -2941,6 +3025,10 @@ __device__ __forceinline__ void mh_ws_run(const MHArgs &P, const MHShared &S, co
             sEN[ch] = EN;
         }
         if (lane == 0) *sq = q;
+        if constexpr (PRIOR && !ZBK) {  // (the z-blocked form decides in k_mh_zdecide)
+            const MHPrior T = mh_prior_terms(P, q, sp);
+            if (lane == 0) *spt = T;
+        }
         D3D_MH_STAMP(stamp_at, 3, NS);  // prepare wavefront done (long before the stream)
     }
     D3D_MH_STAMP(stamp_at, 2, 0);
@@ -2981,7 +3069,8 @@ __device__ __forceinline__ void mh_ws_run(const MHArgs &P, const MHShared &S, co
     // 300x300x128, 31.4 -> 32.1 with uniform variance, same-box A/B, whether or not the other
     // wavefronts end early: with three workgroups per compute unit a second deciding wavefront
     // per window takes issue slots from the neighbours' window passes.  ONE wavefront decides.)
-    if (!mh_finish(P, S, q, sp, sweep, tid, G, EO, EN, 0, NS / 64, streamer, &Gt, &u_gibbs, stamp_at))
+    if (!mh_finish<PRIOR>(P, S, q, sp, sweep, tid, G, EO, EN, 0, NS / 64, streamer, &Gt, &u_gibbs, stamp_at,
+                          PRIOR ? spt : nullptr))
         return;
     if (tid < Dp) {
         double *dst = I.Gcur + ((long)(I.y / P.fh) * P.slots_x + I.x / P.fw) * Dp + tid;
@@ -3008,7 +3097,7 @@ __device__ __forceinline__ void mh_ws_run(const MHArgs &P, const MHShared &S, co
 // (chain-major); the chain's cubes, parameters, bounds and random stream replace the
 // arguments' -- everything else (work list, taps, pending-layer geometry) is common.
 template <int NS, bool UV, int U, int M, int K, int NL = -1, bool NTV = false, bool ZBK = false,
-          bool BATCH = false, bool MULTI = false>
+          bool BATCH = false, bool MULTI = false, bool PRIOR = false>
 __global__ __launch_bounds__(NS + 64) void k_mh_ws(MHArgs P, uint32_t sweep) {
     extern __shared__ double smem[];
     constexpr int NT = NS + 64;
@@ -3038,6 +3127,9 @@ __global__ __launch_bounds__(NS + 64) void k_mh_ws(MHArgs P, uint32_t sweep) {
         P.seed = B.seed;
         P.jscale = B.jscale;
         P.jacc = B.jacc;
+        P.prior = B.prior;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) P.lam[k] = B.lam[k];
     }
     if constexpr (ZBK) {
         const int item = blockIdx.x / P.z_nb, zb = blockIdx.x - item * P.z_nb;
@@ -3077,7 +3169,7 @@ __global__ __launch_bounds__(NS + 64) void k_mh_ws(MHArgs P, uint32_t sweep) {
         mh_ws_table<M>(P, S, I, NT, &tap0);
         mh_ws_gp_store<M, K>(P, S, I, NT, gv);
         __syncthreads();
-        mh_ws_run<NS, UV, false, U, M, false, true, NTV, true, true, MULTI>(P, S, I, sweep, blockIdx.x, &pre, &Z,
+        mh_ws_run<NS, UV, false, U, M, false, true, NTV, true, true, MULTI, PRIOR>(P, S, I, sweep, blockIdx.x, &pre, &Z,
                                                                       item, zb);
         return;
     }
@@ -3117,7 +3209,7 @@ __global__ __launch_bounds__(NS + 64) void k_mh_ws(MHArgs P, uint32_t sweep) {
     __syncthreads();
     D3D_MH_STAMP(blockIdx.x, 1, 0);
     // (U >= 4 or the wide form: the variants of launches that do not fill the chip)
-    mh_ws_run<NS, UV, false, U, M, false, true, NTV, (U >= 4 || NS != 256), false, MULTI>(P, S, I, sweep, blockIdx.x,
+    mh_ws_run<NS, UV, false, U, M, false, true, NTV, (U >= 4 || NS != 256), false, MULTI, PRIOR>(P, S, I, sweep, blockIdx.x,
                                                                            &pre);
 }
 
@@ -4201,7 +4293,7 @@ __device__ __forceinline__ void mh_channel_terms(const MHProposal &q, double EO,
 // depth up to MH_DEEP_MAX: k_mh with every thread looping over its z-pairs tid, tid + 1024,
 // ...  The window sums stay in registers (one position group), the zero-extended unit lines
 // go to LDS, the decision is mh_decide_wave's.  Probe and external-lines modes as k_mh.
-template <bool MULTI = false>
+template <bool MULTI = false, bool PRIOR = false>
 static __global__ __launch_bounds__(1024) void k_mh_deep(MHArgs P, uint32_t sweep) {
     extern __shared__ double smem[];
     constexpr int NT = 1024, ZB = MH_DEEP_ZB;
@@ -4286,7 +4378,7 @@ static __global__ __launch_bounds__(1024) void k_mh_deep(MHArgs P, uint32_t swee
     __syncthreads();
     if (tid < 64) {
         const U2 u_gibbs = philox_pair(P.seed, q.gsp, sweep, BLK_GIBBS);
-        mh_decide_wave(P, S, q, sp, sweep, NT / 64, u_gibbs);
+        mh_decide_wave<PRIOR>(P, S, q, sp, sweep, NT / 64, u_gibbs);
     }
     __syncthreads();
     if (P.probe) return;
@@ -4325,6 +4417,7 @@ static __global__ __launch_bounds__(1024) void k_mh_deep(MHArgs P, uint32_t swee
 // Totals the blocks' wave sums (block by block, wave by wave: a fixed order), takes the decision
 // (mh_decide_wave: accept, Gibbs draw, state), and forms the window's G row from the lines the
 // blocks left in z_E -- the pending layer the next colour's k_mh_ws<..., ZBK> applies.
+template <bool PRIOR = false>
 static __global__ __launch_bounds__(256) void k_mh_zdecide(MHArgs P, uint32_t sweep, int waves_per_block) {
     extern __shared__ double smem[];
     const int tid = threadIdx.x;
@@ -4340,7 +4433,7 @@ static __global__ __launch_bounds__(256) void k_mh_zdecide(MHArgs P, uint32_t sw
     if (tid < 64) {
         const MHProposal q = mh_proposal_of(P, sp, sweep);
         const U2 u_gibbs = philox_pair(P.seed, q.gsp, sweep, BLK_GIBBS);
-        mh_decide_wave(P, S, q, sp, sweep, nw, u_gibbs);
+        mh_decide_wave<PRIOR>(P, S, q, sp, sweep, nw, u_gibbs);
         if (tid == 0) *sq = q;
     }
     __syncthreads();
@@ -4403,6 +4496,64 @@ static __global__ __launch_bounds__(256) void k_mh_adapt(double *jscale, unsigne
     const double s = jscale[sp] * exp(step * (rate - target));
     jscale[sp] = fmin(fmax(s, scale_min), scale_max);
     jacc[sp] = 0u;
+}
+
+// Sums of squared neighbour differences of a parameter map (d3d_prior_energy): E_k = sum_<i,j>
+// (theta_i,k - theta_j,k)^2 over the horizontally and vertically adjacent pairs of unmasked
+// spaxels, k = (a, c, w), and the number of pairs.  Every spaxel takes its right and its lower
+// neighbour; a block walks its cells in a fixed order, its threads' sums meet in a fixed tree,
+// and k_prior_energy_total adds the blocks' partials in a fixed order: no floating-point
+// atomics, so two calls give the same bits.
+constexpr int PRIOR_BLOCKS = 256;  // most blocks of k_prior_energy (a block's share: HW / blocks cells)
+
+__device__ __forceinline__ void prior_block_sum(double (&v)[4], double *out4) {
+    __shared__ double s[4][256];
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k][tid] = v[k];
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s[k][tid] += s[k][tid + off];
+        }
+        __syncthreads();
+    }
+    if (tid < 4) out4[tid] = s[tid][0];
+}
+
+static __global__ __launch_bounds__(256) void k_prior_energy(const double *__restrict__ params,
+                                                             const uint8_t *__restrict__ mask, int H,
+                                                             int W, double *__restrict__ partial) {
+    const long HW = (long)H * W;
+    double v[4] = {0.0, 0.0, 0.0, 0.0};
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < HW; i += (long)gridDim.x * 256) {
+        if (mask[i] != 1) continue;
+        const int y = (int)(i / W), x = (int)(i - (long)y * W);
+        const double a = params[i * 3 + 0], c = params[i * 3 + 1], w = params[i * 3 + 2];
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {  // right, lower
+            const bool in = d == 0 ? (x + 1 < W) : (y + 1 < H);
+            const long j = d == 0 ? i + 1 : i + W;
+            if (!in || mask[j] != 1) continue;
+            const double da = a - params[j * 3 + 0], dc = c - params[j * 3 + 1], dw = w - params[j * 3 + 2];
+            v[0] = fma(da, da, v[0]);
+            v[1] = fma(dc, dc, v[1]);
+            v[2] = fma(dw, dw, v[2]);
+            v[3] += 1.0;
+        }
+    }
+    prior_block_sum(v, partial + (long)blockIdx.x * 4);
+}
+
+static __global__ __launch_bounds__(256) void k_prior_energy_total(const double *__restrict__ partial,
+                                                                   int n_blocks, double *__restrict__ out4) {
+    double v[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int b = threadIdx.x; b < n_blocks; b += 256) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] += partial[(long)b * 4 + k];
+    }
+    prior_block_sum(v, out4);
 }
 
 // Halo exchange of the tiled chain: the cells (all E values per spaxel: E = Dp for

@@ -120,6 +120,23 @@ void fill_mh_args(d3d_ctx *c, d3d::MHArgs &P) {
 #endif
     P.jscale = c->adapt_on ? c->jscale : nullptr;
     P.jacc = c->adapt_on ? c->jacc : nullptr;
+    P.prior = c->prior_on ? 1 : 0;
+    for (int k = 0; k < 3; ++k) P.lam[k] = c->prior_on ? c->prior_lam[k] : 0.0;
+}
+
+int prior_energy(d3d_ctx *c, const double *params_dev, double out4[4]) {
+    const int nb = (int)std::min<long>((c->HW + 255) / 256, d3d::PRIOR_BLOCKS);
+    if (!c->prior_part) HIP_TRY(hipMalloc(&c->prior_part, (size_t)(d3d::PRIOR_BLOCKS + 1) * 4 * sizeof(double)));
+    double *total = c->prior_part + (size_t)d3d::PRIOR_BLOCKS * 4;
+    hipLaunchKernelGGL(d3d::k_prior_energy, dim3((unsigned)nb), dim3(256), 0, c->stream, params_dev,
+                       (const uint8_t *)c->mask, c->H, c->W, c->prior_part);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(d3d::k_prior_energy_total, dim3(1), dim3(256), 0, c->stream,
+                       (const double *)c->prior_part, nb, total);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out4, total, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 int adapt_after_sweep(d3d_ctx *c, int s) {
@@ -144,7 +161,12 @@ int adapt_after_sweep(d3d_ctx *c, int s) {
 // The instantiation of k_mh_ws for the context's line shape: the single Gaussian's kernel for
 // K == 1 (MULTI = false: unchanged code), the multiplet form (unit_line<true>) for K > 1.
 template <int NS, bool UV, int U, int M, int K, int NL, bool NTV = false, bool ZBK = false, bool BATCH = false>
-static auto mh_ws_kernel(bool multi) {
+static auto mh_ws_kernel(bool multi, bool prior) {
+    // (d3d_prior_begin: the instantiations with the smoothness prior's terms -- a template
+    // parameter, so that the others stay the code, registers and occupancy they were)
+    if (prior)
+        return multi ? &d3d::k_mh_ws<NS, UV, U, M, K, NL, NTV, ZBK, BATCH, true, true>
+                     : &d3d::k_mh_ws<NS, UV, U, M, K, NL, NTV, ZBK, BATCH, false, true>;
     return multi ? &d3d::k_mh_ws<NS, UV, U, M, K, NL, NTV, ZBK, BATCH, true>
                  : &d3d::k_mh_ws<NS, UV, U, M, K, NL, NTV, ZBK, BATCH, false>;
 }
@@ -161,8 +183,23 @@ int launch_mh_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep)
     const size_t lds = d3d::mh_lds_doubles(NT, c->HL, c->Dp, c->N, P.npos) * sizeof(double);
     if (c->line.K > 1) {
         if constexpr (MAXIT != 0) return need_single_line(c, "option mh_maxit (register-resident k_mh)");
+        if constexpr (MAXIT == 0) {
+            if (P.prior) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh<NT, 0, true, true>), dim3(grid), dim3(NT), lds,
+                                   c->stream, P, sweep);
+                HIP_TRY(hipGetLastError());
+                return 0;
+            }
+        }
         hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh<NT, MAXIT, true>), dim3(grid), dim3(NT), lds, c->stream,
                            P, sweep);
+    } else if (P.prior) {
+        if constexpr (MAXIT != 0)
+            return fail(D3D_ERR_UNSUPPORTED, "option mh_maxit (register-resident k_mh) has no form with the "
+                        "smoothness prior (d3d_prior_begin)");
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh<NT, 0, false, true>), dim3(grid), dim3(NT), lds,
+                               c->stream, P, sweep);
     } else {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh<NT, MAXIT>), dim3(grid), dim3(NT), lds, c->stream,
                            P, sweep);
@@ -189,7 +226,8 @@ int launch_mh_nt(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep
 int launch_mh(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep) {
     if (c->deep) {  // more than 1024 channels: threads loop over their z-pairs
         const size_t lds = d3d::mh_deep_lds_doubles(c->N, P.npos) * sizeof(double);
-        auto kern = c->line.K > 1 ? &d3d::k_mh_deep<true> : &d3d::k_mh_deep<false>;
+        auto kern = P.prior ? (c->line.K > 1 ? &d3d::k_mh_deep<true, true> : &d3d::k_mh_deep<false, true>)
+                            : (c->line.K > 1 ? &d3d::k_mh_deep<true> : &d3d::k_mh_deep<false>);
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), lds, c->stream, P, sweep);
@@ -207,12 +245,9 @@ int launch_mh(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep) {
 template <int NT>
 int launch_mh_defer_nt(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep) {
     const size_t lds = d3d::mh_lds_doubles(NT, c->HL, c->Dp, c->N, P.npos) * sizeof(double);
-    if (c->line.K > 1)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh_defer<NT, true>), dim3(grid), dim3(NT), lds, c->stream,
-                           P, sweep);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh_defer<NT>), dim3(grid), dim3(NT), lds, c->stream,
-                           P, sweep);
+    auto kern = P.prior ? (c->line.K > 1 ? &d3d::k_mh_defer<NT, true, true> : &d3d::k_mh_defer<NT, false, true>)
+                        : (c->line.K > 1 ? &d3d::k_mh_defer<NT, true> : &d3d::k_mh_defer<NT, false>);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, c->stream, P, sweep);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -234,13 +269,13 @@ int launch_mh_ws_um(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sw
     };
     // (the number of pending layers as a template constant: see k_mh_ws)
     switch (P.n_lay <= M ? P.n_lay : -1) {
-        case 0: go(mh_ws_kernel<NS, UV, U, M, K, 0, NTV>(P.line.K > 1)); break;
-        case 1: go(mh_ws_kernel<NS, UV, U, M, K, 1, NTV>(P.line.K > 1)); break;
+        case 0: go(mh_ws_kernel<NS, UV, U, M, K, 0, NTV>(P.line.K > 1, P.prior != 0)); break;
+        case 1: go(mh_ws_kernel<NS, UV, U, M, K, 1, NTV>(P.line.K > 1, P.prior != 0)); break;
         case 2:
-            if constexpr (M >= 2) go(mh_ws_kernel<NS, UV, U, M, K, 2, NTV>(P.line.K > 1));
+            if constexpr (M >= 2) go(mh_ws_kernel<NS, UV, U, M, K, 2, NTV>(P.line.K > 1, P.prior != 0));
             break;
         case 3:
-            if constexpr (M >= 3) go(mh_ws_kernel<NS, UV, U, M, K, 3, NTV>(P.line.K > 1));
+            if constexpr (M >= 3) go(mh_ws_kernel<NS, UV, U, M, K, 3, NTV>(P.line.K > 1, P.prior != 0));
             break;
         default:
             return fail(D3D_ERR_STATE, "internal: %d pending layers for a %d-layer kernel", P.n_lay, M);
@@ -323,8 +358,12 @@ static int ensure_ptab(d3d_ctx *c) {
 template <bool UV, int NS, int U, int K, int M = 1, bool FULL = false, bool NTV = false>
 int launch_mh_small_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep) {
     const size_t lds = d3d::mh_small_lds_doubles(NS, c->HL, c->Dp, P.npos, M) * sizeof(double);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh_small<NS, UV, U, K, false, M, FULL, NTV>), dim3(grid), dim3(NS),
-                       lds, c->stream, P, sweep);
+    if (P.prior)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh_small<NS, UV, U, K, false, M, FULL, NTV, true>), dim3(grid),
+                           dim3(NS), lds, c->stream, P, sweep);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh_small<NS, UV, U, K, false, M, FULL, NTV>), dim3(grid), dim3(NS),
+                           lds, c->stream, P, sweep);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -574,6 +613,7 @@ int launch_mh_zb_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned n_items, uint32_t 
     const int db = P.z_db;
     const unsigned grid = n_items * (unsigned)P.z_nb;
     const bool few = grid < (unsigned)c->flow_grid / 2;
+    // (the blocks' kernel takes no decision: the prior is k_mh_zdecide's alone)
     auto go = [&](auto kern, int M) {
         // (LDS of the 256-channel kernel: 35-40 KB, four workgroups per CU)
         const size_t lds =
@@ -586,28 +626,29 @@ int launch_mh_zb_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned n_items, uint32_t 
     const int nl = P.n_lay;
     if (layers >= 2) {
         if (few) {
-            if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 2, 4, 0, false, true>(P.line.K > 1), 2);
-            else if (nl == 1) go(mh_ws_kernel<NS, UV, 4, 2, 4, 1, false, true>(P.line.K > 1), 2);
-            else go(mh_ws_kernel<NS, UV, 4, 2, 4, 2, false, true>(P.line.K > 1), 2);
+            if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 2, 4, 0, false, true>(P.line.K > 1, false), 2);
+            else if (nl == 1) go(mh_ws_kernel<NS, UV, 4, 2, 4, 1, false, true>(P.line.K > 1, false), 2);
+            else go(mh_ws_kernel<NS, UV, 4, 2, 4, 2, false, true>(P.line.K > 1, false), 2);
         } else if (ntv) {
             if constexpr (!UV) {
-                if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 4, 0, true, true>(P.line.K > 1), 2);
-                else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 4, 1, true, true>(P.line.K > 1), 2);
-                else go(mh_ws_kernel<NS, UV, 2, 2, 4, 2, true, true>(P.line.K > 1), 2);
+                if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 4, 0, true, true>(P.line.K > 1, false), 2);
+                else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 4, 1, true, true>(P.line.K > 1, false), 2);
+                else go(mh_ws_kernel<NS, UV, 2, 2, 4, 2, true, true>(P.line.K > 1, false), 2);
             }
         } else {
-            if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 4, 0, false, true>(P.line.K > 1), 2);
-            else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 4, 1, false, true>(P.line.K > 1), 2);
-            else go(mh_ws_kernel<NS, UV, 2, 2, 4, 2, false, true>(P.line.K > 1), 2);
+            if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 4, 0, false, true>(P.line.K > 1, false), 2);
+            else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 4, 1, false, true>(P.line.K > 1, false), 2);
+            else go(mh_ws_kernel<NS, UV, 2, 2, 4, 2, false, true>(P.line.K > 1, false), 2);
         }
     } else {
-        if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 1, 4, 0, false, true>(P.line.K > 1), 1);
-        else go(mh_ws_kernel<NS, UV, 4, 1, 4, 1, false, true>(P.line.K > 1), 1);
+        if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 1, 4, 0, false, true>(P.line.K > 1, false), 1);
+        else go(mh_ws_kernel<NS, UV, 4, 1, 4, 1, false, true>(P.line.K > 1, false), 1);
     }
     HIP_TRY(hipGetLastError());
     const int nw = P.z_nb * (NS / 64);
     const size_t lds2 = ((size_t)8 * nw + 8 + 16) * sizeof(double);
-    hipLaunchKernelGGL(d3d::k_mh_zdecide, dim3(n_items), dim3(256), lds2, c->stream, P, sweep, NS / 64);
+    hipLaunchKernelGGL(P.prior ? &d3d::k_mh_zdecide<true> : &d3d::k_mh_zdecide<false>, dim3(n_items), dim3(256), lds2,
+                       c->stream, P, sweep, NS / 64);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -642,7 +683,11 @@ int launch_mh_batch_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t 
     if (P.ltab && layers == 1) {  // the joint launch does not fill the chip either: k_mh_small
         const size_t lds = d3d::mh_small_lds_doubles(NS, c->HL, c->Dp, P.npos, 1) * sizeof(double);
         auto go_small = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(NS), lds, c->stream, P, sweep); };
-        if (c->Dp <= 64) go_small(d3d::k_mh_small<NS, UV, 8, 1, true>);
+        if (P.prior) {
+            if (c->Dp <= 64) go_small(d3d::k_mh_small<NS, UV, 8, 1, true, 1, false, false, true>);
+            else if (c->Dp <= 128) go_small(d3d::k_mh_small<NS, UV, 8, 2, true, 1, false, false, true>);
+            else go_small(d3d::k_mh_small<NS, UV, 8, 4, true, 1, false, false, true>);
+        } else if (c->Dp <= 64) go_small(d3d::k_mh_small<NS, UV, 8, 1, true>);
         else if (c->Dp <= 128) go_small(d3d::k_mh_small<NS, UV, 8, 2, true>);
         else go_small(d3d::k_mh_small<NS, UV, 8, 4, true>);
         HIP_TRY(hipGetLastError());
@@ -655,17 +700,17 @@ int launch_mh_batch_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t 
     const int nl = P.n_lay;
     if (layers >= 2) {  // Dp <= 160: the staged G rows in two registers
         if (few) {
-            if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 2, 2, 0, false, false, true>(P.line.K > 1), 2);
-            else if (nl == 1) go(mh_ws_kernel<NS, UV, 4, 2, 2, 1, false, false, true>(P.line.K > 1), 2);
-            else go(mh_ws_kernel<NS, UV, 4, 2, 2, 2, false, false, true>(P.line.K > 1), 2);
+            if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 2, 2, 0, false, false, true>(P.line.K > 1, P.prior != 0), 2);
+            else if (nl == 1) go(mh_ws_kernel<NS, UV, 4, 2, 2, 1, false, false, true>(P.line.K > 1, P.prior != 0), 2);
+            else go(mh_ws_kernel<NS, UV, 4, 2, 2, 2, false, false, true>(P.line.K > 1, P.prior != 0), 2);
         } else {
-            if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 2, 0, false, false, true>(P.line.K > 1), 2);
-            else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 2, 1, false, false, true>(P.line.K > 1), 2);
-            else go(mh_ws_kernel<NS, UV, 2, 2, 2, 2, false, false, true>(P.line.K > 1), 2);
+            if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 2, 0, false, false, true>(P.line.K > 1, P.prior != 0), 2);
+            else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 2, 1, false, false, true>(P.line.K > 1, P.prior != 0), 2);
+            else go(mh_ws_kernel<NS, UV, 2, 2, 2, 2, false, false, true>(P.line.K > 1, P.prior != 0), 2);
         }
     } else {
-        if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 1, 4, 0, false, false, true>(P.line.K > 1), 1);
-        else go(mh_ws_kernel<NS, UV, 4, 1, 4, 1, false, false, true>(P.line.K > 1), 1);
+        if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 1, 4, 0, false, false, true>(P.line.K > 1, P.prior != 0), 1);
+        else go(mh_ws_kernel<NS, UV, 4, 1, 4, 1, false, false, true>(P.line.K > 1, P.prior != 0), 1);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -726,6 +771,8 @@ int mh_sweeps_batch(d3d_ctx **cs, int R, int n_sweeps, int first_sweep, int64_t 
             B.ltab = nullptr;
             B.jscale = c->adapt_on ? c->jscale : nullptr;
             B.jacc = c->adapt_on ? c->jacc : nullptr;
+            B.prior = c->prior_on ? 1 : 0;
+            for (int k = 0; k < 3; ++k) B.lam[k] = c->prior_on ? c->prior_lam[k] : 0.0;
             if (small) {
                 if (!c->props && hipMalloc(&c->props, (size_t)c->HW * sizeof(d3d::MHProposal)) != hipSuccess) rc = fail(D3D_ERR_HIP, "hipMalloc");
                 if (!rc && !c->ltab && hipMalloc(&c->ltab, (size_t)c->HW * 2 * c->Dp * sizeof(double)) != hipSuccess) rc = fail(D3D_ERR_HIP, "hipMalloc");

@@ -90,7 +90,8 @@ __host__ __device__ inline size_t mh_small_lds_doubles(int NS, int HL, int Dp, i
 // window passes there (measured in k_mh_ws: +0.8 us per launch) -- and few positions in flight.
 // NTV (FULL only): the cache policy of a context beyond the Infinity Cache (k_mh_ws: 1/variance
 // loaded non-temporally, the residual stored write-through through a raw buffer of the window).
-template <int NS, bool UV, int U, int K, bool BATCH = false, int M = 1, bool FULL = false, bool NTV = false>
+template <int NS, bool UV, int U, int K, bool BATCH = false, int M = 1, bool FULL = false, bool NTV = false,
+          bool PRIOR = false>
 __global__ __launch_bounds__(NS) void k_mh_small(MHArgs P, uint32_t sweep) {
     static_assert(M == 1 || M == 2, "one or two pending layers");
     extern __shared__ double smem[];
@@ -162,6 +163,9 @@ __global__ __launch_bounds__(NS) void k_mh_small(MHArgs P, uint32_t sweep) {
         P.ltab = B.ltab;
         P.jscale = B.jscale;
         P.jacc = B.jacc;
+        P.prior = B.prior;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) P.lam[k] = B.lam[k];
     }
     // (measured and dropped: the window centre from the block index -- the grid as the launch's
     // lattice, no work-list entry to wait for: 10.87 against 10.89 us per launch at 64^3, 12.22
@@ -388,6 +392,8 @@ __global__ __launch_bounds__(NS) void k_mh_small(MHArgs P, uint32_t sweep) {
     if (wave >= nwc) return;  // (a wavefront that has ended no longer counts at a barrier)
     double sums[7], tot[7];
     mh_channel_sums_regs(P, s_red, q, tid, G, EO, EN, sums);
+    // (d3d_prior_begin: mh_decide_core loads the neighbours' parameters itself here -- held in
+    // registers from before the window pass they cost this kernel scratch)
     bool accept;
     double r;
     if constexpr (FULL) {
@@ -406,7 +412,7 @@ __global__ __launch_bounds__(NS) void k_mh_small(MHArgs P, uint32_t sweep) {
                 tot[k] = t;
             }
             D3D_MH_STAMP(blockIdx.x, 6, 0);
-            mh_decide_core(P, q, sp, sweep, tot, u_gibbs, tid == 0, &accept, &r);
+            mh_decide_core<PRIOR>(P, q, sp, sweep, tot, u_gibbs, tid == 0, &accept, &r);
             if (tid == 0) {
                 verdict[0] = accept ? 1.0 : 0.0;
                 verdict[1] = r;
@@ -434,7 +440,7 @@ __global__ __launch_bounds__(NS) void k_mh_small(MHArgs P, uint32_t sweep) {
             }
         }
         D3D_MH_STAMP(blockIdx.x, 6, 0);
-        mh_decide_core(P, q, sp, sweep, tot, u_gibbs, tid == 0, &accept, &r);
+        mh_decide_core<PRIOR>(P, q, sp, sweep, tot, u_gibbs, tid == 0, &accept, &r);
         D3D_MH_STAMP(blockIdx.x, 7, 0);
     }
     if (tid < Dp)

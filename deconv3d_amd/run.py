@@ -35,7 +35,8 @@ from os.path import splitext
 
 import numpy as np
 
-from . import _lib, adapt as _adapt, posterior as _posterior, prepare as _prepare, search as _search
+from . import _lib, adapt as _adapt, posterior as _posterior, prepare as _prepare, prior as _prior, \
+    search as _search
 from .cube import Cube, read_fits
 from .instruments import Instrument
 from .line_models import (LineModel, SingleGaussianLineModel, SINGLE_LINE_SHAPE,
@@ -116,6 +117,18 @@ class Run:
     written with other ``adapt_*`` keywords is refused).  A host-evaluated line model raises
     ``NotImplementedError``.
 
+    ``smoothness=`` (default ``None``: off, nothing allocated or launched, the chain is bit for bit
+    what it is without the keyword) adds a pairwise Gaussian prior between 4-neighbours to the
+    reference's flat one (lib/run.py:426-438, 491-496), ``-1/2 sum_<i,j> sum_k (theta_i,k -
+    theta_j,k)^2 / sigma_k^2`` over the adjacent pairs of unmasked spaxels: a dict with any of
+    ``a``, ``c``, ``w``, or a 3-sequence, of sigmas -- the expected difference between neighbouring
+    spaxels in the parameter's own unit; ``None`` or ``inf``: none.  ``run.smoothness`` holds the
+    three sigmas, ``run.roughness(parameters=None)`` the sums of squared neighbour differences
+    ``(E_a, E_c, E_w, pairs)`` of a map.  With ``chains=R`` every chain has the same prior and its
+    own parameters.  The checkpoint records the sigmas; ``resume_state=`` refuses a state written
+    with others.  A host-evaluated line model raises ``NotImplementedError``, an FSF one spaxel
+    wide ``ValueError`` (adjacent spaxels would share a colour class of the sweep).
+
     ``initial_search=True`` (or a dict of :func:`deconv3d_amd.search.line_search` keywords
     ``centres`` / ``widths`` plus ``jitter``; default ``None``: off, nothing allocated or launched,
     the chain is bit for bit what it is without the keyword) starts the chain from a matched-filter
@@ -169,6 +182,7 @@ class Run:
         adapt_scale_range=(1e-3, 1e3),
         initial_search=None,
         prepare=None,
+        smoothness=None,
     ):
         # (before anything else: no device work yet)
         prepare_cfg = _prepare.check_keywords(prepare)
@@ -185,6 +199,7 @@ class Run:
                                  "chain that is still adapting are not posterior moments"
                                  % (posterior_burn_in, adapt_cfg[0]))
         self._adapt_cfg = adapt_cfg
+        self.smoothness = _prior.check_keywords(smoothness)
         # lib/run.py:112-114
         assert keep_one_in > 0, "keep_one_in= MUST be a positive integer"
         assert write_every > 0, "write_every= MUST be a positive integer"
@@ -293,6 +308,12 @@ class Run:
             raise NotImplementedError(
                 "posterior_burn_in=: the line model %s is evaluated on the host; the device "
                 "accumulates posterior moments only for the models it evaluates itself"
+                % type(self.model).__name__)
+        _prior.check_fsf(self.smoothness, self.fsf.shape)
+        if self.smoothness is not None and self._host_model:
+            raise NotImplementedError(
+                "smoothness=: the line model %s is evaluated on the host; the device knows the "
+                "prior only for the (a, c, w) of the models it evaluates itself"
                 % type(self.model).__name__)
         if adapt_cfg is not None and self._host_model:
             raise NotImplementedError(
@@ -406,6 +427,7 @@ class Run:
             self.sweep_origin = int(state["sweep_origin"]) + int(state["iteration"]) - 1
             resumed_adapt = _adapt.check_resume(state, files, adapt_cfg, n_chains,
                                                 (cube_height, cube_width))
+            _prior.check_resume(state, files, self.smoothness)
             _prepare.check_resume(state, files,
                                   None if self.prepared is None else self.prepared.settings)
             # totals over every earlier segment (older checkpoints hold one segment's)
@@ -476,6 +498,8 @@ class Run:
                     eng.adapt_begin(adapt_cfg[2], adapt_cfg[1], adapt_cfg[0], adapt_cfg[3], adapt_cfg[4])
                     if resumed_adapt is not None:
                         eng.adapt_set(*resumed_adapt[r])
+                if self.smoothness is not None:
+                    eng.prior_begin(_prior.lam_of(self.smoothness))
         if resume_state is not None:
             if host_chain is None:
                 for eng in self.engines:
@@ -612,6 +636,19 @@ class Run:
         accept, Gibbs draw and residual, but python-speed proposals and modelize() calls."""
         return model_is_on_device(self.model)
 
+    def roughness(self, parameters=None):
+        """``(E_a, E_c, E_w, pairs)``: the sums of squared differences between horizontally and
+        vertically adjacent unmasked spaxels of an (H, W, 3) parameter map, and the number of such
+        pairs -- what ``smoothness=`` penalises, summed on the device (d3d_prior_energy).
+        ``parameters=None``: ``run.parameters``, the extracted map."""
+        if self._host_model:
+            raise NotImplementedError("roughness(): the line model %s is evaluated on the host"
+                                      % type(self.model).__name__)
+        if parameters is None:
+            parameters = self.parameters
+        parameters = np.asarray(getattr(parameters, "data", parameters), dtype=np.float64)
+        return self.engine.prior_energy(parameters)
+
     def _sweep_chains(self, n, first, all_likelihoods):
         """n sweeps of every chain: ONE launch per colour class for all of them where the
         library can (d3d_mh_sweeps_batch: cubes up to 256 channels -- a small cube's launch
@@ -675,6 +712,8 @@ class Run:
             state["line_ratios"] = np.array(self.line_shape[1], dtype=np.float64)
         if self.prepared is not None:       # (resume_state= checks them)
             state["prepare_settings"] = _prepare.settings_record(self.prepared.settings)
+        if self.smoothness is not None:     # (resume_state= checks them)
+            state["smoothness_sigmas"] = _prior.keyword_record(self.smoothness)
         if self._adapt_cfg is not None:     # (resume_state= checks the keywords, restores the rest)
             got = [eng.adapt_get() for eng in self.engines]
             state["adapt_keywords"] = _adapt.keyword_record(self._adapt_cfg)

@@ -378,6 +378,48 @@ int d3d_adapt_set(d3d_ctx *ctx, const double *scale_hw, const uint32_t *accepted
  * (d3d_ctx_destroy does it too). */
 int d3d_adapt_end(d3d_ctx *ctx);
 
+/* ---- smoothness prior between neighbouring spaxels ------------------------ */
+/* The reference samples a flat prior inside the bounds, every spaxel on its own: its MH ratio is
+ * the likelihood's alone (lib/run.py:426-438) and its Gibbs draw sees only the prior variance ra
+ * (lib/run.py:491-496).  Where the FSF is wider than a spaxel, neighbours trade flux and the
+ * parameter maps are noise.  These entries add a pairwise Gaussian prior between 4-neighbours,
+ *     log p(theta) = -1/2 sum_<i,j> sum_k lam[k] (theta_i,k - theta_j,k)^2,   k = (a, c, w),
+ * over the horizontally and vertically adjacent pairs of unmasked spaxels (mask == 1).  Off until
+ * begun: a ctx that never calls d3d_prior_begin runs the chain it always ran, bit for bit. */
+
+/* Turn the prior on with lam[k] = 1 / sigma_k^2 >= 0 (0: none on that parameter).  With N(i) the
+ * unmasked 4-neighbours of spaxel i inside the cube, as they are when i is decided, every update of
+ * every device kernel then compares (lib/run.py:426-438)
+ *     delta = (ar_old - ar_new)
+ *             - 1/2 sum_{j in N(i)} sum_{k in (c,w)} lam[k] (p_new,k - p_old,k)(p_new,k + p_old,k - 2 theta_j,k)
+ * with log(u) -- d3d_get_dlog and the dlog of d3d_mh_sweeps hold this total -- and draws the
+ * amplitude (lib/run.py:491-496) from
+ *     s_ee' = s_ee + lam[0] |N(i)|,  s_eu' = s_eu + lam[0] sum_{j in N(i)} a_j,
+ *     ro = ra / (1 + ra s_ee'),  mu = ro s_eu',  r ~ TN(min_a, max_a; mu, sqrt(ro)).
+ * Random numbers and the residual update are unchanged; all lam = 0 is the chain without the
+ * prior, bit for bit.  Two spaxels of one colour class are fh rows or fw columns apart, so no
+ * neighbour moves in the launch that decides i: exact for every fh, fw >= 2.  Calling it again
+ * replaces lam.
+ * D3D_ERR_INVALID: a lam that is negative or not finite; fh == 1 or fw == 1 (adjacent spaxels
+ * would share a colour class).  D3D_ERR_UNSUPPORTED: a tile ctx (d3d_set_tile), a ctx cut into
+ * more than one part (d3d_set_parts), or -- EXPERIMENTS builds -- option mh_chain, mh_flow or
+ * mh_pair, whose kernels decide more than one colour class in a launch; each of these, and
+ * d3d_mh_colour_lines, is refused alike while the prior is on.  The ctxs of one
+ * d3d_mh_sweeps_batch call must all have the prior on or all off (D3D_ERR_INVALID; their lam may
+ * differ).  d3d_window_stats keeps returning
+ * the likelihood terms only. */
+int d3d_prior_begin(d3d_ctx *ctx, const double lam[3]);
+/* lam as begun (zeros when off) and whether the prior is on: what the MH ratio of
+ * lib/run.py:426-438 is extended by. */
+int d3d_prior_get(d3d_ctx *ctx, double lam[3], int *on);
+/* Turn it off: the ctx samples the flat prior of lib/run.py:426-438, 491-496 again. */
+int d3d_prior_end(d3d_ctx *ctx);
+/* E_k = sum_<i,j> (theta_i,k - theta_j,k)^2 over the pairs above for k = (a, c, w), and their
+ * number: -2 log p = sum_k lam[k] E_k, the term the ratio of lib/run.py:426-438 is extended by.
+ * params: an (H,W,3) map on the host, or NULL for the ctx's current parameters.  Summed on the
+ * device in fp64 in a fixed order: two calls return the same bits.  Works with the prior off. */
+int d3d_prior_energy(d3d_ctx *ctx, const double *params, double energy[3], int64_t *pairs);
+
 /* ---- spatial tiling (one chain over several GPUs) --------- */
 /* The reference has no counterpart (single process).  What makes tiling possible is
  * that an update at (y,x) touches only its FSF window (lib/run.py:404-419), and that
