@@ -457,8 +457,9 @@ int post_reset(d3d_ctx *c) {
     return 0;
 }
 
-// the chain state as one more sample
-int post_sample(d3d_ctx *c) {
+}  // namespace
+
+int d3dh::post_sample(d3d_ctx *c) {
     NEED(c->post_on, D3D_ERR_STATE, "posterior moments not begun (d3d_post_begin)");
     NEED(!c->tiled, D3D_ERR_UNSUPPORTED,
          "posterior moments on a tile: the parameters of its frame belong to other ranks");
@@ -472,12 +473,12 @@ int post_sample(d3d_ctx *c) {
     return 0;
 }
 
-// sweep s (the caller's numbering) is one d3d_post_schedule asked for
-bool post_due(const d3d_ctx *c, int s) {
+bool d3dh::post_due(const d3d_ctx *c, int s) {
     return c->post_on && c->post_every > 0 && s >= c->post_first &&
            (s - c->post_first) % c->post_every == 0;
 }
 
+namespace {
 
 // ---- per-context options (d3d_ctx_set_option) -----------------------------------------
 // Every switch of the library is a field of the context.  The environment is only the
@@ -1401,408 +1402,6 @@ int d3d_window_stats(d3d_ctx *c, int y, int x, const double p_new[3], double out
     return D3D_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
-// ---- asynchronous chain streaming ------------------------------------------------
-struct SnapQueue {
-    int slot[d3d_ctx::STREAM_NB];  // chain slot each in-flight buffer belongs to
-    int head = 0, count = 0;       // ring of in-flight buffers, oldest first
-};
-
-int snap_setup(d3d_ctx *c) {
-    if (c->copy_stream) return 0;
-    HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    const size_t bytes = (size_t)c->HW * 4 * sizeof(double);
-    for (int b = 0; b < d3d_ctx::STREAM_NB; ++b) {
-        HIP_TRY(hipMalloc(&c->snap_dev[b], bytes));
-        HIP_TRY(hipHostMalloc((void **)&c->snap_host[b], bytes, hipHostMallocDefault));
-        HIP_TRY(hipEventCreateWithFlags(&c->snap_ready[b], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&c->snap_done[b], hipEventDisableTiming));
-    }
-    return 0;
-}
-
-// The oldest snapshot in flight: wait for its copy, hand it to the caller's arrays.
-int snap_drain_one(d3d_ctx *c, SnapQueue &q, double *chain_out, double *dlog_out) {
-    const int b = q.head;
-    HIP_TRY(hipEventSynchronize(c->snap_done[b]));
-    const size_t slot = (size_t)q.slot[b];
-    if (chain_out)
-        memcpy(chain_out + slot * c->HW * 3, c->snap_host[b], (size_t)c->HW * 3 * sizeof(double));
-    if (dlog_out)
-        memcpy(dlog_out + slot * c->HW, c->snap_host[b] + (size_t)c->HW * 3,
-               (size_t)c->HW * sizeof(double));
-    q.head = (q.head + 1) % d3d_ctx::STREAM_NB;
-    --q.count;
-    return 0;
-}
-
-// Snapshot the current parameters / log ratios for chain slot `slot`.
-int snap_push(d3d_ctx *c, SnapQueue &q, int slot, double *chain_out, double *dlog_out) {
-    if (q.count == d3d_ctx::STREAM_NB)
-        if (int rc = snap_drain_one(c, q, chain_out, dlog_out)) return rc;
-    const int b = (q.head + q.count) % d3d_ctx::STREAM_NB;
-    HIP_TRY(hipMemcpyAsync(c->snap_dev[b], c->params, (size_t)c->HW * 3 * sizeof(double),
-                           hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->snap_dev[b] + (size_t)c->HW * 3, c->dlog, (size_t)c->HW * sizeof(double),
-                           hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipEventRecord(c->snap_ready[b], c->stream));
-    HIP_TRY(hipStreamWaitEvent(c->copy_stream, c->snap_ready[b], 0));
-    HIP_TRY(hipMemcpyAsync(c->snap_host[b], c->snap_dev[b], (size_t)c->HW * 4 * sizeof(double),
-                           hipMemcpyDeviceToHost, c->copy_stream));
-    HIP_TRY(hipEventRecord(c->snap_done[b], c->copy_stream));
-    q.slot[b] = slot;
-    ++q.count;
-    return 0;
-}
-
-// Every colour class of one part, for one sweep (lib/run.py:367-519 restricted to
-// the part, in colour order).
-int run_part(d3d_ctx *c, int pi, uint32_t sweep) {
-    d3d_ctx::Part &pt = c->parts[pi];
-    const int ncol = c->fh * c->fw;
-    // deferred write-back with pending layers: the wave-specialised kernel (D <= 256);
-    // an unpartitioned context may also use the plain deferred kernel
-    const bool partitioned = c->tiled || c->parts.size() > 1;
-    const bool deferred =
-        c->mh_defer &&
-        (!partitioned || (c->mh_defer == 1 && (c->Dp <= d3d::MH_WS_MAX_DP || c->mh_zb)));
-    // (more layers pending than this part's kernels take: a batched launch that filled the chip
-    // left two, the context alone keeps one)
-    if (c->lay_n && (c->pend_part != pi || !deferred || c->lay_n > pt.layers))
-        if (int rc = flush_pending(c)) return rc;
-#ifdef D3D_EXPERIMENTS
-    if (deferred && pt.chain) return launch_mh_chain(c, pi, sweep, 1);  // all colours in one launch
-#endif
-    // two colour classes per launch (k_mh_pair) where the N/W alternation of two pending
-    // layers allows it: an unpartitioned context, a launch that fills the chip
-    const bool pairs = deferred && c->mh_pair && !partitioned && c->mh_defer == 1 && c->Dp <= 256 &&
-                       pt.layers == 2 && c->flow_K > 1 && !c->flow_first.empty();
-    int ord = 0;  // ordinal of `col` among the active colours
-    for (int col = 0; col < ncol; ++col) {
-        const int n_real = pt.real[col];
-        if (n_real <= 0) continue;
-        const int ka = ord++;
-        if (deferred) c->pend_part = pi;  // fill_mh_args takes the domain from it
-#ifdef D3D_EXPERIMENTS
-        if (pairs && c->lay_n == 1 && ka + 1 < c->flow_K) {
-            if (c->stampbuf) goto single;  // phase stamps are per colour launch
-            int rc = launch_mh_pair(c, ka, sweep);
-            if (rc) return rc;
-            // skip colour B in this loop
-            ++col;
-            while (col < ncol && pt.real[col] <= 0) ++col;
-            ++ord;
-            continue;
-        }
-    single:
-#else
-        (void)pairs;
-#endif
-        // small colour launches: the sweep's proposals come from one launch before them
-        // (and the z-blocked kernels: every block's prepare wavefront and k_mh_zdecide need it;
-        // and every part that runs k_mh_small)
-        const bool tables = deferred && c->mh_defer == 1 && !c->mh_zb && d3dh::mh_part_uses_tables(c, pt);
-        const bool use_props =
-            c->mh_props && deferred && (c->mh_zb || (pt.layers == 1 && !c->deep) || tables);
-        if (use_props)
-            if (int rc = ensure_proposals(c, sweep)) return rc;
-        d3d::MHArgs P;
-        fill_mh_args(c, P);
-        P.spx = c->spx + pt.off[col];
-        P.rev = (c->mh_zigzag && (ka & 1)) ? 1 : 0;
-        if (use_props) P.props = c->props;
-        // (k_mh_small reads the sweep's line table, built with the proposals)
-        if (use_props && tables) {
-            P.ltab = c->ltab;
-            P.ptab = c->ptab;
-            const int ly = ((col / c->fw - c->gy0) % c->fh + c->fh) % c->fh;
-            const int lx = ((col % c->fw - c->gx0) % c->fw + c->fw) % c->fw;
-            for (int j = 0; j < 2; ++j) P.ptab_row[j] = d3dh::mh_ptab_row(c, ly, lx, j);
-        }
-        if (deferred) {
-            // real + virtual positions: the windows of this launch tile the domain
-            const int n_all = pt.off[col + 1] - pt.off[col];
-#ifdef D3D_EXPERIMENTS
-            if (c->stampbuf && c->stamp_next < c->stamp_launches &&
-                (size_t)n_all * 8 <= c->stamp_stride)
-                P.stamp = c->stampbuf + (c->stamp_next++) * c->stamp_stride;
-#endif
-            // the launch that finds `layers` layers pending applies them for good
-            P.write_back = (c->lay_n >= pt.layers) ? 1 : 0;
-            const int g_cur = pend_free_buf(c);
-            int rc = c->mh_zb ? launch_mh_zb(c, P, (unsigned)n_all, sweep, pt.layers)
-                              : launch_mh_defer(c, P, (unsigned)n_all, sweep, pt.layers, pt.wide);
-            if (rc) return rc;
-            if (P.write_back) c->lay_n = 0;
-            // this launch's updates are the newest pending layer (local residues)
-            pend_push(c, ((col / c->fw - c->gy0) % c->fh + c->fh) % c->fh,
-                      ((col % c->fw - c->gx0) % c->fw + c->fw) % c->fw, g_cur);
-            c->pend_part = pi;
-        } else {
-            int rc = launch_mh(c, P, (unsigned)n_real, sweep);
-            if (rc) return rc;
-        }
-    }
-    return 0;
-}
-
-int run_phase(d3d_ctx *c, int phase, uint32_t sweep) {
-    for (size_t pi = 0; pi < c->parts.size(); ++pi)
-        if (c->parts[pi].phase == phase)
-            if (int rc = run_part(c, (int)pi, sweep)) return rc;
-    return 0;
-}
-
-int halo_exchange(d3d_ctx *c, int plan);
-// option halo_timing: the oldest event pair in flight, reduced into halo_ms / halo_count
-int halo_drain_one(d3d_ctx *c) {
-    const size_t at = c->halo_ev_head;
-    float f = 0.f;
-    HIP_TRY(hipEventSynchronize(c->halo_ev[2 * at + 1]));
-    HIP_TRY(hipEventElapsedTime(&f, c->halo_ev[2 * at], c->halo_ev[2 * at + 1]));
-    c->halo_ms += (double)f;
-    ++c->halo_count;
-    c->halo_ev_head = (at + 1) % d3d_ctx::HALO_RING;
-    --c->halo_ev_used;
-    return 0;
-}
-bool plan_has_entries(const d3d_ctx *c, int plan) {
-    return plan >= 0 && plan < (int)c->plans.size() && !c->plans[plan].empty();
-}
-
-}  // namespace
-
-extern "C" {
-
-int d3d_mh_sweeps(d3d_ctx *c, int n_sweeps, int first_sweep, int keep_one_in, double *chain_out,
-                  double *dlog_out, int64_t *accepted) {
-    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
-    NEED(c->have_taps && c->have_data && c->have_params && c->have_cfg, D3D_ERR_STATE,
-         "taps/data/parameters/mh_config not set");
-    NEED(n_sweeps >= 0 && first_sweep >= 0, D3D_ERR_INVALID, "negative sweep count/index");
-    NEED(keep_one_in > 0, D3D_ERR_INVALID, "keep_one_in= MUST be a positive integer");
-    // a tile whose neighbours' updates reach it needs the halo exchange between the phases
-    // phases of a sweep: this tile's own, and those after which a neighbour sends to it
-    bool any_plan = false;
-    int n_phases = c->n_phases;
-    for (int ph = 0; ph < D3D_PLAN_PARAMS; ++ph)
-        if (plan_has_entries(c, ph)) {
-            any_plan = true;
-            n_phases = std::max(n_phases, ph + 1);
-        }
-    NEED(!any_plan || c->comm, D3D_ERR_STATE,
-         "this tile has halo plans: call d3d_comm_init, or drive the phases with d3d_mh_phase "
-         "and exchange the halos yourself");
-    HIP_TRY(hipSetDevice(c->device));
-    if (!c->err_valid) {
-        int rc = d3d_residual(c, nullptr);
-        if (rc) return rc;
-    }
-    HIP_TRY(hipMemsetAsync(c->accepted, 0, sizeof(unsigned long long), c->stream));
-    c->props_sweep = -1;  // a proposal table never outlives the call it was made in
-    c->halo_ev_used = 0;  // (pairs a failed call left behind are dropped)
-    c->halo_ev_head = 0;
-    SnapQueue snaps;
-    if (chain_out || dlog_out)
-        if (int rc = snap_setup(c)) return rc;
-    // k_mh_flow addresses SLOT_ERR through a raw buffer (32-bit byte offsets)
-    const bool flow = c->mh_flow && c->mh_defer == 1 && !c->tiled && c->parts.size() == 1 &&
-                      c->Dp <= 256 && c->flow_K > 0 &&
-                      c->cube_elems * sizeof(double) < (size_t(1) << 31);
-    // One part, no halo plans, the chain form: several sweeps per launch -- up to the next
-    // sweep that is saved or followed by a from-scratch residual.
-    const bool chain_batches = !flow && !any_plan && c->parts.size() == 1 && c->parts[0].chain &&
-                               c->mh_defer == 1 && n_phases == 1;
-    (void)chain_batches;
-    for (int s = first_sweep; s < first_sweep + n_sweeps; ++s) {
-        const uint32_t rs = (uint32_t)s + c->sweep_origin;
-#ifdef D3D_EXPERIMENTS
-        if (chain_batches) {
-            int last = first_sweep + n_sweeps - 1;  // last sweep of this launch
-            for (int t = s; t <= last; ++t) {
-                const bool saved = t % keep_one_in == 0 && (chain_out || dlog_out);
-                const bool refresh = c->refresh_every > 0 && t % c->refresh_every == 0;
-                if (saved || refresh || post_due(c, t)) {
-                    last = t;
-                    break;
-                }
-            }
-            if (c->lay_n && c->pend_part != 0)
-                if (int rc = flush_pending(c)) return rc;
-            if (int rc = launch_mh_chain(c, 0, rs, last - s + 1)) return rc;
-            s = last;
-        } else if (flow) {
-            c->pend_part = 0;
-            int rc = launch_mh_flow(c, rs);
-            if (rc) return rc;
-            c->pend_part = 0;
-        } else
-#endif
-        {
-            for (int ph = 0; ph < n_phases; ++ph) {
-                int rc = run_phase(c, ph, rs);
-                if (rc) return rc;
-                if (plan_has_entries(c, ph)) {
-                    hipEvent_t ev[2] = {nullptr, nullptr};
-                    if (c->halo_timing) {
-                        // a bounded ring of event pairs: a long call (50 000 sweeps x 2-4
-                        // phases) reduces the oldest pair when the ring is full
-                        if (c->halo_ev_used == d3d_ctx::HALO_RING)
-                            if (int rc2 = halo_drain_one(c)) return rc2;
-                        const size_t at = (c->halo_ev_head + c->halo_ev_used) % d3d_ctx::HALO_RING;
-                        while (c->halo_ev.size() < 2 * (at + 1)) {
-                            hipEvent_t e;
-                            HIP_TRY(hipEventCreate(&e));
-                            c->halo_ev.push_back(e);
-                        }
-                        ev[0] = c->halo_ev[2 * at];
-                        ev[1] = c->halo_ev[2 * at + 1];
-                        ++c->halo_ev_used;
-                        HIP_TRY(hipEventRecord(ev[0], c->stream));
-                    }
-                    rc = halo_exchange(c, ph);
-                    if (rc) return rc;
-                    if (ev[1]) HIP_TRY(hipEventRecord(ev[1], c->stream));
-                }
-            }
-        }
-        if (s % keep_one_in == 0 && (chain_out || dlog_out)) {
-            // lib/run.py:353, 430-432, 449-451 -- streamed: the compute stream only pays
-            // for a device-to-device snapshot
-            int rc = snap_push(c, snaps, s / keep_one_in, chain_out, dlog_out);
-            if (rc) return rc;
-        }
-        if (post_due(c, s))  // d3d_post_schedule: this sweep's state into the running moments
-            if (int rc = post_sample(c)) return rc;
-        if (c->adapt_on)     // d3d_adapt_begin: the sweep that fills a window moves the jump scales
-            if (int rc = d3dh::adapt_after_sweep(c, s)) return rc;
-        // lib/run.py:521-534: squash the error creep with a fresh residual.  A tile
-        // first gathers the parameters of the spaxels of its frame from their owners.
-        if (c->refresh_every > 0 && s % c->refresh_every == 0) {
-            if (plan_has_entries(c, D3D_PLAN_PARAMS)) {
-                NEED(c->comm, D3D_ERR_STATE, "parameter gather needs d3d_comm_init");
-                int rc = halo_exchange(c, D3D_PLAN_PARAMS);
-                if (rc) return rc;
-            }
-            int rc = forward_into(c, c->slot[D3D_SLOT_ERR], true);
-            if (rc) return rc;
-        }
-    }
-    unsigned long long acc = 0;
-    unsigned flow_err = 0;
-    HIP_TRY(hipMemcpyAsync(&acc, c->accepted, sizeof acc, hipMemcpyDeviceToHost, c->stream));
-    if (flow || c->mh_pair || c->chain_used)  // (these kernels raise *flow_err when a flag wait times out)
-        HIP_TRY(hipMemcpyAsync(&flow_err, c->flow_err, sizeof flow_err, hipMemcpyDeviceToHost,
-                               c->stream));
-    while (snaps.count > 0)
-        if (int rc = snap_drain_one(c, snaps, chain_out, dlog_out)) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    while (c->halo_ev_used > 0)  // option halo_timing
-        if (int rc = halo_drain_one(c)) return rc;
-    if (accepted) *accepted = (int64_t)acc;
-    c->chain_used = false;
-    NEED(!flow_err, D3D_ERR_HIP,
-         "a dependency wait inside a sweep kernel timed out (k_mh_chain needs all its workgroups "
-         "resident: is another process using this GPU?  option mh_chain = 0 avoids it); the "
-         "chain state is invalid");
-    return D3D_OK;
-}
-
-int d3d_mh_sweeps_batch(d3d_ctx **ctxs, int n_ctx, int n_sweeps, int first_sweep, int keep_one_in,
-                        double **chain_out, double **dlog_out, int64_t *accepted) {
-    NEED(ctxs && n_ctx >= 1, D3D_ERR_INVALID, "no contexts");
-    NEED(n_sweeps >= 0 && first_sweep >= 0, D3D_ERR_INVALID, "negative sweep count/index");
-    NEED(keep_one_in > 0, D3D_ERR_INVALID, "keep_one_in= MUST be a positive integer");
-    d3d_ctx *L = ctxs[0];
-    for (int r = 0; r < n_ctx; ++r) {
-        d3d_ctx *c = ctxs[r];
-        NEED(c, D3D_ERR_INVALID, "ctx %d is NULL", r);
-        for (int q = 0; q < r; ++q) NEED(ctxs[q] != c, D3D_ERR_INVALID, "ctx %d appears twice", r);
-        NEED(c->have_taps && c->have_data && c->have_params && c->have_cfg, D3D_ERR_STATE,
-             "ctx %d: taps/data/parameters/mh_config not set", r);
-        NEED(!c->tiled && c->parts.size() == 1 && !c->comm, D3D_ERR_UNSUPPORTED,
-             "ctx %d is tiled or partitioned: batched chains are whole cubes", r);
-        NEED(c->mh_defer == 1 && c->Dp <= 256 && !c->deep, D3D_ERR_UNSUPPORTED,
-             "ctx %d: batched chains take cubes up to 256 channels with the default write-back scheme", r);
-        NEED(c->device == L->device && c->D == L->D && c->H == L->H && c->W == L->W && c->fh == L->fh &&
-                 c->fw == L->fw,
-             D3D_ERR_INVALID, "ctx %d: another device or shape than ctx 0", r);
-        NEED(c->h_mask == L->h_mask && c->h_fsf == L->h_fsf && c->h_has_lsf == L->h_has_lsf &&
-                 (!c->h_has_lsf || c->h_lsf == L->h_lsf) && c->h_thr == L->h_thr,
-             D3D_ERR_INVALID, "ctx %d: another mask, FSF or LSF than ctx 0 (the chains share the work lists and taps)", r);
-        NEED((c->ivar_is_uniform && c->uniform_fast_path) == (L->ivar_is_uniform && L->uniform_fast_path),
-             D3D_ERR_INVALID, "ctx %d: uniform and per-voxel variances cannot share a launch", r);
-        NEED(c->mh_zigzag == L->mh_zigzag && c->sweep_origin == L->sweep_origin, D3D_ERR_INVALID,
-             "ctx %d: another walk order or sweep origin than ctx 0", r);
-        bool same_line = c->line.K == L->line.K;
-        for (int k = 0; k < d3d::LINE_KMAX; ++k)
-            same_line = same_line && c->line.off[k] == L->line.off[k] && c->line.ratio[k] == L->line.ratio[k];
-        NEED(same_line, D3D_ERR_INVALID,
-             "ctx %d: another line shape than ctx 0 (the chains share the launch's arguments)", r);
-        // (the chains share the leader's pending-layer state, and a from-scratch residual
-        // clears a chain's own: they must all be rebuilt at the same sweeps)
-        NEED(c->prior_on == L->prior_on, D3D_ERR_INVALID,
-             "ctx %d: the smoothness prior (d3d_prior_begin) is %s, on ctx 0 it is %s (the chains share the "
-             "launch's kernel; their weights may differ)", r, c->prior_on ? "on" : "off", L->prior_on ? "on" : "off");
-        NEED(c->refresh_every == L->refresh_every, D3D_ERR_INVALID,
-             "ctx %d: refresh_every %d differs from ctx 0's %d (batched chains rebuild their residuals together)",
-             r, c->refresh_every, L->refresh_every);
-    }
-    HIP_TRY(hipSetDevice(L->device));
-    // saved sweeps (lib/run.py:353, 430-432, 449-451): every chain streams its samples as
-    // d3d_mh_sweeps does -- device snapshot on the common stream, copy stream, pinned ring
-    const bool saving = chain_out || dlog_out;
-    std::vector<SnapQueue> snaps(n_ctx);
-    if (saving)
-        for (int r = 0; r < n_ctx; ++r)
-            if (int rc = snap_setup(ctxs[r])) return rc;
-    auto co = [&](int r) { return chain_out ? chain_out[r] : nullptr; };
-    auto lo = [&](int r) { return dlog_out ? dlog_out[r] : nullptr; };
-    std::function<int(int)> after;
-    std::function<int()> drain;
-    bool scheduled = false;  // d3d_post_schedule on any of them
-    for (int r = 0; r < n_ctx; ++r) scheduled = scheduled || (ctxs[r]->post_on && ctxs[r]->post_every > 0);
-    if (saving || scheduled)
-        after = [&](int s) {
-            if (saving && s % keep_one_in == 0)
-                for (int r = 0; r < n_ctx; ++r)
-                    if (co(r) || lo(r))
-                        if (int rc = snap_push(ctxs[r], snaps[r], s / keep_one_in, co(r), lo(r))) return rc;
-            for (int r = 0; r < n_ctx; ++r)
-                if (post_due(ctxs[r], s))
-                    if (int rc = post_sample(ctxs[r])) return rc;
-            return 0;
-        };
-    if (saving) {
-        drain = [&]() {
-            for (int r = 0; r < n_ctx; ++r)
-                while (snaps[r].count > 0)
-                    if (int rc = snap_drain_one(ctxs[r], snaps[r], co(r), lo(r))) return rc;
-            return 0;
-        };
-    }
-    return mh_sweeps_batch(ctxs, n_ctx, n_sweeps, first_sweep, accepted, after, drain);
-}
-
-int d3d_mh_phase(d3d_ctx *c, int phase, int sweep) {
-    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
-    NEED(c->have_taps && c->have_data && c->have_params && c->have_cfg, D3D_ERR_STATE,
-         "taps/data/parameters/mh_config not set");
-    // (a tile may have no part in a phase its neighbours have: then there is nothing to do)
-    NEED(phase >= 0 && phase < D3D_PLAN_PARAMS && sweep >= 0, D3D_ERR_INVALID,
-         "phase %d / sweep %d out of range", phase, sweep);
-    HIP_TRY(hipSetDevice(c->device));
-    if (!c->err_valid) {
-        int rc = d3d_residual(c, nullptr);
-        if (rc) return rc;
-    }
-    c->props_sweep = -1;  // (recomputed per call: the spaxels not yet updated get the same proposals)
-    return run_phase(c, phase, (uint32_t)sweep + c->sweep_origin);
-}
-
 int d3d_mh_accepted(d3d_ctx *c, int64_t *count, int reset) {
     NEED(c && count, D3D_ERR_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(c->device));
@@ -2206,33 +1805,6 @@ int d3d_set_parts(d3d_ctx *c, int nparts, const int *rects, const int *phases) {
     return D3D_OK;
 }
 
-int d3d_mh_colour(d3d_ctx *c, int colour, int sweep) {
-    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
-    NEED(c->have_taps && c->have_data && c->have_params && c->have_cfg, D3D_ERR_STATE,
-         "taps/data/parameters/mh_config not set");
-    NEED(colour >= 0 && colour < c->fh * c->fw && sweep >= 0, D3D_ERR_INVALID,
-         "colour %d / sweep %d out of range", colour, sweep);
-    HIP_TRY(hipSetDevice(c->device));
-    if (!c->err_valid) {
-        int rc = d3d_residual(c, nullptr);
-        if (rc) return rc;
-    }
-    if (int rc = flush_pending(c)) return rc;
-    for (const d3d_ctx::Part &pt : c->parts) {
-        const int n_real = pt.real[colour];
-        if (n_real <= 0) continue;
-        d3d::MHArgs P;
-        fill_mh_args(c, P);
-        P.spx = c->spx + pt.off[colour];
-        int ord = 0;  // the colour's ordinal among the part's active ones, as in run_part
-        for (int col = 0; col < colour; ++col) ord += pt.real[col] > 0;
-        P.rev = (c->mh_zigzag && (ord & 1)) ? 1 : 0;
-        int rc = launch_mh(c, P, (unsigned)n_real, (uint32_t)sweep + c->sweep_origin);
-        if (rc) return rc;
-    }
-    return D3D_OK;
-}
-
 int d3d_export_updates(d3d_ctx *c, int n, const int *spaxels, double *out) {
     NEED(c && (n == 0 || (spaxels && out)), D3D_ERR_INVALID, "NULL argument");
     NEED(n >= 0 && n <= c->HW, D3D_ERR_INVALID, "bad record count %d", n);
@@ -2404,9 +1976,15 @@ int halo_unpack(d3d_ctx *c, int plan) {
     return 0;
 }
 
+}  // namespace
+
+bool d3dh::plan_has_entries(const d3d_ctx *c, int plan) {
+    return plan >= 0 && plan < (int)c->plans.size() && !c->plans[plan].empty();
+}
+
 // pack -> grouped point-to-point RCCL send/recv -> unpack, all queued on the ctx
 // stream: no host synchronisation, no staging through host memory.
-int halo_exchange(d3d_ctx *c, int plan) {
+int d3dh::halo_exchange(d3d_ctx *c, int plan) {
     if (!plan_has_entries(c, plan)) return 0;
     if (!c->comm) return fail(D3D_ERR_STATE, "d3d_comm_init has not been called");
     if (int rc = halo_pack(c, plan)) return rc;
@@ -2422,6 +2000,8 @@ int halo_exchange(d3d_ctx *c, int plan) {
     RCCL_TRY(g_rccl.GroupEnd());
     return halo_unpack(c, plan);
 }
+
+namespace {
 
 bool plan_ok(const d3d_ctx *c, int plan) { return plan >= 0 && plan < (int)c->plans.size(); }
 

@@ -1,8 +1,8 @@
 // Internal header of libdeconv3d_hip.so: the context struct and the launch
 // functions shared by the library's translation units (d3d_api.hip: C ABI and host
 // logic; d3d_spatial.hip: line / LSF / FSF kernels; d3d_mh.hip: the MH-within-Gibbs
-// kernels; d3d_post.hip: posterior moments; d3d_search.hip: the matched-filter line search;
-// d3d_prep.hip: continuum removal and channel noise of a raw cube).
+// kernels; d3d_sweep.hip: the sweep driver; d3d_post.hip: posterior moments; d3d_search.hip: the
+// matched-filter line search; d3d_prep.hip: continuum removal and channel noise of a raw cube).
 // Not installed: the public interface is include/deconv3d_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -16,7 +16,6 @@
 #include <cstring>
 #include <new>
 #include <string>
-#include <functional>
 #include <vector>
 
 #include "../../include/deconv3d_hip.h"
@@ -342,6 +341,15 @@ bool zmajor_ok(const d3d_ctx *c);
 // LSF (x) FSF of c->stage in the reference layout (D,H,W), in place (zmajor_ok())
 int launch_zmajor_convolve(d3d_ctx *c);
 
+// ---- d3d_api.hip: what the sweep driver runs between and after the sweeps -----------------
+int post_sample(d3d_ctx *c);               // the chain state as one more sample of the posterior moments
+bool post_due(const d3d_ctx *c, int s);    // sweep s (the caller's numbering) is one d3d_post_schedule asked for
+bool plan_has_entries(const d3d_ctx *c, int plan);
+int halo_exchange(d3d_ctx *c, int plan);
+
+// ---- d3d_sweep.hip: local colour residues of colour class `col` (a tile's origin shifts them)
+void colour_residue(const d3d_ctx *c, int col, int *cy, int *cx);
+
 // ---- d3d_mh.hip: the MH-within-Gibbs kernels ---------------------------------------------
 void pend_clear(d3d_ctx *c);
 int pend_free_buf(const d3d_ctx *c);
@@ -349,13 +357,21 @@ void pend_push(d3d_ctx *c, int cy, int cx, int g);
 void fill_mh_args(d3d_ctx *c, d3d::MHArgs &P);
 int launch_mh(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep);
 int launch_mh_zb(d3d_ctx *c, d3d::MHArgs &P, unsigned n_items, uint32_t sweep, int layers);
-int mh_sweeps_batch(d3d_ctx **cs, int R, int n_sweeps, int first_sweep, int64_t *accepted,
-                    const std::function<int(int)> &after_sweep, const std::function<int()> &drain);
+// a colour launch of R chains together (MHArgs::batch; d3d_mh_sweeps_batch), grid = R x windows
+int launch_mh_batch(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep, int layers);
+// what differs between the chains of a joint launch; tables: with the chain's sweep tables
+void fill_chain_args(const d3d_ctx *c, d3d::MHChainArgs &B, bool tables);
 int launch_mh_defer(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep, int layers,
                     bool wide);
 int flush_pending(d3d_ctx *c);
 // the proposals of sweep `sweep` for every owned spaxel (MHArgs::props), once per sweep
 int ensure_proposals(d3d_ctx *c, uint32_t sweep);
+// the proposal table and (lines) the line table, allocated on first use; the position tables
+int ensure_tables(d3d_ctx *c, bool lines);
+int ensure_ptab(d3d_ctx *c);
+// proposals and line table of sweep `sweep` (k_mh_line_table): the context's, or those of the R
+// chains of a batch in one launch
+int launch_line_table(d3d_ctx *c, const d3d::MHArgs &P, uint32_t sweep, const d3d::MHChainArgs *chains, int R);
 // k_mh_small can take this context's small parts (depth, tap count, options)
 bool mh_small_usable(const d3d_ctx *c);
 // row of the position tables for a launch of local colour residues (ly, lx) over the pending layer

@@ -28,7 +28,39 @@ void pend_push(d3d_ctx *c, int cy, int cx, int g) {
     ++c->lay_n;
 }
 
+// What differs between the chains of a batch: fields MHArgs (one context's launch) and
+// MHChainArgs (a chain of a joint launch) both have.
+template <class A>
+static void fill_chain_fields(const d3d_ctx *c, A &a) {
+    a.err = c->slot[D3D_SLOT_ERR];
+    a.ivar = c->slot[D3D_SLOT_IVAR];
+    a.ivar_uniform = c->ivar_uniform;
+    a.params = c->params;
+    a.prev = c->prev;
+    a.dlog = c->dlog;
+    a.accepted = c->accepted;
+    for (int k = 0; k < 3; ++k) {
+        a.min_b[k] = c->min_b[k];
+        a.max_b[k] = c->max_b[k];
+        a.amp[k] = c->amp[k];
+        a.lam[k] = c->prior_on ? c->prior_lam[k] : 0.0;
+    }
+    a.ra = c->ra;
+    a.seed = c->seed;
+    a.jscale = c->adapt_on ? c->jscale : nullptr;
+    a.jacc = c->adapt_on ? c->jacc : nullptr;
+    a.prior = c->prior_on ? 1 : 0;
+}
+
+void fill_chain_args(const d3d_ctx *c, d3d::MHChainArgs &B, bool tables) {
+    fill_chain_fields(c, B);
+    for (int b = 0; b < 4; ++b) B.gbuf[b] = c->gbuf[b];
+    B.props = tables ? c->props : nullptr;  // (k_mh_small: the chain's tables of the sweep)
+    B.ltab = tables ? c->ltab : nullptr;
+}
+
 void fill_mh_args(d3d_ctx *c, d3d::MHArgs &P) {
+    fill_chain_fields(c, P);
     P.D = c->D;
     P.Dp = c->Dp;
     P.HL = c->HL;
@@ -39,16 +71,9 @@ void fill_mh_args(d3d_ctx *c, d3d::MHArgs &P) {
     P.N = c->N;
     P.ntaps = c->ntaps;
     P.npos = c->fh * c->fw;
-    P.err = c->slot[D3D_SLOT_ERR];
-    P.ivar = c->slot[D3D_SLOT_IVAR];
-    P.ivar_uniform = c->ivar_uniform;
-    P.params = c->params;
-    P.prev = c->prev;
     P.fsf = c->fsf;
     P.shift = c->lsf_shift;
     P.weight = c->lsf_weight;
-    P.dlog = c->dlog;
-    P.accepted = c->accepted;
     P.spx = c->spx;
     P.rev = 0;
     P.prio = c->mh_prio;
@@ -58,7 +83,7 @@ void fill_mh_args(d3d_ctx *c, d3d::MHArgs &P) {
     P.ptab = nullptr;
     P.ptab_row[0] = P.ptab_row[1] = c->fh * c->fw;
     P.line = c->line;
-    P.batch = nullptr;  // (mh_sweeps_batch)
+    P.batch = nullptr;  // (d3d_mh_sweeps_batch)
     P.b_items = 0;
     P.b_gcur = 0;
     P.b_lay_g[0] = P.b_lay_g[1] = P.b_lay_g[2] = 0;
@@ -67,13 +92,6 @@ void fill_mh_args(d3d_ctx *c, d3d::MHArgs &P) {
     P.z_db = 256;
     P.z_nb = (c->Dp + P.z_db - 1) / P.z_db;
     P.z_slots = (int)c->slots;
-    for (int k = 0; k < 3; ++k) {
-        P.min_b[k] = c->min_b[k];
-        P.max_b[k] = c->max_b[k];
-        P.amp[k] = c->amp[k];
-    }
-    P.ra = c->ra;
-    P.seed = c->seed;
     P.gy0 = c->gy0;
     P.gx0 = c->gx0;
     P.Wg = c->Wg;
@@ -118,10 +136,6 @@ void fill_mh_args(d3d_ctx *c, d3d::MHArgs &P) {
 #ifdef D3D_EXPERIMENTS
     P.stamp = nullptr;
 #endif
-    P.jscale = c->adapt_on ? c->jscale : nullptr;
-    P.jacc = c->adapt_on ? c->jacc : nullptr;
-    P.prior = c->prior_on ? 1 : 0;
-    for (int k = 0; k < 3; ++k) P.lam[k] = c->prior_on ? c->prior_lam[k] : 0.0;
 }
 
 int prior_energy(d3d_ctx *c, const double *params_dev, double out4[4]) {
@@ -320,7 +334,7 @@ bool mh_part_uses_tables(const d3d_ctx *c, const d3d_ctx::Part &pt) {
 }
 
 // The relative position tables of k_mh_small (d3d_mh_small.h: MHPos), once per set of taps.
-static int ensure_ptab(d3d_ctx *c) {
+int ensure_ptab(d3d_ctx *c) {
     if (c->ptab_valid) return 0;
     const int fh = c->fh, fw = c->fw, npos = fh * fw, fhh = (fh - 1) / 2, fhw = (fw - 1) / 2;
     std::vector<double> tab((size_t)(npos + 1) * npos * 4, 0.0);
@@ -716,144 +730,9 @@ int launch_mh_batch_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t 
     return 0;
 }
 
-int mh_sweeps_batch(d3d_ctx **cs, int R, int n_sweeps, int first_sweep, int64_t *accepted,
-                    const std::function<int(int)> &after_sweep, const std::function<int()> &drain) {
-    d3d_ctx *L = cs[0];  // the leader: its stream, its work lists
-    const d3d_ctx::Part &pt = L->parts[0];
-    const int ncol = L->fh * L->fw;
-    int most = 0;
-    for (int col = 0; col < ncol; ++col) most = std::max(most, pt.off[col + 1] - pt.off[col]);
-    // two pending layers where the launch of all chains together fills the chip
-    const int layers = (L->Dp <= 160 && (long)most * R >= L->flow_grid / 2) ? 2 : 1;
-    for (int r = 0; r < R; ++r) cs[r]->batch_layers = layers;  // (read-only option batch_layers)
-    const bool uv = L->ivar_is_uniform && L->uniform_fast_path;
-    // a joint launch that still does not fill the chip: k_mh_small with the chains' sweep tables
-    bool small = layers == 1;
-    for (int r = 0; r < R; ++r) small = small && mh_small_usable(cs[r]);
-    // every chain on the leader's stream for the duration of the call
-    std::vector<hipStream_t> own(R);
-    for (int r = 0; r < R; ++r) {
-        HIP_TRY(hipStreamSynchronize(cs[r]->stream));
-        own[r] = cs[r]->stream;
-        cs[r]->stream = L->stream;
-    }
-    auto restore = [&]() {
-        for (int r = 0; r < R; ++r) cs[r]->stream = own[r];
-    };
-    int rc = 0;
-    d3d::MHChainArgs *dev = nullptr;
-    do {
-        std::vector<d3d::MHChainArgs> host(R);
-        for (int r = 0; r < R && !rc; ++r) {
-            d3d_ctx *c = cs[r];
-            if (!c->err_valid) rc = d3d_residual(c, nullptr);
-            if (!rc) rc = flush_pending(c);
-            if (rc) break;
-            if (hipMemsetAsync(c->accepted, 0, sizeof(unsigned long long), c->stream) != hipSuccess) rc = fail(D3D_ERR_HIP, "hipMemsetAsync");
-            d3d::MHChainArgs &B = host[r];
-            B.err = c->slot[D3D_SLOT_ERR];
-            B.ivar = c->slot[D3D_SLOT_IVAR];
-            B.ivar_uniform = c->ivar_uniform;
-            B.params = c->params;
-            B.prev = c->prev;
-            B.dlog = c->dlog;
-            B.accepted = c->accepted;
-            for (int b = 0; b < 4; ++b) B.gbuf[b] = c->gbuf[b];
-            for (int k = 0; k < 3; ++k) {
-                B.min_b[k] = c->min_b[k];
-                B.max_b[k] = c->max_b[k];
-                B.amp[k] = c->amp[k];
-            }
-            B.ra = c->ra;
-            B.seed = c->seed;
-            c->props_sweep = -1;
-            B.props = nullptr;
-            B.ltab = nullptr;
-            B.jscale = c->adapt_on ? c->jscale : nullptr;
-            B.jacc = c->adapt_on ? c->jacc : nullptr;
-            B.prior = c->prior_on ? 1 : 0;
-            for (int k = 0; k < 3; ++k) B.lam[k] = c->prior_on ? c->prior_lam[k] : 0.0;
-            if (small) {
-                if (!c->props && hipMalloc(&c->props, (size_t)c->HW * sizeof(d3d::MHProposal)) != hipSuccess) rc = fail(D3D_ERR_HIP, "hipMalloc");
-                if (!rc && !c->ltab && hipMalloc(&c->ltab, (size_t)c->HW * 2 * c->Dp * sizeof(double)) != hipSuccess) rc = fail(D3D_ERR_HIP, "hipMalloc");
-                B.props = c->props;
-                B.ltab = c->ltab;
-            }
-        }
-        if (rc) break;
-        if (small) rc = ensure_ptab(L);
-        if (rc) break;
-        if (hipMalloc(&dev, R * sizeof(d3d::MHChainArgs)) != hipSuccess) { rc = fail(D3D_ERR_HIP, "hipMalloc"); break; }
-        if (hipMemcpy(dev, host.data(), R * sizeof(d3d::MHChainArgs), hipMemcpyHostToDevice) != hipSuccess) { rc = fail(D3D_ERR_HIP, "hipMemcpy"); break; }
-        for (int s = first_sweep; s < first_sweep + n_sweeps && !rc; ++s) {
-            const uint32_t rs = (uint32_t)s + L->sweep_origin;
-            if (small) {  // every chain's proposals and lines of this sweep, one launch
-                d3d::MHArgs T;
-                fill_mh_args(L, T);
-                const int n = (L->oy1 - L->oy0) * (L->ox1 - L->ox0);
-                const size_t lds = (size_t)4 * 2 * L->N * sizeof(double);
-                hipLaunchKernelGGL(L->line.K > 1 ? &d3d::k_mh_line_table<true> : &d3d::k_mh_line_table<false>,
-                                   dim3((unsigned)(((long)n * R + 3) / 4)), dim3(256), lds,
-                                   L->stream, T, rs, L->oy0, L->oy1, L->ox0, L->ox1, L->props, L->ltab,
-                                   (const d3d::MHChainArgs *)dev, R);
-                if (hipGetLastError() != hipSuccess) { rc = fail(D3D_ERR_HIP, "k_mh_line_table"); break; }
-            }
-            int ord = 0;
-            for (int col = 0; col < ncol && !rc; ++col) {
-                if (pt.real[col] <= 0) continue;
-                const int ka = ord++;
-                L->pend_part = 0;
-                d3d::MHArgs P;
-                fill_mh_args(L, P);
-                if (small) {
-                    P.props = L->props;   // (replaced per chain in the kernel)
-                    P.ltab = L->ltab;
-                    P.ptab = L->ptab;
-                    P.ptab_row[0] = mh_ptab_row(L, ((col / L->fw - L->gy0) % L->fh + L->fh) % L->fh,
-                                                ((col % L->fw - L->gx0) % L->fw + L->fw) % L->fw);
-                }
-                P.spx = L->spx + pt.off[col];
-                P.rev = (L->mh_zigzag && (ka & 1)) ? 1 : 0;
-                const int n_all = pt.off[col + 1] - pt.off[col];
-                P.write_back = (L->lay_n >= layers) ? 1 : 0;
-                const int g_cur = pend_free_buf(L);
-                P.batch = dev;
-                P.b_items = n_all;
-                P.b_gcur = g_cur;
-                for (int j = 0; j < 3; ++j) P.b_lay_g[j] = j < L->lay_n ? L->lay_g[j] : 0;
-                rc = uv ? launch_mh_batch_t<true>(L, P, (unsigned)n_all * R, rs, layers)
-                        : launch_mh_batch_t<false>(L, P, (unsigned)n_all * R, rs, layers);
-                if (rc) break;
-                const int cy = ((col / L->fw - L->gy0) % L->fh + L->fh) % L->fh;
-                const int cx = ((col % L->fw - L->gx0) % L->fw + L->fw) % L->fw;
-                for (int r = 0; r < R; ++r) {  // all chains keep their pending layers alike
-                    d3d_ctx *c = cs[r];
-                    if (P.write_back) c->lay_n = 0;
-                    pend_push(c, cy, cx, g_cur);
-                    c->pend_part = 0;
-                }
-            }
-            if (!rc && after_sweep) rc = after_sweep(s);  // (saved sweeps: snapshots of every chain)
-            for (int r = 0; r < R && !rc; ++r) rc = adapt_after_sweep(cs[r], s);  // (each from its own counters)
-            // lib/run.py:521-534, per chain
-            for (int r = 0; r < R && !rc; ++r)
-                if (cs[r]->refresh_every > 0 && s % cs[r]->refresh_every == 0)
-                    rc = forward_into(cs[r], cs[r]->slot[D3D_SLOT_ERR], true);
-        }
-        if (rc) break;
-        if (drain) rc = drain();
-        if (rc) break;
-        std::vector<unsigned long long> acc(R, 0);
-        for (int r = 0; r < R; ++r)
-            if (hipMemcpyAsync(&acc[r], cs[r]->accepted, sizeof(unsigned long long), hipMemcpyDeviceToHost, L->stream) != hipSuccess) rc = fail(D3D_ERR_HIP, "hipMemcpyAsync");
-        if (hipStreamSynchronize(L->stream) != hipSuccess) rc = fail(D3D_ERR_HIP, "hipStreamSynchronize");
-        if (!rc && accepted)
-            for (int r = 0; r < R; ++r) accepted[r] = (int64_t)acc[r];
-    } while (false);
-    (void)hipStreamSynchronize(L->stream);
-    if (dev) (void)hipFree(dev);
-    restore();
-    return rc;
+int launch_mh_batch(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep, int layers) {
+    if (c->ivar_is_uniform && c->uniform_fast_path) return launch_mh_batch_t<true>(c, P, grid, sweep, layers);
+    return launch_mh_batch_t<false>(c, P, grid, sweep, layers);
 }
 
 int launch_mh_defer(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep, int layers,
@@ -873,25 +752,35 @@ int launch_mh_defer(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sw
     }
 }
 
+int ensure_tables(d3d_ctx *c, bool lines) {
+    if (!c->props) HIP_TRY(hipMalloc(&c->props, (size_t)c->HW * sizeof(d3d::MHProposal)));
+    if (lines && !c->ltab) HIP_TRY(hipMalloc(&c->ltab, (size_t)c->HW * 2 * c->Dp * sizeof(double)));
+    return 0;
+}
+
+int launch_line_table(d3d_ctx *c, const d3d::MHArgs &P, uint32_t sweep, const d3d::MHChainArgs *chains, int R) {
+    const long n = (long)(c->oy1 - c->oy0) * (c->ox1 - c->ox0) * std::max(R, 1);  // one wavefront per spaxel
+    if (n <= 0) return 0;
+    const size_t lds = (size_t)4 * 2 * c->N * sizeof(double);
+    hipLaunchKernelGGL(c->line.K > 1 ? &d3d::k_mh_line_table<true> : &d3d::k_mh_line_table<false>,
+                       dim3((unsigned)((n + 3) / 4)), dim3(256), lds, c->stream, P, sweep, c->oy0, c->oy1,
+                       c->ox0, c->ox1, c->props, c->ltab, chains, R);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 int ensure_proposals(d3d_ctx *c, uint32_t sweep) {
     if (c->props_sweep == (long)sweep) return 0;
-    if (!c->props) HIP_TRY(hipMalloc(&c->props, (size_t)c->HW * sizeof(d3d::MHProposal)));
+    // with the lines of every update where a part runs k_mh_small
+    bool lines = false;
+    for (const d3d_ctx::Part &pt : c->parts) lines = lines || mh_part_uses_tables(c, pt);
+    if (int rc = ensure_tables(c, lines)) return rc;
     d3d::MHArgs P;
     fill_mh_args(c, P);
     const int n = (c->oy1 - c->oy0) * (c->ox1 - c->ox0);
-    // with the lines of every update where a part runs k_mh_small (one wavefront per spaxel)
-    bool lines = false;
-    for (const d3d_ctx::Part &pt : c->parts) lines = lines || mh_part_uses_tables(c, pt);
-    if (lines && !c->ltab) HIP_TRY(hipMalloc(&c->ltab, (size_t)c->HW * 2 * c->Dp * sizeof(double)));
-    if (lines)
+    if (lines) {
         if (int rc = ensure_ptab(c)) return rc;
-    if (n > 0 && lines) {
-        const size_t lds = (size_t)4 * 2 * c->N * sizeof(double);
-        hipLaunchKernelGGL(c->line.K > 1 ? &d3d::k_mh_line_table<true> : &d3d::k_mh_line_table<false>,
-                           dim3((unsigned)((n + 3) / 4)), dim3(256), lds, c->stream, P,
-                           sweep, c->oy0, c->oy1, c->ox0, c->ox1, c->props, c->ltab,
-                           (const d3d::MHChainArgs *)nullptr, 0);
-        HIP_TRY(hipGetLastError());
+        if (int rc = launch_line_table(c, P, sweep, nullptr, 0)) return rc;
     } else if (n > 0) {
         hipLaunchKernelGGL(d3d::k_mh_proposals, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
                            P, sweep, c->oy0, c->oy1, c->ox0, c->ox1, c->props);
@@ -1022,8 +911,9 @@ int launch_mh_chain(d3d_ctx *c, int pi, uint32_t sweep0, int n_sweeps) {
     c->chain_used = true;
     // afterwards the part's last colour is the one pending layer (local residues)
     pend_clear(c);
-    pend_push(c, ((pt.last_col / c->fw - c->gy0) % c->fh + c->fh) % c->fh,
-              ((pt.last_col % c->fw - c->gx0) % c->fw + c->fw) % c->fw, g_out);
+    int cy, cx;
+    colour_residue(c, pt.last_col, &cy, &cx);
+    pend_push(c, cy, cx, g_out);
     c->pend_part = pi;
     return 0;
 }

@@ -304,6 +304,98 @@ def test_batched_chains_then_alone_whatever_layers_were_left_pending():
             e.close()
 
 
+def every_hook_case(D, empty_class):
+    """A 3 x 3 Gaussian FSF (nine colour classes) on 10 x 11 spaxels -- neither a multiple of 3 --,
+    the LSF on, per-voxel variance, spaxels (0, 2) and (0, 5) masked; empty_class: all of colour
+    class (0, 2) masked, so that the ordinal of the later classes is not their index."""
+    from oracle import deconv3d_oracle as O
+    H, W = 10, 11
+    rng = np.random.default_rng(2024 + D)
+    g = np.exp(-0.5 * (np.arange(-1, 2) / 0.8) ** 2)
+    fsf = np.outer(g, g) / np.sum(np.outer(g, g))
+    lsf = O.gaussian_lsf_vector(D, 0.9088)
+    mask = np.ones((H, W))
+    mask[0, 2] = mask[0, 5] = 0
+    if empty_class:
+        mask[0::3, 2::3] = 0
+    truth = np.dstack((1.0 + 9.0 * rng.random((H, W)), D * (0.25 + 0.5 * rng.random((H, W))),
+                       0.8 + 2.0 * rng.random((H, W))))
+    clean = O.forward_full((D, H, W), truth, mask, fsf, lsf)
+    sigma = 0.05 * np.max(clean) + 1e-3
+    data = clean + rng.normal(0., sigma, size=(D, H, W))
+    var = (sigma * (0.5 + rng.random((D, H, W)))) ** 2
+    min_b, max_b = O.model_min_boundaries(), O.model_max_boundaries(data, fsf)
+    init = min_b + (max_b - min_b) * rng.random((H, W, 3))
+    init[..., 2] = np.maximum(init[..., 2], 0.3)
+    return dict(D=D, H=H, W=W, fsf=fsf, lsf=lsf, mask=mask, data=data, var=var, min_b=min_b,
+                max_b=max_b, init=init)
+
+
+@pytest.mark.parametrize("D,empty_class", [(16, False), (21, False), (16, True)])
+def test_every_end_of_sweep_hook_at_once_batched_and_alone_across_a_call_boundary(D, empty_class):
+    """What follows a sweep -- streamed snapshot (every 2nd sweep), posterior sample (sweeps 6, 8,
+    10, 12), jump-scale step (window 3, up to sweep 9), from-scratch residual (every 5th) -- with
+    the smoothness prior on the line centre, over 12 sweeps in two calls of 7 and 5: three
+    contexts of seeds s, s + 1, s + 2 through d3d_mh_sweeps_batch equal three fresh ones through
+    d3d_mh_sweeps one at a time, bit for bit, in every array the library hands back.  (21: odd
+    depth, a padded spectrum.  Two masked spaxels cannot empty a colour class of 10 x 11 spaxels
+    -- the smallest has nine --, so a third case masks the whole of class (0, 2).)"""
+    from deconv3d_amd import ensemble
+    case = every_hook_case(D, empty_class)
+    H, W, R, seed = case["H"], case["W"], 3, 500
+
+    def make(r):
+        eng = _lib.Engine((D, H, W), case["fsf"].shape)
+        eng.set_taps(case["fsf"], case["lsf"])
+        eng.set_data(case["data"], case["var"], mask=case["mask"])
+        eng.set_params(case["init"])
+        eng.mh_config(case["min_b"], case["max_b"], 0.1, 40.0, seed=seed + r, refresh_every=5)
+        eng.adapt_begin(window=3, last_sweep=9)
+        eng.post_begin()
+        eng.post_schedule(6, 2)
+        eng.prior_begin([0., 1. / 2.0 ** 2, 0.])
+        return eng
+
+    def state(eng, chain, dlog, accepted):
+        out = [chain[1:], dlog[1:], np.asarray(accepted), eng.get_params()]
+        out += [np.asarray(a) for a in eng.adapt_get()]
+        for which in (0, 1, 2):
+            out += list(eng.post_get(which))
+        assert np.isnan(chain[0]).all() and not np.isnan(chain[1:][:, case["mask"] == 1]).any()
+        return out + [np.asarray(eng.post_count())]
+
+    def arrays():
+        return np.full((7, H, W, 3), np.nan), np.full((7, H, W), np.nan)
+
+    alone = []
+    for r in range(R):
+        with make(r) as eng:
+            chain, dlog = arrays()
+            acc = [eng.mh_sweeps(7, 1, 2, chain, dlog), eng.mh_sweeps(5, 8, 2, chain, dlog)]
+            alone.append(state(eng, chain, dlog, acc))
+    engs = [make(r) for r in range(R)]
+    try:
+        chains, dlogs = zip(*[arrays() for _ in engs])
+        a1 = ensemble.sweep_chains_batched(engs, 7, 1, 2, list(chains), list(dlogs))
+        a2 = ensemble.sweep_chains_batched(engs, 5, 8, 2, list(chains), list(dlogs))
+        for r, eng in enumerate(engs):
+            got = state(eng, chains[r], dlogs[r], [a1[r], a2[r]])
+            assert len(got) == len(alone[r]) == 15
+            for i, (a, b) in enumerate(zip(got, alone[r])):
+                assert np.array_equal(a, b, equal_nan=True), "chain %d, array %d" % (r, i)
+    finally:
+        for e in engs:
+            e.close()
+    # the case is not degenerate: proposals are taken and refused, the scales moved three times,
+    # four samples, and the seeds give different chains
+    live = int(np.sum(case["mask"] == 1))
+    for r in range(R):
+        assert 0 < int(np.sum(alone[r][2])) < 12 * live
+        assert int(alone[r][6]) == 3 and int(alone[r][7]) == 3 and int(alone[r][14]) == 4
+        assert len(np.unique(alone[r][4][case["mask"] == 1])) > 1
+    assert not np.array_equal(alone[0][3], alone[1][3])
+
+
 def test_run_is_reproducible_and_seed_sensitive():
     inst, cube, var, _, _ = synthetic_cube(D=16, H=9, W=9, seed=3)
     a = d3d.Run(cube, inst, variance=var, max_iterations=6, seed=11)
