@@ -11,7 +11,7 @@ from .masks import above_percentile, above_snr  # noqa: F401
 from .math_utils import median_clip  # noqa: F401
 from . import adapt  # noqa: F401
 from . import posterior  # noqa: F401
-from .posterior import PosteriorMoments  # noqa: F401
+from .posterior import PosteriorHistograms, PosteriorMoments  # noqa: F401
 from . import prepare  # noqa: F401
 from .prepare import Prepared, prepare_cube  # noqa: F401
 from .run import Run, logger  # noqa: F401

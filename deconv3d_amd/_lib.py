@@ -38,6 +38,7 @@ SYMBOLS = [
     "d3d_mh_colour", "d3d_export_updates", "d3d_apply_updates",
     "d3d_post_begin", "d3d_post_schedule", "d3d_post_accumulate", "d3d_post_count", "d3d_post_get",
     "d3d_post_end",
+    "d3d_hist_begin", "d3d_hist_count", "d3d_hist_get", "d3d_hist_quantiles", "d3d_hist_end",
     "d3d_adapt_begin", "d3d_adapt_get", "d3d_adapt_set", "d3d_adapt_end",
     "d3d_prior_begin", "d3d_prior_get", "d3d_prior_end", "d3d_prior_energy",
     "d3d_line_search",
@@ -53,6 +54,15 @@ POST_PROTOTYPES = {
     "d3d_post_count": [C.POINTER(C.c_int64)],
     "d3d_post_get": [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)],
     "d3d_post_end": [],
+}
+# posterior histograms (a table for the same reason: tools/hist_time.py loads the parent's library)
+HIST_PROTOTYPES = {
+    "d3d_hist_begin": [C.c_int64, C.c_double],
+    "d3d_hist_count": [C.POINTER(C.c_int64)],
+    "d3d_hist_get": [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_double)],
+    "d3d_hist_quantiles": [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                           C.POINTER(C.c_double)],
+    "d3d_hist_end": [],
 }
 # per-spaxel jump scales (a table for the same reason: tools that load the parent's library)
 ADAPT_PROTOTYPES = {
@@ -193,7 +203,7 @@ def load():
     lib.d3d_apply_updates.argtypes = [ctx_p, C.c_int, dbl_p]
     for name, argtypes in (list(POST_PROTOTYPES.items()) + list(ADAPT_PROTOTYPES.items())
                            + list(SEARCH_PROTOTYPES.items()) + list(PREP_PROTOTYPES.items())
-                           + list(PRIOR_PROTOTYPES.items())):
+                           + list(PRIOR_PROTOTYPES.items()) + list(HIST_PROTOTYPES.items())):
         getattr(lib, name).argtypes = [ctx_p] + argtypes
     for name in SYMBOLS:
         fn = getattr(lib, name)
@@ -682,6 +692,43 @@ class Engine(object):
 
     def post_end(self):
         _check(self._lib.d3d_post_end(self._ctx))
+
+    # -- posterior histograms -----------------------------------------------------
+    def hist_begin(self, pilot=200, span=6.0):
+        """Allocate the per-spaxel histograms of (a, c, w, F) (include/deconv3d_hip.h:
+        d3d_hist_begin) and start the moments afresh: their first ``pilot`` samples freeze every
+        range at mean +- ``span`` standard deviations (clipped to the bounds of mh_config), every
+        later sample is binned.  Needs post_begin and mh_config."""
+        _check(self._lib.d3d_hist_begin(self._ctx, int(pilot), float(span)))
+
+    def hist_count(self):
+        n = C.c_int64(0)
+        _check(self._lib.d3d_hist_count(self._ctx, C.byref(n)))
+        return n.value
+
+    def hist_get(self):
+        """(bins (H,W,4,64) uint32, tails (H,W,4,2) uint32 = below | above, range (H,W,4,2) = lo | hi)."""
+        hw4 = self.shape[1:] + (4,)
+        bins = np.empty(hw4 + (64,), dtype=np.uint32)
+        tails = np.empty(hw4 + (2,), dtype=np.uint32)
+        rng = np.empty(hw4 + (2,), dtype=np.float64)
+        u32 = C.POINTER(C.c_uint32)
+        _check(self._lib.d3d_hist_get(self._ctx, bins.ctypes.data_as(u32), tails.ctypes.data_as(u32), _dp(rng)))
+        return bins, tails, rng
+
+    def hist_quantiles(self, qs):
+        """(quantiles (H,W,4,len(qs)), mode (H,W,4), outside (H,W,4)) extracted on the device; 1 to 8
+        ``qs`` inside (0, 1)."""
+        q = np.ascontiguousarray(qs, dtype=np.float64).reshape(-1)
+        hw4 = self.shape[1:] + (4,)
+        quant = np.empty(hw4 + (max(q.size, 1),), dtype=np.float64)
+        mode = np.empty(hw4, dtype=np.float64)
+        outside = np.empty(hw4, dtype=np.float64)
+        _check(self._lib.d3d_hist_quantiles(self._ctx, int(q.size), _dp(q), _dp(quant), _dp(mode), _dp(outside)))
+        return quant, mode, outside
+
+    def hist_end(self):
+        _check(self._lib.d3d_hist_end(self._ctx))
 
     # -- per-spaxel jump scales ---------------------------------------------------
     def adapt_begin(self, target=0.25, window=50, last_sweep=0, gain=2.0, scale_range=(1e-3, 1e3)):

@@ -397,7 +397,17 @@ int build_colour_lists(d3d_ctx *c) {
 
 
 // ---- posterior moments (d3d_post_*) ------------------------------------------------------
+void hist_free(d3d_ctx *c) {
+    if (c->hist_bins) (void)hipFree(c->hist_bins);
+    if (c->hist_tails) (void)hipFree(c->hist_tails);
+    if (c->hist_range) (void)hipFree(c->hist_range);
+    c->hist_bins = c->hist_tails = nullptr;
+    c->hist_range = nullptr;
+    c->hist_on = c->hist_frozen = false;
+}
+
 void post_free(d3d_ctx *c) {
+    hist_free(c);
     for (double *&p : c->post_cube) {
         if (p) (void)hipFree(p);
         p = nullptr;
@@ -454,6 +464,13 @@ int post_reset(d3d_ctx *c) {
     for (double *p : c->post_cube)
         if (p) HIP_TRY(hipMemsetAsync(p, 0, c->cube_elems * sizeof(double), c->stream));
     HIP_TRY(hipMemsetAsync(c->post_map, 0, (size_t)c->HW * 8 * sizeof(double), c->stream));
+    if (c->hist_on) {  // counters zero, ranges not frozen (all bits set: NaN)
+        const size_t nser = (size_t)c->HW * 4;
+        c->hist_frozen = false;
+        HIP_TRY(hipMemsetAsync(c->hist_bins, 0, nser * 64 * sizeof(uint32_t), c->stream));
+        HIP_TRY(hipMemsetAsync(c->hist_tails, 0, nser * 2 * sizeof(uint32_t), c->stream));
+        HIP_TRY(hipMemsetAsync(c->hist_range, 0xff, nser * 2 * sizeof(double), c->stream));
+    }
     return 0;
 }
 
@@ -470,6 +487,14 @@ int d3dh::post_sample(d3d_ctx *c) {
     }
     if (int rc = launch_post_accum(c)) return rc;
     ++c->post_n;
+    if (c->hist_on) {  // d3d_hist_begin: the pilot's last sample freezes the ranges, later ones are binned
+        if (c->post_n == c->hist_pilot) {
+            if (int rc = launch_hist_freeze(c)) return rc;
+            c->hist_frozen = true;
+        } else if (c->hist_frozen) {
+            if (int rc = launch_hist_accum(c)) return rc;
+        }
+    }
     return 0;
 }
 
@@ -721,6 +746,7 @@ int d3d_ctx_destroy(d3d_ctx *c) {
     for (double *p : c->post_cube)
         if (p) (void)hipFree(p);
     if (c->post_map) (void)hipFree(c->post_map);
+    hist_free(c);
     adapt_free(c);
     if (c->prior_part) (void)hipFree(c->prior_part);
     for (hipEvent_t e : c->halo_ev) (void)hipEventDestroy(e);
@@ -1494,6 +1520,90 @@ int d3d_post_end(d3d_ctx *c) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     post_free(c);
+    return D3D_OK;
+}
+
+int d3d_hist_begin(d3d_ctx *c, int64_t pilot, double span) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    NEED(pilot >= 2, D3D_ERR_INVALID, "pilot = %lld: the range needs a standard deviation (>= 2 samples)",
+         (long long)pilot);
+    NEED(std::isfinite(span) && span > 0.0, D3D_ERR_INVALID, "span = %g is not a positive number", span);
+    NEED(c->post_on, D3D_ERR_STATE, "posterior moments not begun (d3d_post_begin)");
+    NEED(c->have_cfg, D3D_ERR_STATE, "bounds not set (d3d_mh_config)");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    hist_free(c);
+    const size_t nser = (size_t)c->HW * 4;
+    hipError_t e = hipMalloc(&c->hist_bins, nser * 64 * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&c->hist_tails, nser * 2 * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&c->hist_range, nser * 2 * sizeof(double));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // the context stays usable for the chain and the moments
+        hist_free(c);
+        return fail(D3D_ERR_HIP, "posterior histograms (%zu bytes): %s", nser * (66 * sizeof(uint32_t) + 16),
+                    hipGetErrorString(e));
+    }
+    c->hist_on = true;
+    c->hist_pilot = pilot;
+    c->hist_span = span;
+    return post_reset(c);  // the pilot is the moments' first samples
+}
+
+int d3d_hist_count(d3d_ctx *c, int64_t *n) {
+    NEED(c && n, D3D_ERR_INVALID, "NULL argument");
+    *n = c->hist_on ? std::max<int64_t>(c->post_n - c->hist_pilot, 0) : 0;
+    return D3D_OK;
+}
+
+int d3d_hist_get(d3d_ctx *c, uint32_t *bins, uint32_t *tails, double *range) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    NEED(c->hist_on, D3D_ERR_STATE, "posterior histograms not begun (d3d_hist_begin)");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t nser = (size_t)c->HW * 4;
+    if (bins)
+        HIP_TRY(hipMemcpyAsync(bins, c->hist_bins, nser * 64 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (tails)
+        HIP_TRY(hipMemcpyAsync(tails, c->hist_tails, nser * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (range)
+        HIP_TRY(hipMemcpyAsync(range, c->hist_range, nser * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return D3D_OK;
+}
+
+int d3d_hist_quantiles(d3d_ctx *c, int n_q, const double *q, double *quantiles, double *mode, double *outside) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    NEED(n_q >= 1 && n_q <= 8, D3D_ERR_INVALID, "n_q = %d: 1 to 8 quantiles a call", n_q);
+    NEED(q, D3D_ERR_INVALID, "q is NULL");
+    for (int j = 0; j < n_q; ++j)
+        NEED(q[j] > 0.0 && q[j] < 1.0, D3D_ERR_INVALID, "q[%d] = %g lies outside (0, 1)", j, q[j]);
+    NEED(c->hist_on, D3D_ERR_STATE, "posterior histograms not begun (d3d_hist_begin)");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t nser = (size_t)c->HW * 4;
+    double *buf = nullptr;  // quantiles [nser][n_q] | mode [nser] | outside [nser]
+    HIP_TRY(hipMalloc(&buf, nser * (size_t)(n_q + 2) * sizeof(double)));
+    double *d_mode = buf + nser * (size_t)n_q, *d_out = d_mode + nser;
+    int rc = launch_hist_quantiles(c, n_q, q, quantiles ? buf : nullptr, mode ? d_mode : nullptr,
+                                   outside ? d_out : nullptr);
+    hipError_t e = hipSuccess;
+    if (!rc && quantiles)
+        e = hipMemcpyAsync(quantiles, buf, nser * (size_t)n_q * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (!rc && e == hipSuccess && mode)
+        e = hipMemcpyAsync(mode, d_mode, nser * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (!rc && e == hipSuccess && outside)
+        e = hipMemcpyAsync(outside, d_out, nser * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    (void)hipFree(buf);
+    if (rc) return rc;
+    HIP_TRY(e);
+    HIP_TRY(es);
+    return D3D_OK;
+}
+
+int d3d_hist_end(d3d_ctx *c) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    hist_free(c);
     return D3D_OK;
 }
 

@@ -275,6 +275,16 @@ struct d3d_ctx {
     int64_t post_n = 0;            // samples accumulated
     int post_first = 0, post_every = 0;  // d3d_post_schedule (every == 0: none)
     int post_nt = 0;               // option post_nt = 1: the accumulators' loads and stores non-temporal
+    // posterior histograms (d3d_hist_*): per spaxel and per quantity of post_map 64 equal bins and
+    // two tail counters over a range frozen from the moments of the first hist_pilot samples
+    // (k_hist_freeze); every later sample is binned (k_hist_accum).  Nothing is allocated before
+    // d3d_hist_begin.
+    bool hist_on = false, hist_frozen = false;
+    int64_t hist_pilot = 0;        // samples that feed the moments only
+    double hist_span = 0.0;        // the range is mean +- span * sd of the pilot, clipped to the bounds
+    uint32_t *hist_bins = nullptr;   // [HW*4][64]
+    uint32_t *hist_tails = nullptr;  // [HW*4][2]: below | above
+    double *hist_range = nullptr;    // [HW*4][2]: lo | hi (NaN: not frozen yet, or masked)
     // per-spaxel jump scales (d3d_adapt_*): every `adapt_window` sweeps of d3d_mh_sweeps each
     // spaxel's scale moves towards the target acceptance rate (k_mh_adapt), up to sweep
     // adapt_last; the counters then go on counting.  Nothing is allocated before d3d_adapt_begin.
@@ -319,6 +329,12 @@ int forward_into(d3d_ctx *c, double *dst, bool resid);
 // d3d_post.hip: one sample (the chain state; SLOT_SIM holds its convolved cube when that moment
 // is on) into the running moments, as sample number c->post_n + 1
 int launch_post_accum(d3d_ctx *c);
+// d3d_post.hip, posterior histograms: the ranges from the moments as they are (c->post_n samples);
+// the chain state into its bins; quantiles, mode and outside share of every histogram into device
+// buffers [HW*4][n_q], [HW*4], [HW*4] (any may be NULL)
+int launch_hist_freeze(d3d_ctx *c);
+int launch_hist_accum(d3d_ctx *c);
+int launch_hist_quantiles(d3d_ctx *c, int n_q, const double *q, double *quantiles, double *mode, double *outside);
 // d3d_mh.hip: after sweep `s` of a d3d_mh_sweeps call (d3d_adapt_begin): the sweep is counted and,
 // where it fills a window at or before the last adapted sweep, the jump scales take a step
 int adapt_after_sweep(d3d_ctx *c, int s);

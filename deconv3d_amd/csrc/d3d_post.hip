@@ -1,6 +1,8 @@
 // Posterior moments on the device (d3d_post_*): running mean and sum of squared deviations of
 // the chain's samples -- clean cube, LSF (x) FSF convolved cube, (a, c, w, F) map -- updated
-// between sweeps without a host round trip.  gfx950 only.
+// between sweeps without a host round trip.  Posterior histograms (d3d_hist_*): per spaxel and per
+// quantity of the map 64 equal bins over a range frozen from a pilot, filled between sweeps, and
+// their quantile / mode / outside maps.  gfx950 only.
 #include "d3d_ctx.h"
 
 namespace d3d {
@@ -99,6 +101,144 @@ static __global__ __launch_bounds__(256) void k_post_accum(PostArgs A) {
     }
 }
 
+// ---- posterior histograms -----------------------------------------------
+// A SERIES is one (spaxel, quantity) pair, i = spaxel * 4 + k, k over (a, c, w, F) as in the map.
+constexpr int HIST_BINS = 64;  // one bin per lane of a wavefront (k_hist_quantiles)
+
+struct HistArgs {
+    long nser;              // HW * 4
+    double pilot_m1;        // pilot - 1
+    double span;
+    double flux_k;
+    double L[4], U[4];      // bounds of (a, c, w, F)
+    const double *params;
+    const uint8_t *mask;
+    const double *map_mean, *map_m2;
+    double *range;          // [nser][2]
+    uint32_t *bins;         // [nser][64]
+    uint32_t *tails;        // [nser][2]
+};
+
+// One thread per series: lo = max(mean - span sd, L), hi = min(mean + span sd, U) of the pilot's
+// moments; a pilot that did not move (or moved to one side of a bound only) takes the whole of
+// [L, U].  Masked spaxels keep NaN, which k_hist_accum never counts.  Plain IEEE operations in
+// this order, as welford.
+static __global__ __launch_bounds__(256) void k_hist_freeze(HistArgs A) {
+#pragma clang fp contract(off)
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= A.nser) return;
+    const int k = (int)(i & 3);
+    const double L = k == 0 ? A.L[0] : k == 1 ? A.L[1] : k == 2 ? A.L[2] : A.L[3];
+    const double U = k == 0 ? A.U[0] : k == 1 ? A.U[1] : k == 2 ? A.U[2] : A.U[3];
+    double lo = __builtin_nan(""), hi = __builtin_nan("");
+    if (A.mask[i >> 2]) {
+        const double mean = A.map_mean[i];
+        const double sd = sqrt(A.map_m2[i] / A.pilot_m1);
+        const double half = A.span * sd;
+        lo = mean - half;
+        hi = mean + half;
+        lo = lo > L ? lo : L;
+        hi = hi < U ? hi : U;
+        if (!(sd > 0.0) || !(hi > lo)) {
+            lo = L;
+            hi = U;
+        }
+    }
+    A.range[2 * i] = lo;
+    A.range[2 * i + 1] = hi;
+}
+
+// One thread per series: the sample's bin, and a plain read-modify-write of that one counter -- the
+// series is this thread's alone and the launches of a stream are ordered, so no atomics.  F is
+// k_post_accum's expression.
+static __global__ __launch_bounds__(256) void k_hist_accum(HistArgs A) {
+#pragma clang fp contract(off)
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= A.nser) return;
+    const double lo = A.range[2 * i], hi = A.range[2 * i + 1];
+    if (!(hi > lo)) return;  // masked (NaN), or bounds that coincide
+    const long sp = i >> 2;
+    const int k = (int)(i & 3);
+    const double a = A.params[sp * 3 + 0], c = A.params[sp * 3 + 1], w = A.params[sp * 3 + 2];
+    const double v = k == 0 ? a : k == 1 ? c : k == 2 ? w : a * w * A.flux_k;
+    const double b = floor((v - lo) * ((double)HIST_BINS / (hi - lo)));
+    uint32_t *p;
+    if (b < 0.0)
+        p = A.tails + 2 * i;
+    else if (b >= (double)HIST_BINS)
+        p = A.tails + 2 * i + 1;
+    else if (b >= 0.0)
+        p = A.bins + (size_t)HIST_BINS * i + (int)b;
+    else
+        return;  // a NaN sample is not counted
+    *p += 1u;
+}
+
+struct HistQArgs {
+    long nser;
+    int n_q;
+    double q[8];
+    const double *range;
+    const uint32_t *bins, *tails;
+    double *quantiles, *mode, *outside;  // [nser][n_q], [nser], [nser]; NULL: not wanted
+};
+
+// One wavefront per series, lane = bin: the 64 counters in one coalesced 256-byte load, an
+// inclusive scan by shuffles, the crossing bin of each quantile from the 64-bit ballot of
+// "below + cum >= q n", the mode by a butterfly arg-max (ties to the lower bin).  Every value the
+// branches test is the same in all lanes, so the shuffles inside them see the whole wavefront.
+static __global__ __launch_bounds__(256) void k_hist_quantiles(HistQArgs A) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= A.nser) return;
+    const uint32_t cnt = A.bins[(size_t)HIST_BINS * i + lane];
+    uint32_t cum = cnt;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(cum, d);
+        if (lane >= d) cum += up;
+    }
+    const uint32_t inside = __shfl(cum, 63);
+    const uint64_t below = A.tails[2 * i], above = A.tails[2 * i + 1];
+    const uint64_t n = below + inside + above;
+    const double lo = A.range[2 * i], hi = A.range[2 * i + 1];
+    const double width = (hi - lo) / (double)HIST_BINS;
+    const double nan = __builtin_nan("");
+    for (int j = 0; j < A.n_q; ++j) {
+        double r = nan;
+        if (n) {
+            const double t = A.q[j] * (double)n;
+            if (t <= (double)below) {
+                r = lo;
+            } else if (t > (double)(n - above)) {
+                r = hi;
+            } else {
+                const unsigned long long crossed = __ballot((double)(below + cum) >= t);
+                const int b = __ffsll(crossed) - 1;
+                const uint32_t cum_b = __shfl(cum, b), cnt_b = __shfl(cnt, b);
+                r = lo + ((double)b + (t - (double)(below + cum_b - cnt_b)) / (double)cnt_b) * width;
+            }
+        }
+        if (A.quantiles && lane == j) A.quantiles[i * A.n_q + j] = r;
+    }
+    uint32_t best = cnt;
+    int best_bin = lane;
+#pragma unroll
+    for (int d = 32; d; d >>= 1) {
+        const uint32_t oc = __shfl_xor(best, d);
+        const int ob = __shfl_xor(best_bin, d);
+        if (oc > best || (oc == best && ob < best_bin)) {
+            best = oc;
+            best_bin = ob;
+        }
+    }
+    if (lane == 0) {
+        if (A.mode) A.mode[i] = inside ? lo + ((double)best_bin + 0.5) * width : nan;
+        if (A.outside) A.outside[i] = n ? (double)(below + above) / (double)n : nan;
+    }
+}
+
 }  // namespace d3d
 
 namespace d3dh {
@@ -111,6 +251,13 @@ static int launch_post_t(d3d_ctx *c, const d3d::PostArgs &A) {
     return 0;
 }
 
+// F = a w flux_k
+static double flux_factor(const d3d_ctx *c) {
+    double ratios = 0.0;
+    for (int k = 0; k < c->line.K; ++k) ratios += c->line.ratio[k];
+    return std::sqrt(2.0 * M_PI) * ratios;
+}
+
 int launch_post_accum(d3d_ctx *c) {
     d3d::PostArgs A;
     A.D = c->D;
@@ -118,9 +265,7 @@ int launch_post_accum(d3d_ctx *c) {
     A.HL = c->HL;
     A.nspax = c->HW;
     A.n = (double)(c->post_n + 1);
-    double ratios = 0.0;
-    for (int k = 0; k < c->line.K; ++k) ratios += c->line.ratio[k];
-    A.flux_k = std::sqrt(2.0 * M_PI) * ratios;
+    A.flux_k = flux_factor(c);
     A.params = c->params;
     A.mask = c->mask;
     A.sim = c->slot[D3D_SLOT_SIM];
@@ -135,6 +280,58 @@ int launch_post_accum(d3d_ctx *c) {
     if (c->line.K > 1)
         return c->post_nt ? launch_post_t<true, true>(c, A) : launch_post_t<true, false>(c, A);
     return c->post_nt ? launch_post_t<false, true>(c, A) : launch_post_t<false, false>(c, A);
+}
+
+static d3d::HistArgs hist_args(const d3d_ctx *c) {
+    d3d::HistArgs A;
+    A.nser = c->HW * 4;
+    A.pilot_m1 = (double)(c->hist_pilot - 1);
+    A.span = c->hist_span;
+    A.flux_k = flux_factor(c);
+    for (int k = 0; k < 3; ++k) {
+        A.L[k] = c->min_b[k];
+        A.U[k] = c->max_b[k];
+    }
+    A.L[3] = c->min_b[0] * c->min_b[2] * A.flux_k;
+    A.U[3] = c->max_b[0] * c->max_b[2] * A.flux_k;
+    A.params = c->params;
+    A.mask = c->mask;
+    A.map_mean = c->post_map;
+    A.map_m2 = c->post_map + (size_t)c->HW * 4;
+    A.range = c->hist_range;
+    A.bins = c->hist_bins;
+    A.tails = c->hist_tails;
+    return A;
+}
+
+int launch_hist_freeze(d3d_ctx *c) {
+    const d3d::HistArgs A = hist_args(c);
+    hipLaunchKernelGGL(d3d::k_hist_freeze, dim3((unsigned)((A.nser + 255) / 256)), dim3(256), 0, c->stream, A);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_hist_accum(d3d_ctx *c) {
+    const d3d::HistArgs A = hist_args(c);
+    hipLaunchKernelGGL(d3d::k_hist_accum, dim3((unsigned)((A.nser + 255) / 256)), dim3(256), 0, c->stream, A);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_hist_quantiles(d3d_ctx *c, int n_q, const double *q, double *quantiles, double *mode, double *outside) {
+    d3d::HistQArgs A;
+    A.nser = c->HW * 4;
+    A.n_q = n_q;
+    for (int j = 0; j < 8; ++j) A.q[j] = j < n_q ? q[j] : 0.5;
+    A.range = c->hist_range;
+    A.bins = c->hist_bins;
+    A.tails = c->hist_tails;
+    A.quantiles = quantiles;
+    A.mode = mode;
+    A.outside = outside;
+    hipLaunchKernelGGL(d3d::k_hist_quantiles, dim3((unsigned)((A.nser + 3) / 4)), dim3(256), 0, c->stream, A);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 }  // namespace d3dh

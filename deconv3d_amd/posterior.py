@@ -10,6 +10,10 @@ neighbours trade flux through the FSF -- every sample fits the data while the cu
 map do not; the estimator that is right there is the mean of the cubes.  This module holds the
 host side: lazily downloaded moments, their standard deviations, and the pooling of several
 chains' moments (pure numpy).
+
+The per-spaxel ``(a, c, w, F)`` are heavy-tailed, so mean and standard deviation summarise them
+badly; :class:`PosteriorHistograms` reads medians, intervals and modes off the per-spaxel
+histograms the device keeps beside the moments (d3d_hist_*; ``Run(posterior_histograms=...)``).
 """
 from __future__ import annotations
 
@@ -80,16 +84,19 @@ class PosteriorMoments(object):
     every array is NaN.
     """
 
-    def __init__(self, count, fetch, template=None):
+    def __init__(self, count, fetch, template=None, histograms=None):
         self.count = int(count)
         self._fetch = fetch
         self._template = template
         self._cache = {}
+        self.histograms = histograms    # a PosteriorHistograms, or None
 
     @classmethod
-    def from_engine(cls, engine, template=None):
-        """The moments a device context holds now (downloaded on first access)."""
-        return cls(engine.post_count(), engine.post_get, template)
+    def from_engine(cls, engine, template=None, histograms=False):
+        """The moments a device context holds now (downloaded on first access); ``histograms``:
+        with the context's histograms (hist_begin) as ``.histograms``."""
+        return cls(engine.post_count(), engine.post_get, template,
+                   PosteriorHistograms.from_engine(engine) if histograms else None)
 
     def moments(self, which):
         """``(count, mean, M2)`` as :func:`pool` takes them."""
@@ -163,6 +170,116 @@ class PosteriorMoments(object):
         np.savez("%s_posterior_parameters.npz" % prefix, count=self.count,
                  parameters_mean=self.parameters_mean, parameters_std=self.parameters_std,
                  flux_mean=self.flux_mean, flux_std=self.flux_std)
+
+
+class PosteriorHistograms(object):
+    """
+    The histograms of one chain's ``(a, c, w, F)`` samples after the pilot: per unmasked spaxel
+    and quantity 64 equal bins over a range frozen at the pilot's mean +- span standard deviations
+    (clipped to the model's bounds), and two tail counters for what fell outside.  Everything is
+    (H, W, 4) in the order a, c, w, F and NaN where masked or while ``count == 0``.
+
+    ``count``: samples in every histogram.  ``quantiles(qs)``: (H, W, 4, len(qs)), extracted on
+    the device, linear inside the crossing bin -- within one bin width ``(hi - lo) / 64`` of the
+    sample quantile while it lies inside the range, else the range's end.  ``median``;
+    ``interval(0.68)``: the central interval ``(lo, hi)``; ``mode``: the centre of the fullest
+    bin; ``outside``: the share of the samples beyond the range -- a mode the pilot never visited
+    is counted there, not resolved: read a spaxel with a large share off the chain instead.
+    ``counts`` (H, W, 4, 64), ``tails`` (H, W, 4, 2: below, above) and ``range`` (H, W, 4, 2: lo,
+    hi) are the downloaded counters.  Device results are fetched on first access and kept.
+    """
+
+    def __init__(self, count, get, quantiles, pilot=None, span=None):
+        self.count = int(count)
+        self.pilot, self.span = pilot, span
+        self._get = get
+        self._quantiles = quantiles
+        self._raw = None
+        self._cache = {}
+
+    @classmethod
+    def from_engine(cls, engine, pilot=None, span=None):
+        return cls(engine.hist_count(), engine.hist_get, engine.hist_quantiles, pilot, span)
+
+    def _counters(self):
+        if self._raw is None:
+            self._raw = self._get()
+        return self._raw
+
+    counts = property(lambda self: self._counters()[0])
+    tails = property(lambda self: self._counters()[1])
+    range = property(lambda self: self._counters()[2])
+
+    def _extract(self, qs):
+        qs = tuple(float(q) for q in np.atleast_1d(qs))
+        if not qs:
+            raise ValueError("no quantile asked for")
+        for q in qs:
+            if not 0. < q < 1.:
+                raise ValueError("quantile %r lies outside (0, 1)" % q)
+        if qs not in self._cache:
+            parts = [self._quantiles(qs[i:i + 8]) for i in range(0, len(qs), 8)]
+            self._cache[qs] = (np.concatenate([p[0] for p in parts], axis=-1),) + tuple(parts[0][1:])
+        return self._cache[qs]
+
+    def quantiles(self, qs):
+        return self._extract(qs)[0]
+
+    @property
+    def median(self):
+        return self._extract((0.5,))[0][..., 0]
+
+    def interval(self, mass=0.68):
+        """The central interval holding ``mass`` of the samples: ``(lo, hi)``."""
+        if not 0. < mass < 1.:
+            raise ValueError("interval(%r): a mass inside (0, 1)" % mass)
+        both = self._extract((0.5 - 0.5 * mass, 0.5 + 0.5 * mass))[0]
+        return both[..., 0], both[..., 1]
+
+    @property
+    def mode(self):
+        return self._extract((0.5,))[1]
+
+    @property
+    def outside(self):
+        return self._extract((0.5,))[2]
+
+    def save(self, prefix):
+        """``<prefix>_posterior_histograms.npz``: count, pilot, span, counts, tails, range, median,
+        the 68 % interval (lo68, hi68), mode and outside."""
+        lo68, hi68 = self.interval(0.68)
+        np.savez("%s_posterior_histograms.npz" % prefix, count=self.count,
+                 pilot=-1 if self.pilot is None else self.pilot,
+                 span=np.nan if self.span is None else self.span,
+                 counts=self.counts, tails=self.tails, range=self.range, median=self.median,
+                 lo68=lo68, hi68=hi68, mode=self.mode, outside=self.outside)
+
+
+def check_histograms(keyword, burn_in):
+    """``Run``'s ``posterior_histograms``: None / False (off: returns None), True, or a dict with
+    any of ``pilot`` (integer >= 2) and ``span`` (finite, positive); returns
+    ``dict(pilot=200, span=6.0)`` updated with it.  Needs ``posterior_burn_in`` (ValueError)."""
+    if keyword is None or keyword is False:
+        return None
+    cfg = dict(pilot=200, span=6.0)
+    if keyword is not True:
+        if not isinstance(keyword, dict):
+            raise ValueError("posterior_histograms= MUST be None, True or a dict(pilot=, span=), got %r"
+                             % (keyword,))
+        unknown = sorted(set(keyword) - set(cfg))
+        if unknown:
+            raise ValueError("posterior_histograms=: unknown key(s) %s (pilot, span)" % unknown)
+        cfg.update(keyword)
+    pilot, span = cfg["pilot"], cfg["span"]
+    if isinstance(pilot, bool) or not isinstance(pilot, (int, np.integer)) or pilot < 2:
+        raise ValueError("posterior_histograms=: pilot MUST be an integer >= 2, got %r" % (pilot,))
+    if isinstance(span, bool) or not isinstance(span, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(span) or not span > 0:
+        raise ValueError("posterior_histograms=: span MUST be a finite positive number, got %r" % (span,))
+    if burn_in is None:
+        raise ValueError("posterior_histograms= needs posterior_burn_in=: the histograms count the "
+                         "samples the posterior moments take")
+    return dict(pilot=int(pilot), span=float(span))
 
 
 def pooled(parts, template=None):

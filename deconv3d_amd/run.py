@@ -100,6 +100,21 @@ class Run:
     not part of a checkpoint: a ``resume_state=`` run starts fresh ones, scheduled in this
     segment's sweep numbering.  Costs four more cubes of device memory per chain.
 
+    ``posterior_histograms=True`` (or ``dict(pilot=200, span=6.0)``; default ``None``: off, nothing
+    allocated or launched, the chain is bit for bit what it is without the keyword; needs
+    ``posterior_burn_in``) keeps, on the device, a 64-bin histogram of every unmasked spaxel's
+    ``a``, ``c``, ``w`` and ``F`` beside the moments: the first ``pilot`` accumulated samples
+    freeze each range at their mean +- ``span`` standard deviations, clipped to the model's
+    bounds, and every later accumulated sample is binned, whatever ``keep_one_in`` is.
+    ``run.posterior.histograms`` is a :class:`deconv3d_amd.posterior.PosteriorHistograms`
+    (``count``, ``median``, ``interval(0.68)``, ``quantiles(qs)``, ``mode``, ``outside``,
+    ``counts``, ``tails``, ``range``, ``save(prefix)``) whose maps are extracted on the device;
+    ``outside`` is the share of the samples beyond the frozen range, where a mode the pilot never
+    visited ends up.  With ``chains=R`` every chain keeps its own,
+    ``run.posteriors[r].histograms``, and the pooled ``run.posterior.histograms`` is ``None``
+    (the chains' ranges differ).  A run that cannot accumulate more than ``pilot`` samples logs a
+    warning.  Not part of a checkpoint, like the moments.  Costs 1120 bytes per spaxel and chain.
+
     ``adapt_sweeps=N`` (default ``None``: off, nothing allocated or launched, the chain is bit for
     bit what it is without the keyword) gives every spaxel its own multiplicative jump scale: the
     reference proposes all of them with the one ``jump_amplitude`` (lib/run.py:251-262, 570-579),
@@ -175,6 +190,7 @@ class Run:
         chains=1,
         posterior_burn_in=None,
         posterior_every=1,
+        posterior_histograms=None,
         adapt_sweeps=None,
         adapt_window=50,
         adapt_target=0.25,
@@ -190,6 +206,7 @@ class Run:
         if posterior_burn_in is not None:     # (before anything else: no device work yet)
             posterior_burn_in, posterior_every = _posterior.check_schedule(posterior_burn_in,
                                                                            posterior_every)
+        hist_cfg = _posterior.check_histograms(posterior_histograms, posterior_burn_in)
         adapt_cfg = None
         if adapt_sweeps is not None:
             adapt_cfg = _adapt.check_keywords(adapt_sweeps, adapt_window, adapt_target, adapt_gain,
@@ -492,6 +509,8 @@ class Run:
                 if posterior_burn_in is not None:
                     eng.post_begin()
                     eng.post_schedule(posterior_burn_in, posterior_every)
+                    if hist_cfg is not None:
+                        eng.hist_begin(hist_cfg["pilot"], hist_cfg["span"])
                 if adapt_cfg is not None:
                     # (the last adapted sweep in the numbering of the whole run: a resumed
                     # segment counts from its sweep origin)
@@ -507,6 +526,16 @@ class Run:
             else:
                 for hc in self._host_chains:
                     hc.set_sweep_origin(self.sweep_origin)
+        if hist_cfg is not None:
+            reachable = len(range(posterior_burn_in, self.max_iterations, posterior_every))
+            if reachable <= hist_cfg["pilot"]:
+                self.logger.warning("posterior_histograms=: max_iterations=%d leaves %d accumulated sweeps, "
+                                    "none beyond the pilot of %d; the histograms will hold no sample"
+                                    % (self.max_iterations, reachable, hist_cfg["pilot"]))
+            if n_chains > 1:
+                self.logger.info("posterior_histograms=: every chain freezes its own ranges; "
+                                 "run.posteriors[r].histograms are per chain and the pooled "
+                                 "run.posterior.histograms is None")
         self.logger.info("Iteration #1")
         if host_chain is None:
             for eng in self.engines:
@@ -617,8 +646,11 @@ class Run:
         # posterior moments of the samples' cubes (still on the device: fetched on access)
         self.posteriors, self.posterior = None, None
         if posterior_burn_in is not None:
-            self.posteriors = [_posterior.PosteriorMoments.from_engine(eng, self.cube)
+            self.posteriors = [_posterior.PosteriorMoments.from_engine(eng, self.cube, hist_cfg is not None)
                                for eng in self.engines]
+            if hist_cfg is not None:
+                for pm in self.posteriors:
+                    pm.histograms.pilot, pm.histograms.span = hist_cfg["pilot"], hist_cfg["span"]
             self.posterior = self.posteriors[0] if n_chains == 1 else \
                 _posterior.pooled(self.posteriors, self.cube)
             if self.posterior.count == 0:

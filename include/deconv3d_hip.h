@@ -281,6 +281,43 @@ int d3d_post_get(d3d_ctx *ctx, int which, double *mean, double *m2);
 /* Free the accumulators and drop the schedule (d3d_ctx_destroy does it too). */
 int d3d_post_end(d3d_ctx *ctx);
 
+/* ---- posterior histograms ------------------------------------------------- */
+/* The moments summarise a spaxel's (a, c, w, F) badly where they are heavy-tailed or bimodal, and
+ * the reference can read a median or an interval only off the saved chain (lib/run.py:447-451,
+ * 581-593).  These entries keep, per unmasked spaxel and per quantity of the d3d_post_get map, a
+ * histogram of 64 equal bins and two tail counters (below, above), all uint32, filled on the device
+ * from every sample the moments take after their first `pilot`:
+ *   range, frozen once, right after sample number pilot:  sd = sqrt(M2 / (pilot - 1)),
+ *     lo = max(mean - span sd, L), hi = min(mean + span sd, U), with L, U the bounds of
+ *     d3d_mh_config for a, c, w and min_a min_w flux_k, max_a max_w flux_k for F; when !(sd > 0)
+ *     or !(hi > lo): lo = L, hi = U; when still !(hi > lo) the series is never counted.  Masked
+ *     spaxels are never counted and their range is NaN, as is every range before the freeze;
+ *   counting:  b = floor((v - lo) * (64 / (hi - lo))); b < 0 -> below, b >= 64 -> above, else bin b;
+ *   quantile q:  n = below + sum(bins) + above, t = q n; NaN when n == 0; lo when t <= below; hi
+ *     when t > n - above; else, b the first bin with below + cum[b] >= t,
+ *     lo + (b + (t - (below + cum[b] - cnt[b])) / cnt[b]) * ((hi - lo) / 64);
+ *   mode:  lo + (b* + 0.5) * ((hi - lo) / 64), b* the lowest bin with the largest count; NaN when
+ *     every bin is empty;
+ *   outside:  (below + above) / n, the share of the samples the frozen range missed -- a second
+ *     mode the pilot never visited is counted here, not resolved.
+ * Every step is a plain IEEE double operation in the written order.  1120 bytes per spaxel. */
+
+/* Allocate the counters (needs d3d_post_begin and d3d_mh_config: D3D_ERR_STATE) and start the
+ * moments afresh (count 0): their first `pilot` samples set the ranges.  pilot < 2, or a span that
+ * is not finite and positive: D3D_ERR_INVALID.  An allocation failure is D3D_ERR_HIP, frees what it
+ * got and leaves the ctx usable.  Whatever resets the moments zeroes the counters and unfreezes the
+ * ranges; d3d_post_begin and d3d_post_end free them. */
+int d3d_hist_begin(d3d_ctx *ctx, int64_t pilot, double span);
+/* *n = samples counted into every histogram: max(moments' count - pilot, 0). */
+int d3d_hist_count(d3d_ctx *ctx, int64_t *n);
+/* bins (H,W,4,64), tails (H,W,4,2) = below | above, range (H,W,4,2) = lo | hi.  Any may be NULL. */
+int d3d_hist_get(d3d_ctx *ctx, uint32_t *bins, uint32_t *tails, double *range);
+/* quantiles (H,W,4,n_q) for q[0..n_q), mode (H,W,4) and outside (H,W,4), extracted on the device
+ * (k_hist_quantiles).  Outputs may be NULL.  n_q outside 1..8 or a q outside (0,1): D3D_ERR_INVALID. */
+int d3d_hist_quantiles(d3d_ctx *ctx, int n_q, const double *q, double *quantiles, double *mode, double *outside);
+/* Free the counters; the moments go on. */
+int d3d_hist_end(d3d_ctx *ctx);
+
 /* ---- matched-filter line search ------------------------------------------ */
 /* The reference starts every spaxel from a uniform draw inside the bounds (lib/run.py:310-314) and
  * its only mask helper thresholds the spectrally summed flux (lib/masks.py:17-29).  This entry
