@@ -29,7 +29,7 @@ SYMBOLS = [
     "d3d_convolve_slots", "d3d_stage_upload", "d3d_stage_convolve", "d3d_stage_download",
     "d3d_mh_config", "d3d_mh_set_sweep_origin", "d3d_window_stats",
     "d3d_mh_sweeps", "d3d_mh_colour_lines", "d3d_get_dlog", "d3d_variance_is_uniform", "d3d_mh_layers",
-    "d3d_colour_count", "d3d_rtnorm",
+    "d3d_colour_count", "d3d_rtnorm", "d3d_philox",
     "d3d_set_tile", "d3d_set_parts", "d3d_mh_phase", "d3d_mh_sweeps_batch", "d3d_mh_accepted", "d3d_flush",
     "d3d_halo_plan", "d3d_comm_unique_id", "d3d_comm_init", "d3d_comm_destroy", "d3d_comm_info",
     "d3d_halo_time",
@@ -175,6 +175,8 @@ def load():
                                         dbl_p, C.c_int, dbl_p]
     lib.d3d_colour_count.argtypes = [ctx_p, C.c_int, C.POINTER(C.c_int)]
     lib.d3d_rtnorm.argtypes = [ctx_p, C.c_long] + [C.c_double] * 4 + [C.c_uint64, C.c_int, dbl_p]
+    u32_p = C.POINTER(C.c_uint32)
+    lib.d3d_philox.argtypes = [ctx_p, C.c_long, u32_p, u32_p, u32_p, dbl_p]
     lib.d3d_set_tile.argtypes = [ctx_p] + [C.c_int] * 7
     int_p = C.POINTER(C.c_int)
     lib.d3d_set_parts.argtypes = [ctx_p, C.c_int, int_p, int_p]
@@ -552,6 +554,24 @@ class Engine(object):
                                     float(sigma), C.c_uint64(int(seed) & (2 ** 64 - 1)),
                                     1 if wave_mode else 0, _dp(out)))
         return out
+
+    def philox(self, counters, keys):
+        """Test hook (d3d_philox): the device's Philox4x32-10 and its uniforms for
+        ``counters`` (n,4) and ``keys`` (n,2), uint32.  Returns (words (n,4) uint32,
+        pairs (n,2) float64)."""
+        counters = np.ascontiguousarray(counters, dtype=np.uint32).reshape(-1, 4)
+        keys = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1, 2)
+        n = counters.shape[0]
+        if keys.shape[0] != n:
+            raise ValueError("one key per counter: %d counters, %d keys" % (n, keys.shape[0]))
+        words = np.empty((n, 4), dtype=np.uint32)
+        pairs = np.empty((n, 2), dtype=np.float64)
+        u32 = C.POINTER(C.c_uint32)
+        if n:
+            _check(self._lib.d3d_philox(self._ctx, n, counters.ctypes.data_as(u32),
+                                        keys.ctypes.data_as(u32), words.ctypes.data_as(u32),
+                                        _dp(pairs)))
+        return words, pairs
 
     # -- spatial tiling (deconv3d_amd/tiling.py) ----------------------------
     def set_tile(self, gy0, gx0, Wg, oy0, oy1, ox0, ox1):

@@ -2321,6 +2321,44 @@ int d3d_rtnorm(d3d_ctx *c, long n, double lo, double hi, double mu, double sigma
     return D3D_OK;
 }
 
+int d3d_philox(d3d_ctx *c, long n, const uint32_t *counters, const uint32_t *keys, uint32_t *out_words,
+               double *out_pairs) {
+    NEED(c && counters && keys && out_words && out_pairs, D3D_ERR_INVALID, "NULL argument");
+    NEED(n >= 0 && n <= (1L << 24), D3D_ERR_INVALID, "block count %ld out of range", n);
+    if (n == 0) return D3D_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    // one allocation: pairs [2n] doubles | counters [4n] | keys [2n] | words [4n]
+    const size_t nn = (size_t)n;
+    char *buf = nullptr;
+    HIP_TRY(hipMalloc(&buf, nn * (2 * sizeof(double) + 10 * sizeof(uint32_t))));
+    double *d_pairs = reinterpret_cast<double *>(buf);
+    uint32_t *d_counters = reinterpret_cast<uint32_t *>(buf + nn * 2 * sizeof(double));
+    uint32_t *d_keys = d_counters + 4 * nn;
+    uint32_t *d_words = d_keys + 2 * nn;
+    hipError_t e = hipMemcpyAsync(d_counters, counters, nn * 4 * sizeof(uint32_t), hipMemcpyHostToDevice,
+                                  c->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_keys, keys, nn * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(buf);
+        HIP_TRY(e);
+    }
+    if (int rc = launch_philox(c, n, d_counters, d_keys, d_words, d_pairs)) {
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(buf);
+        return rc;
+    }
+    e = hipMemcpyAsync(out_words, d_words, nn * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(out_pairs, d_pairs, nn * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    (void)hipFree(buf);
+    HIP_TRY(e);
+    HIP_TRY(es);
+    return D3D_OK;
+}
+
 int d3d_colour_count(d3d_ctx *c, int colour, int *count) {
     NEED(c && count, D3D_ERR_INVALID, "NULL argument");
     NEED(c->have_data, D3D_ERR_STATE, "data not set");

@@ -401,6 +401,8 @@ int launch_mh_chain(d3d_ctx *c, int pi, uint32_t sweep0, int n_sweeps);
 int launch_apply_updates(d3d_ctx *c, const d3d::MHArgs &P, const double *rec, int n);
 int launch_rtnorm(d3d_ctx *c, long n, double lo, double hi, double mu, double sigma, uint64_t seed,
                   int wave_mode, double *buf);
+int launch_philox(d3d_ctx *c, long n, const uint32_t *counters, const uint32_t *keys, uint32_t *words,
+                  double *pairs);
 #ifdef D3D_EXPERIMENTS
 int launch_mh_flow(d3d_ctx *c, uint32_t sweep);
 int launch_mh_pair(d3d_ctx *c, int ka, uint32_t sweep);

@@ -4147,6 +4147,23 @@ static __global__ __launch_bounds__(256) void k_rtnorm(long n, double lo, double
     if (!wave_mode || (t & 63) == 0) out[i] = r;
 }
 
+// Test hook: the raw generator of d3d_rng.h for arbitrary counters and keys.  Block i:
+// words[4i..] = philox4x32_10(counters[4i..], keys[2i..]), pairs[2i..] = the two uniforms
+// u64_to_unit makes of them as philox_pair does.
+static __global__ __launch_bounds__(256) void k_philox(long n, const uint32_t *__restrict__ counters,
+                                                 const uint32_t *__restrict__ keys,
+                                                 uint32_t *__restrict__ words,
+                                                 double *__restrict__ pairs) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    uint32_t r[4];
+    philox4x32_10(counters[4 * i], counters[4 * i + 1], counters[4 * i + 2], counters[4 * i + 3],
+                  keys[2 * i], keys[2 * i + 1], r);
+    for (int k = 0; k < 4; ++k) words[4 * i + k] = r[k];
+    pairs[2 * i] = u64_to_unit(((uint64_t)r[1] << 32) | r[0]);
+    pairs[2 * i + 1] = u64_to_unit(((uint64_t)r[3] << 32) | r[2]);
+}
+
 // Apply the pending layers (oldest first) to the whole residual, before anything
 // other than the next colour launch looks at it.
 template <int NT>

@@ -949,4 +949,12 @@ int launch_rtnorm(d3d_ctx *c, long n, double lo, double hi, double mu, double si
     return 0;
 }
 
+int launch_philox(d3d_ctx *c, long n, const uint32_t *counters, const uint32_t *keys, uint32_t *words,
+                  double *pairs) {
+    hipLaunchKernelGGL(d3d::k_philox, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n,
+                       counters, keys, words, pairs);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 }  // namespace d3dh

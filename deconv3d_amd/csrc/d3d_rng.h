@@ -83,9 +83,28 @@ __device__ inline double truncated_standard_normal(double alpha, double beta, U2
     }
     double z;
     if (alpha >= TN_TAIL) {
-        // Robert (1995): translated exponential proposal, rate lam
+        // Robert (1995): translated exponential proposal, rate lam.  An interval narrower
+        // than the proposal's scale (lam * width < 1) would reject nearly every such
+        // proposal for lying beyond beta; there Robert's uniform proposal on [alpha, beta]
+        // is taken, accepted with probability exp((alpha^2 - z^2) / 2) -- 0.63 on average
+        // at lam * width = 1, more below.  (The exponential truncated to the interval would
+        // accept more often still, but its expm1 / log1p take the k_mh_ws kernels from
+        // 77-80 to 83-84 VGPRs, a wavefront per SIMD: profiles/sampler_checks.txt.)  Wider
+        // intervals run the loop they always ran and keep their bits.
         const double lam = 0.5 * (alpha + sqrt(alpha * alpha + 4.0));
         z = alpha;
+        if (lam * (beta - alpha) < 1.0) {
+            for (int it = 0; it < 1000; ++it) {
+                const U2 u = (it == 0) ? u0 : philox_pair(seed, spaxel, sweep, *blk);
+                ++*blk;
+                const double zz = alpha + u.x * (beta - alpha);
+                if (zz <= beta && log(u.y) <= -0.5 * (zz - alpha) * (zz + alpha)) {
+                    z = zz;
+                    break;
+                }
+            }
+            return sign * z;
+        }
         for (int it = 0; it < 1000; ++it) {
             const U2 u = (it == 0) ? u0 : philox_pair(seed, spaxel, sweep, *blk);
             ++*blk;

@@ -230,6 +230,13 @@ int d3d_mh_colour_lines(d3d_ctx *ctx, int sweep, int n, const int *spaxels, cons
  * runs the wavefront-cooperative form of the MH kernel (bit-identical draws). */
 int d3d_rtnorm(d3d_ctx *ctx, long n, double lo, double hi, double mu, double sigma,
                uint64_t seed, int wave_mode, double *out);
+/* Test hook, like d3d_rtnorm: the raw generator under the sampler, for arbitrary
+ * counters and keys.  For block i < n, out_words[4i..4i+3] = Philox4x32-10 of
+ * counters[4i..4i+3] under keys[2i..2i+1] (the chain's layout: counter = {global
+ * spaxel, sweep, block, 0}, key = {seed low, seed high}); out_pairs[2i], [2i+1]
+ * = the two uniforms in [2^-53, 1 - 2^-53] made of words {1,0} and {3,2}. */
+int d3d_philox(d3d_ctx *ctx, long n, const uint32_t *counters, const uint32_t *keys,
+               uint32_t *out_words, double *out_pairs);
 /* Last sweep's log acceptance ratios, (H,W). */
 int d3d_get_dlog(d3d_ctx *ctx, double *out_hw);
 /* *out = 1 when d3d_set_data found one constant variance and no NaN voxel -- the

@@ -527,7 +527,8 @@ def truncated_standard_normal(alpha, beta, draw):
     reference's is Chopin's table method, lib/rtnorm.py:95-224, GPL tables not
     reproduced): inverse CDF on the side of the interval where it is well
     conditioned, Robert's (1995) translated-exponential rejection beyond
-    TN_TAIL sigmas.  Same distribution as ``rtstdnorm``; checked by KS tests
+    TN_TAIL sigmas (his uniform proposal where the interval is narrower than
+    the exponential's scale).  Same distribution as ``rtstdnorm``; checked by KS tests
     against draws of the reference's ``rtnorm``.
     """
     if alpha > beta:
@@ -536,10 +537,19 @@ def truncated_standard_normal(alpha, beta, draw):
         return -truncated_standard_normal(-beta, -alpha, draw)
     if alpha >= TN_TAIL:
         lam = 0.5 * (alpha + math.sqrt(alpha * alpha + 4.0))
+        # an interval narrower than the proposal's scale would reject nearly
+        # every such proposal for lying beyond beta: there Robert's uniform
+        # proposal, accepted with probability exp((alpha^2 - z^2) / 2)
+        narrow = lam * (beta - alpha) < 1.0
         for _ in range(1000):
             u1, u2 = draw()
-            z = alpha - math.log(u1) / lam
-            if z <= beta and math.log(u2) <= -0.5 * (z - lam) ** 2:
+            if narrow:
+                z = alpha + u1 * (beta - alpha)
+                t = (z - alpha) * (z + alpha)
+            else:
+                z = alpha - math.log(u1) / lam
+                t = (z - lam) ** 2
+            if z <= beta and math.log(u2) <= -0.5 * t:
                 return z
         return alpha
     u1, _ = draw()
