@@ -682,6 +682,7 @@ int d3d_ctx_create(d3d_ctx **out, int device, int D, int H, int W, int fh, int f
     CTX_TRY(hipMalloc(&c->hwbuf, (size_t)c->HW * sizeof(double)));
     CTX_TRY(hipMalloc(&c->scal, 16 * sizeof(double)));
     CTX_TRY(hipMalloc(&c->accepted, sizeof(unsigned long long)));
+    CTX_TRY(hipMalloc(&c->acc_map, (size_t)c->HW * sizeof(unsigned)));
     c->spx_cap = (size_t)(H + 2 * fh) * (W + 2 * fw);
     CTX_TRY(hipMalloc(&c->spx, c->spx_cap * sizeof(int4)));
     c->slots_x = (W + fw - 1) / fw;
@@ -719,6 +720,7 @@ int d3d_ctx_create(d3d_ctx **out, int device, int D, int H, int W, int fh, int f
     }
     CTX_TRY(hipMemsetAsync(c->dlog, 0, (size_t)c->HW * sizeof(double), c->stream));
     CTX_TRY(hipMemsetAsync(c->accepted, 0, sizeof(unsigned long long), c->stream));
+    CTX_TRY(hipMemsetAsync(c->acc_map, 0, (size_t)c->HW * sizeof(unsigned), c->stream));
     CTX_TRY(hipMemsetAsync(c->mask, 1, (size_t)c->HW, c->stream));
     CTX_TRY(hipStreamSynchronize(c->stream));
 #undef CTX_TRY
@@ -753,7 +755,7 @@ int d3d_ctx_destroy(d3d_ctx *c) {
     for (int s = 0; s < D3D_SLOT_COUNT; ++s)
         if (c->slot[s]) (void)hipFree(c->slot[s]);
     void *ptrs[] = {c->stage, c->stage2, c->params, c->params_alt, c->mask, c->fsf, c->lsf_shift, c->lsf_weight,
-                    c->dlog, c->hwbuf, c->scal, c->accepted, c->spx, c->gbuf[0], c->gbuf[1], c->gbuf[2], c->gbuf[3],
+                    c->dlog, c->hwbuf, c->scal, c->accepted, c->acc_map, c->spx, c->gbuf[0], c->gbuf[1], c->gbuf[2], c->gbuf[3],
                     c->flow_ent, c->flow_col, c->flow_lat, c->flow_state, c->flow_err, c->pair_state, c->sep_uv,
                     c->lsf_dense, c->prev, c->recbuf, c->idxbuf, c->extbuf, c->fsf_quad, c->fsf_quad_sep,
                     c->chain_cols, c->chain_flags, c->chain_G, c->props, c->z_part, c->z_E, c->ltab, c->ptab};
@@ -1432,6 +1434,7 @@ int d3d_mh_accepted(d3d_ctx *c, int64_t *count, int reset) {
     NEED(c && count, D3D_ERR_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(c->device));
     unsigned long long acc = 0;
+    if (int rc = accepted_collect(c)) return rc;
     HIP_TRY(hipMemcpyAsync(&acc, c->accepted, sizeof acc, hipMemcpyDeviceToHost, c->stream));
     if (reset) HIP_TRY(hipMemsetAsync(c->accepted, 0, sizeof(unsigned long long), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

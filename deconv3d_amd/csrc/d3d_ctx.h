@@ -76,6 +76,7 @@ struct d3d_ctx {
     double *hwbuf = nullptr; // HW scratch (chi2 map)
     double *scal = nullptr;  // small device scalars (8 doubles)
     unsigned long long *accepted = nullptr;
+    unsigned *acc_map = nullptr;  // [HW] accepted moves per spaxel since the last accepted_collect (MHArgs::acc_map)
     int4 *spx = nullptr;  // work lists per (part, colour): real spaxels first, then virtual ones
     std::vector<int> colour_real;  // fh*fw: number of real spaxels of each colour (all parts)
     size_t spx_cap = 0;
@@ -338,6 +339,9 @@ int launch_hist_quantiles(d3d_ctx *c, int n_q, const double *q, double *quantile
 // d3d_mh.hip: after sweep `s` of a d3d_mh_sweeps call (d3d_adapt_begin): the sweep is counted and,
 // where it fills a window at or before the last adapted sweep, the jump scales take a step
 int adapt_after_sweep(d3d_ctx *c, int s);
+// d3d_mh.hip: the accepted moves the decisions left in c->acc_map, added to *c->accepted (on the
+// context's stream); every read of the counter is preceded by it
+int accepted_collect(d3d_ctx *c);
 // d3d_mh.hip: sums of squared neighbour differences of a parameter map on the device over the
 // adjacent pairs of unmasked spaxels, {E_a, E_c, E_w, pairs} (k_prior_energy)
 int prior_energy(d3d_ctx *c, const double *params_dev, double out4[4]);

@@ -1751,6 +1751,7 @@ struct MHChainArgs {  // one chain of a batch: see MHArgs::batch
     // chains of a batch share the kernel instantiation)
     double lam[3];
     int prior;
+    unsigned *acc_map;  // (as MHArgs::acc_map)
 };
 struct MHArgs {
     int D, Dp, HL, H, W, fh, fw, N, ntaps, npos;
@@ -1870,6 +1871,12 @@ struct MHArgs {
     // read `prior` to pick the kernels' PRIOR = true instantiations; the kernels read lam only.
     double lam[3];
     int prior;
+    // Accepted moves, [H*W] by local spaxel index: a decision adds its verdict to ITS spaxel's
+    // counter, and k_accepted_collect totals the map into *accepted where the host reads the
+    // count.  (Every accepted move of a launch added to *accepted itself before: ~700 atomics
+    // on one address per launch at config 3, issued as the windows finish -- they serialise,
+    // and the launch cannot end before the last of them.)
+    unsigned *acc_map;
 };
 
 #ifdef D3D_EXPERIMENTS
@@ -2196,7 +2203,8 @@ __device__ __forceinline__ void mh_decide_core(const MHArgs &P, const MHProposal
         }
         P.dlog[sp] = delta;
         if (P.jacc && !P.ext_lines) P.jacc[sp] += accept ? 1u : 0u;  // (one writer per spaxel and sweep)
-        if (accept) atomicAdd(P.accepted, 1ULL);
+        // (one spaxel, one address: nothing to serialise behind, and no value to wait for)
+        if (accept) atomicAdd(P.acc_map + sp, 1u);
     }
 }
 
@@ -3114,6 +3122,7 @@ __global__ __launch_bounds__(NS + 64) void k_mh_ws(MHArgs P, uint32_t sweep) {
         P.prev = B.prev;
         P.dlog = B.dlog;
         P.accepted = B.accepted;
+        P.acc_map = B.acc_map;
         P.Gcur = B.gbuf[P.b_gcur];
 #pragma unroll
         for (int j = 0; j < MH_LAYERS; ++j) P.lay_G[j] = B.gbuf[P.b_lay_g[j]];
@@ -4561,6 +4570,27 @@ static __global__ __launch_bounds__(256) void k_prior_energy(const double *__res
         }
     }
     prior_block_sum(v, partial + (long)blockIdx.x * 4);
+}
+
+// The accepted moves of the map (MHArgs::acc_map) added to the context's counter; the map starts
+// over.  One workgroup: H*W integers, once per call that reports the count.
+static __global__ __launch_bounds__(1024) void k_accepted_collect(unsigned *__restrict__ map, int n,
+                                                                  unsigned long long *__restrict__ total) {
+    __shared__ unsigned long long part[16];
+    unsigned long long t = 0;
+    for (int i = threadIdx.x; i < n; i += 1024) {
+        t += map[i];
+        map[i] = 0u;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long s = 0;
+        for (int w = 0; w < 16; ++w) s += part[w];
+        *total += s;
+    }
 }
 
 static __global__ __launch_bounds__(256) void k_prior_energy_total(const double *__restrict__ partial,

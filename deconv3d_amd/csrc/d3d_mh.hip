@@ -39,6 +39,7 @@ static void fill_chain_fields(const d3d_ctx *c, A &a) {
     a.prev = c->prev;
     a.dlog = c->dlog;
     a.accepted = c->accepted;
+    a.acc_map = c->acc_map;
     for (int k = 0; k < 3; ++k) {
         a.min_b[k] = c->min_b[k];
         a.max_b[k] = c->max_b[k];
@@ -150,6 +151,13 @@ int prior_energy(d3d_ctx *c, const double *params_dev, double out4[4]) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out4, total, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int accepted_collect(d3d_ctx *c) {
+    hipLaunchKernelGGL(d3d::k_accepted_collect, dim3(1), dim3(1024), 0, c->stream, c->acc_map, (int)c->HW,
+                       c->accepted);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

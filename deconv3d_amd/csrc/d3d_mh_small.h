@@ -148,6 +148,7 @@ __global__ __launch_bounds__(NS) void k_mh_small(MHArgs P, uint32_t sweep) {
         P.prev = B.prev;
         P.dlog = B.dlog;
         P.accepted = B.accepted;
+        P.acc_map = B.acc_map;
         P.Gcur = B.gbuf[P.b_gcur];
 #pragma unroll
         for (int j = 0; j < M; ++j) P.lay_G[j] = B.gbuf[P.b_lay_g[j]];

@@ -76,7 +76,10 @@ int begin_sweeps(d3d_ctx *c, bool zero_accepted) {
     HIP_TRY(hipSetDevice(c->device));
     if (!c->err_valid)
         if (int rc = d3d_residual(c, nullptr)) return rc;
-    if (zero_accepted) HIP_TRY(hipMemsetAsync(c->accepted, 0, sizeof(unsigned long long), c->stream));
+    if (zero_accepted) {
+        HIP_TRY(hipMemsetAsync(c->accepted, 0, sizeof(unsigned long long), c->stream));
+        HIP_TRY(hipMemsetAsync(c->acc_map, 0, (size_t)c->HW * sizeof(unsigned), c->stream));
+    }
     c->props_sweep = -1;
     return 0;
 }
@@ -363,6 +366,7 @@ int d3d_mh_sweeps(d3d_ctx *c, int n_sweeps, int first_sweep, int keep_one_in, do
     }
     unsigned long long acc = 0;
     unsigned flow_err = 0;
+    if (int rc = accepted_collect(c)) return rc;
     HIP_TRY(hipMemcpyAsync(&acc, c->accepted, sizeof acc, hipMemcpyDeviceToHost, c->stream));
     if (flow || c->mh_pair || c->chain_used)  // (these kernels raise *flow_err when a flag wait times out)
         HIP_TRY(hipMemcpyAsync(&flow_err, c->flow_err, sizeof flow_err, hipMemcpyDeviceToHost,
@@ -476,9 +480,11 @@ int d3d_mh_sweeps_batch(d3d_ctx **ctxs, int n_ctx, int n_sweeps, int first_sweep
         while (snaps[r].count > 0)
             if (int rc = snap_drain_one(ctxs[r], snaps[r], co(r), lo(r))) return rc;
     std::vector<unsigned long long> acc(n_ctx, 0);
-    for (int r = 0; r < n_ctx; ++r)
+    for (int r = 0; r < n_ctx; ++r) {
+        if (int rc = accepted_collect(ctxs[r])) return rc;  // (on the common stream: BatchScope)
         HIP_TRY(hipMemcpyAsync(&acc[r], ctxs[r]->accepted, sizeof(unsigned long long), hipMemcpyDeviceToHost,
                                L->stream));
+    }
     HIP_TRY(hipStreamSynchronize(L->stream));
     if (accepted)
         for (int r = 0; r < n_ctx; ++r) accepted[r] = (int64_t)acc[r];
