@@ -6,7 +6,8 @@ reference's own ``Run / Instrument / SpreadFunction / LineModel`` API
 """
 from .cube import Axis, Cube, HyperspectralCube  # noqa: F401
 from .instruments import MUSE, Instrument  # noqa: F401
-from .line_models import GaussianMultipletLineModel, LineModel, SingleGaussianLineModel  # noqa: F401
+from .line_models import (GaussianMultipletLineModel, LineModel, SingleGaussianLineModel,  # noqa: F401
+                          TabulatedLineModel)
 from .masks import above_percentile, above_snr  # noqa: F401
 from .math_utils import median_clip  # noqa: F401
 from . import adapt  # noqa: F401

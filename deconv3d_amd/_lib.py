@@ -23,7 +23,7 @@ SYMBOLS = [
     "d3d_ctx_create", "d3d_ctx_destroy", "d3d_ctx_set_stream", "d3d_sync",
     "d3d_ctx_set_option", "d3d_ctx_get_option", "d3d_has_experiments",
     "d3d_timer_start", "d3d_timer_stop",
-    "d3d_set_taps", "d3d_set_data", "d3d_set_params", "d3d_get_params", "d3d_set_line_shape",
+    "d3d_set_taps", "d3d_set_data", "d3d_set_params", "d3d_get_params", "d3d_set_line_shape", "d3d_set_line_table",
     "d3d_build_clean", "d3d_convolve", "d3d_forward", "d3d_simulate", "d3d_residual",
     "d3d_chi2_map", "d3d_upload_slot", "d3d_download_slot",
     "d3d_convolve_slots", "d3d_stage_upload", "d3d_stage_convolve", "d3d_stage_download",
@@ -150,6 +150,7 @@ def load():
     lib.d3d_set_params.argtypes = [ctx_p, dbl_p]
     lib.d3d_get_params.argtypes = [ctx_p, dbl_p]
     lib.d3d_set_line_shape.argtypes = [ctx_p, C.c_int, dbl_p, dbl_p]
+    lib.d3d_set_line_table.argtypes = [ctx_p, C.c_int, C.c_double, dbl_p, C.c_double]
     lib.d3d_build_clean.argtypes = [ctx_p, dbl_p]
     lib.d3d_convolve.argtypes = [ctx_p, dbl_p, dbl_p]
     lib.d3d_forward.argtypes = [ctx_p, dbl_p]
@@ -397,6 +398,18 @@ class Engine(object):
         if off.size == 0:
             raise ValueError("a line shape has 1 to 4 components, got 0")
         _check(self._lib.d3d_set_line_shape(self._ctx, int(off.size), _dp(off), _dp(rat)))
+
+    def set_line_table(self, table, support=0., flux_factor=0.):
+        """Tabulated profile of the unit line (include/deconv3d_hip.h: d3d_set_line_table):
+        ``table`` holds 8 to 65537 samples of phi on the uniform grid over
+        ``[-support, support]``, the sample of largest magnitude equal to 1; ``flux_factor`` is
+        the integral of phi.  ``table=None`` (or empty) returns the context to Gaussians."""
+        if table is None:
+            tab = np.zeros(0)
+        else:
+            tab = np.ascontiguousarray(table, dtype=np.float64).reshape(-1)
+        _check(self._lib.d3d_set_line_table(self._ctx, int(tab.size), float(support),
+                                            _dp(tab) if tab.size else None, float(flux_factor)))
 
     def get_params(self):
         out = np.empty(self.shape[1:] + (3,), dtype=np.float64)

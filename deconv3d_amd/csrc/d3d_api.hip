@@ -754,6 +754,7 @@ int d3d_ctx_destroy(d3d_ctx *c) {
     for (hipEvent_t e : c->halo_ev) (void)hipEventDestroy(e);
     for (int s = 0; s < D3D_SLOT_COUNT; ++s)
         if (c->slot[s]) (void)hipFree(c->slot[s]);
+    if (c->line.tab) (void)hipFree(const_cast<double *>(c->line.tab));
     void *ptrs[] = {c->stage, c->stage2, c->params, c->params_alt, c->mask, c->fsf, c->lsf_shift, c->lsf_weight,
                     c->dlog, c->hwbuf, c->scal, c->accepted, c->acc_map, c->spx, c->gbuf[0], c->gbuf[1], c->gbuf[2], c->gbuf[3],
                     c->flow_ent, c->flow_col, c->flow_lat, c->flow_state, c->flow_err, c->pair_state, c->sep_uv,
@@ -1194,12 +1195,70 @@ int d3d_set_line_shape(d3d_ctx *c, int K, const double *offsets, const double *r
     // the pending updates were made with the old line: written back with it, then everything
     // built from the line -- the residual, the sweep's proposal and line tables -- is stale
     if (int rc = flush_pending(c)) return rc;
-    d3d::LineShape L = {K, {0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
-    for (int k = 0; k < K; ++k) {
-        L.off[k] = offsets[k];
-        L.ratio[k] = ratios[k];
+    d3d::LineShape L = c->line;  // (the table, if any, stays: d3d_set_line_table)
+    L.K = K;
+    for (int k = 0; k < d3d::LINE_KMAX; ++k) {
+        L.off[k] = k < K ? offsets[k] : 0.0;
+        L.ratio[k] = k < K ? ratios[k] : 0.0;
     }
     c->line = L;
+    c->err_valid = false;
+    c->props_sweep = -1;
+    return post_reset(c);  // moments over two line models mean nothing
+}
+
+int d3d_set_line_table(d3d_ctx *c, int n, double support, const double *table, double flux_factor) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    if (n != 0) {
+        NEED(table, D3D_ERR_INVALID, "NULL argument");
+        NEED(n >= 8 && n <= 65537, D3D_ERR_INVALID, "a line table has 8 to 65537 samples, got %d", n);
+        NEED(std::isfinite(support) && support > 0.0, D3D_ERR_INVALID,
+             "line table: the support must be finite and > 0");
+        NEED(std::isfinite(flux_factor), D3D_ERR_INVALID, "line table: the flux factor must be finite");
+        double peak = 0.0;
+        for (int j = 0; j < n; ++j) {
+            NEED(std::isfinite(table[j]), D3D_ERR_INVALID, "line table: sample %d is not finite", j);
+            if (std::fabs(table[j]) > std::fabs(peak)) peak = table[j];
+        }
+        NEED(peak == 1.0, D3D_ERR_INVALID,
+             "line table: the sample of largest magnitude must be 1 (a is the peak amplitude), got %g", peak);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    // the new table first (a failure keeps the old one), then as d3d_set_line_shape: the pending
+    // updates were made with the old line
+    double *dev = nullptr;
+    if (n != 0) {
+        std::vector<double> padded((size_t)n + 2, 0.0);
+        std::copy(table, table + n, padded.begin() + 1);
+        HIP_TRY(hipMalloc(&dev, padded.size() * sizeof(double)));
+        hipError_t e = hipMemcpy(dev, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(dev);
+            HIP_TRY(e);
+        }
+    }
+    if (int rc = flush_pending(c)) {
+        if (dev) (void)hipFree(dev);
+        return rc;
+    }
+    if (c->line.tab) {
+        // (launches that read the old table may still be queued)
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) {
+            if (dev) (void)hipFree(dev);
+            HIP_TRY(e);
+        }
+        (void)hipFree(const_cast<double *>(c->line.tab));
+    }
+    c->line.tab = dev;
+    c->line.n = n;
+    c->line.support = n ? support : 0.0;
+    c->line.inv_h = n ? (double)(n - 1) / (2.0 * support) : 0.0;
+    c->line_tab_flux = n ? flux_factor : 0.0;
+    if (n)
+        c->h_line_tab.assign(table, table + n);
+    else
+        c->h_line_tab.clear();
     c->err_valid = false;
     c->props_sweep = -1;
     return post_reset(c);  // moments over two line models mean nothing

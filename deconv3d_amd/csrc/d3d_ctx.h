@@ -137,7 +137,11 @@ struct d3d_ctx {
     std::vector<uint8_t> h_mask;
     std::vector<uint8_t> h_user_mask;  // the caller's mask alone, without the NaN rule (d3d_line_search)
 
-    d3d::LineShape line = {1, {0.0, 0.0, 0.0, 0.0}, {1.0, 0.0, 0.0, 0.0}};  // d3d_set_line_shape
+    d3d::LineShape line = {1, {0.0, 0.0, 0.0, 0.0}, {1.0, 0.0, 0.0, 0.0}, nullptr, 0, 0.0, 0.0};  // d3d_set_line_shape
+    // d3d_set_line_table: line.tab is the device copy (n + 2 doubles, owned), h_line_tab the n
+    // samples on the host (d3d_mh_sweeps_batch compares them), line_tab_flux the integral of phi
+    std::vector<double> h_line_tab;
+    double line_tab_flux = 0.0;
     bool have_taps = false, have_data = false, have_params = false, have_cfg = false;
     bool err_valid = false;
     double min_b[3] = {}, max_b[3] = {}, amp[3] = {};

@@ -101,17 +101,48 @@ __device__ __forceinline__ double unit_gaussian(double z, double c, double w) {
 // (off[0] == 0, ratio[0] == 1) -- GaussianMultipletLineModel, deconv3d_amd/line_models.py.
 // K == 1 is SingleGaussianLineModel.
 constexpr int LINE_KMAX = 4;
+// With a table (d3d_set_line_table; TabulatedLineModel) every component is phi((d) / w) instead
+// of the Gaussian: tab holds the n samples of phi on the uniform grid over [-support, support]
+// with one zero before and one after (n + 2 doubles on the device), inv_h = (n - 1) / (2 support).
+// The new members come last: what the K == 1 kernels read of their arguments stays where it was.
 struct LineShape {
     int K;
     double off[LINE_KMAX];
     double ratio[LINE_KMAX];
+    const double *tab;  // nullptr: Gaussians
+    int n;
+    double support, inv_h;
 };
 
-// The unit line at channel z.  MULTI = false (the instantiation every kernel runs for K == 1):
-// unit_gaussian itself, the shape unread -- that kernel is the single Gaussian's code, bit for bit
-// and register for register.  MULTI = true (K > 1): sum_k ratio[k] g_k in component order with g_k
-// from d = (z - c) - off[k] -- the order of GaussianMultipletLineModel.modelize -- and
-// unit_gaussian's delta rule for w == 0 per component.
+// The kernels of a context run their MULTI = true instantiation for a multiplet and for any
+// tabulated line, K == 1 included -- the one place that decides it.
+__host__ __device__ inline bool line_multi(const LineShape &L) { return L.K > 1 || L.tab != nullptr; }
+
+// phi(d / w) of the table: the Catmull-Rom cubic through the four samples around
+// t = (u + support) inv_h, 0 beyond the support and for NaN; w == 0 keeps unit_gaussian's delta
+// rule (phi(0) at d == 0, else 0); the value returned is ratio * phi.  One IEEE operation per step in the order of
+// TabulatedLineModel.tabulated (no contraction): host and device agree bit for bit.
+// j lies in [0, n - 2] whatever d and w are, so the four loads stay inside the n + 2 doubles.
+__device__ __forceinline__ double table_line(const LineShape &L, double d, double w, double ratio) {
+#pragma clang fp contract(off)
+    const double u = (w != 0.0) ? d / w : ((d == 0.0) ? 0.0 : __builtin_nan(""));
+    const double t = (u + L.support) * L.inv_h;
+    if (!(t >= 0.0 && t <= (double)(L.n - 1))) return 0.0;
+    const int j = min((int)floor(t), L.n - 2);
+    const double s = t - (double)j;
+    const double *p = L.tab + j;
+    const double p0 = p[0], p1 = p[1], p2 = p[2], p3 = p[3];
+    const double phi =
+        p1 + 0.5 * s * ((p2 - p0) + s * ((2.0 * p0 - 5.0 * p1 + 4.0 * p2 - p3) + s * (3.0 * (p1 - p2) + (p3 - p0))));
+    return ratio * phi;  // (the product in here: the caller's sum cannot fuse it)
+}
+
+// The unit line at channel z.  MULTI = false (the instantiation every kernel runs for K == 1
+// without a table): unit_gaussian itself, the shape unread -- that kernel is the single Gaussian's
+// code, bit for bit and register for register.  MULTI = true (line_multi): sum_k ratio[k] g_k in
+// component order with g_k from d = (z - c) - off[k] -- the order of
+// GaussianMultipletLineModel.modelize -- and unit_gaussian's delta rule for w == 0 per component;
+// with a table g_k = table_line (the test of the pointer is the same in every lane).
 template <bool MULTI>
 __device__ __forceinline__ double unit_line(const LineShape &L, double z, double c, double w) {
     if constexpr (!MULTI) return unit_gaussian(z, c, w);
@@ -122,8 +153,12 @@ __device__ __forceinline__ double unit_line(const LineShape &L, double z, double
     for (int k = 0; k < LINE_KMAX; ++k) {
         if (k < L.K) {
             const double d = (z - c) - L.off[k];
-            const double g = (w2 > 0.0) ? exp(-(d * d) / w2) : ((d == 0.0) ? 1.0 : 0.0);
-            s += L.ratio[k] * g;
+            if (L.tab) {
+                s += table_line(L, d, w, L.ratio[k]);
+            } else {
+                const double g = (w2 > 0.0) ? exp(-(d * d) / w2) : ((d == 0.0) ? 1.0 : 0.0);
+                s += L.ratio[k] * g;
+            }
         }
     }
     return s;

@@ -181,7 +181,7 @@ int adapt_after_sweep(d3d_ctx *c, int s) {
 }
 
 // The instantiation of k_mh_ws for the context's line shape: the single Gaussian's kernel for
-// K == 1 (MULTI = false: unchanged code), the multiplet form (unit_line<true>) for K > 1.
+// K == 1 (MULTI = false: unchanged code), the multiplet form (unit_line<true>) for K > 1 or a table.
 template <int NS, bool UV, int U, int M, int K, int NL, bool NTV = false, bool ZBK = false, bool BATCH = false>
 static auto mh_ws_kernel(bool multi, bool prior) {
     // (d3d_prior_begin: the instantiations with the smoothness prior's terms -- a template
@@ -195,7 +195,10 @@ static auto mh_ws_kernel(bool multi, bool prior) {
 
 // options whose kernels have no multiplet form (EXPERIMENTS builds): refused, never ignored
 static int need_single_line(const d3d_ctx *c, const char *what) {
-    if (c->line.K == 1) return 0;
+    if (!d3d::line_multi(c->line)) return 0;
+    if (c->line.tab)
+        return fail(D3D_ERR_UNSUPPORTED, "%s has no tabulated form: the line is a table of %d samples "
+                    "(d3d_set_line_table; one Gaussian only)", what, c->line.n);
     return fail(D3D_ERR_UNSUPPORTED, "%s has no multiplet form: the line shape has %d components "
                 "(d3d_set_line_shape; one Gaussian only)", what, c->line.K);
 }
@@ -203,7 +206,7 @@ static int need_single_line(const d3d_ctx *c, const char *what) {
 template <int NT, int MAXIT>
 int launch_mh_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep) {
     const size_t lds = d3d::mh_lds_doubles(NT, c->HL, c->Dp, c->N, P.npos) * sizeof(double);
-    if (c->line.K > 1) {
+    if (d3d::line_multi(c->line)) {
         if constexpr (MAXIT != 0) return need_single_line(c, "option mh_maxit (register-resident k_mh)");
         if constexpr (MAXIT == 0) {
             if (P.prior) {
@@ -248,8 +251,8 @@ int launch_mh_nt(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep
 int launch_mh(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep) {
     if (c->deep) {  // more than 1024 channels: threads loop over their z-pairs
         const size_t lds = d3d::mh_deep_lds_doubles(c->N, P.npos) * sizeof(double);
-        auto kern = P.prior ? (c->line.K > 1 ? &d3d::k_mh_deep<true, true> : &d3d::k_mh_deep<false, true>)
-                            : (c->line.K > 1 ? &d3d::k_mh_deep<true> : &d3d::k_mh_deep<false>);
+        auto kern = P.prior ? (d3d::line_multi(c->line) ? &d3d::k_mh_deep<true, true> : &d3d::k_mh_deep<false, true>)
+                            : (d3d::line_multi(c->line) ? &d3d::k_mh_deep<true> : &d3d::k_mh_deep<false>);
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), lds, c->stream, P, sweep);
@@ -267,8 +270,8 @@ int launch_mh(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep) {
 template <int NT>
 int launch_mh_defer_nt(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep) {
     const size_t lds = d3d::mh_lds_doubles(NT, c->HL, c->Dp, c->N, P.npos) * sizeof(double);
-    auto kern = P.prior ? (c->line.K > 1 ? &d3d::k_mh_defer<NT, true, true> : &d3d::k_mh_defer<NT, false, true>)
-                        : (c->line.K > 1 ? &d3d::k_mh_defer<NT, true> : &d3d::k_mh_defer<NT, false>);
+    auto kern = P.prior ? (d3d::line_multi(c->line) ? &d3d::k_mh_defer<NT, true, true> : &d3d::k_mh_defer<NT, false, true>)
+                        : (d3d::line_multi(c->line) ? &d3d::k_mh_defer<NT, true> : &d3d::k_mh_defer<NT, false>);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, c->stream, P, sweep);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -291,13 +294,13 @@ int launch_mh_ws_um(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sw
     };
     // (the number of pending layers as a template constant: see k_mh_ws)
     switch (P.n_lay <= M ? P.n_lay : -1) {
-        case 0: go(mh_ws_kernel<NS, UV, U, M, K, 0, NTV>(P.line.K > 1, P.prior != 0)); break;
-        case 1: go(mh_ws_kernel<NS, UV, U, M, K, 1, NTV>(P.line.K > 1, P.prior != 0)); break;
+        case 0: go(mh_ws_kernel<NS, UV, U, M, K, 0, NTV>(d3d::line_multi(P.line), P.prior != 0)); break;
+        case 1: go(mh_ws_kernel<NS, UV, U, M, K, 1, NTV>(d3d::line_multi(P.line), P.prior != 0)); break;
         case 2:
-            if constexpr (M >= 2) go(mh_ws_kernel<NS, UV, U, M, K, 2, NTV>(P.line.K > 1, P.prior != 0));
+            if constexpr (M >= 2) go(mh_ws_kernel<NS, UV, U, M, K, 2, NTV>(d3d::line_multi(P.line), P.prior != 0));
             break;
         case 3:
-            if constexpr (M >= 3) go(mh_ws_kernel<NS, UV, U, M, K, 3, NTV>(P.line.K > 1, P.prior != 0));
+            if constexpr (M >= 3) go(mh_ws_kernel<NS, UV, U, M, K, 3, NTV>(d3d::line_multi(P.line), P.prior != 0));
             break;
         default:
             return fail(D3D_ERR_STATE, "internal: %d pending layers for a %d-layer kernel", P.n_lay, M);
@@ -648,23 +651,23 @@ int launch_mh_zb_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned n_items, uint32_t 
     const int nl = P.n_lay;
     if (layers >= 2) {
         if (few) {
-            if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 2, 4, 0, false, true>(P.line.K > 1, false), 2);
-            else if (nl == 1) go(mh_ws_kernel<NS, UV, 4, 2, 4, 1, false, true>(P.line.K > 1, false), 2);
-            else go(mh_ws_kernel<NS, UV, 4, 2, 4, 2, false, true>(P.line.K > 1, false), 2);
+            if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 2, 4, 0, false, true>(d3d::line_multi(P.line), false), 2);
+            else if (nl == 1) go(mh_ws_kernel<NS, UV, 4, 2, 4, 1, false, true>(d3d::line_multi(P.line), false), 2);
+            else go(mh_ws_kernel<NS, UV, 4, 2, 4, 2, false, true>(d3d::line_multi(P.line), false), 2);
         } else if (ntv) {
             if constexpr (!UV) {
-                if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 4, 0, true, true>(P.line.K > 1, false), 2);
-                else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 4, 1, true, true>(P.line.K > 1, false), 2);
-                else go(mh_ws_kernel<NS, UV, 2, 2, 4, 2, true, true>(P.line.K > 1, false), 2);
+                if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 4, 0, true, true>(d3d::line_multi(P.line), false), 2);
+                else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 4, 1, true, true>(d3d::line_multi(P.line), false), 2);
+                else go(mh_ws_kernel<NS, UV, 2, 2, 4, 2, true, true>(d3d::line_multi(P.line), false), 2);
             }
         } else {
-            if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 4, 0, false, true>(P.line.K > 1, false), 2);
-            else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 4, 1, false, true>(P.line.K > 1, false), 2);
-            else go(mh_ws_kernel<NS, UV, 2, 2, 4, 2, false, true>(P.line.K > 1, false), 2);
+            if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 4, 0, false, true>(d3d::line_multi(P.line), false), 2);
+            else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 4, 1, false, true>(d3d::line_multi(P.line), false), 2);
+            else go(mh_ws_kernel<NS, UV, 2, 2, 4, 2, false, true>(d3d::line_multi(P.line), false), 2);
         }
     } else {
-        if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 1, 4, 0, false, true>(P.line.K > 1, false), 1);
-        else go(mh_ws_kernel<NS, UV, 4, 1, 4, 1, false, true>(P.line.K > 1, false), 1);
+        if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 1, 4, 0, false, true>(d3d::line_multi(P.line), false), 1);
+        else go(mh_ws_kernel<NS, UV, 4, 1, 4, 1, false, true>(d3d::line_multi(P.line), false), 1);
     }
     HIP_TRY(hipGetLastError());
     const int nw = P.z_nb * (NS / 64);
@@ -722,17 +725,17 @@ int launch_mh_batch_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t 
     const int nl = P.n_lay;
     if (layers >= 2) {  // Dp <= 160: the staged G rows in two registers
         if (few) {
-            if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 2, 2, 0, false, false, true>(P.line.K > 1, P.prior != 0), 2);
-            else if (nl == 1) go(mh_ws_kernel<NS, UV, 4, 2, 2, 1, false, false, true>(P.line.K > 1, P.prior != 0), 2);
-            else go(mh_ws_kernel<NS, UV, 4, 2, 2, 2, false, false, true>(P.line.K > 1, P.prior != 0), 2);
+            if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 2, 2, 0, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 2);
+            else if (nl == 1) go(mh_ws_kernel<NS, UV, 4, 2, 2, 1, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 2);
+            else go(mh_ws_kernel<NS, UV, 4, 2, 2, 2, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 2);
         } else {
-            if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 2, 0, false, false, true>(P.line.K > 1, P.prior != 0), 2);
-            else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 2, 1, false, false, true>(P.line.K > 1, P.prior != 0), 2);
-            else go(mh_ws_kernel<NS, UV, 2, 2, 2, 2, false, false, true>(P.line.K > 1, P.prior != 0), 2);
+            if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 2, 0, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 2);
+            else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 2, 1, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 2);
+            else go(mh_ws_kernel<NS, UV, 2, 2, 2, 2, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 2);
         }
     } else {
-        if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 1, 4, 0, false, false, true>(P.line.K > 1, P.prior != 0), 1);
-        else go(mh_ws_kernel<NS, UV, 4, 1, 4, 1, false, false, true>(P.line.K > 1, P.prior != 0), 1);
+        if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 1, 4, 0, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 1);
+        else go(mh_ws_kernel<NS, UV, 4, 1, 4, 1, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 1);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -770,7 +773,7 @@ int launch_line_table(d3d_ctx *c, const d3d::MHArgs &P, uint32_t sweep, const d3
     const long n = (long)(c->oy1 - c->oy0) * (c->ox1 - c->ox0) * std::max(R, 1);  // one wavefront per spaxel
     if (n <= 0) return 0;
     const size_t lds = (size_t)4 * 2 * c->N * sizeof(double);
-    hipLaunchKernelGGL(c->line.K > 1 ? &d3d::k_mh_line_table<true> : &d3d::k_mh_line_table<false>,
+    hipLaunchKernelGGL(d3d::line_multi(c->line) ? &d3d::k_mh_line_table<true> : &d3d::k_mh_line_table<false>,
                        dim3((unsigned)((n + 3) / 4)), dim3(256), lds, c->stream, P, sweep, c->oy0, c->oy1,
                        c->ox0, c->ox1, c->props, c->ltab, chains, R);
     HIP_TRY(hipGetLastError());
@@ -930,7 +933,7 @@ int launch_mh_chain(d3d_ctx *c, int pi, uint32_t sweep0, int n_sweeps) {
 
 int launch_apply_updates(d3d_ctx *c, const d3d::MHArgs &P, const double *rec, int n) {
     const size_t lds = (size_t)(2 * c->N + c->Dp) * sizeof(double);
-    if (c->line.K > 1) {
+    if (d3d::line_multi(c->line)) {
         if (c->HL <= 256)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_apply_updates<256, true>), dim3((unsigned)n), dim3(256),
                                lds, c->stream, P, rec, n);

@@ -255,6 +255,7 @@ static int launch_post_t(d3d_ctx *c, const d3d::PostArgs &A) {
 static double flux_factor(const d3d_ctx *c) {
     double ratios = 0.0;
     for (int k = 0; k < c->line.K; ++k) ratios += c->line.ratio[k];
+    if (c->line.tab) return c->line_tab_flux * ratios;  // (the table's own integral: d3d_set_line_table)
     return std::sqrt(2.0 * M_PI) * ratios;
 }
 
@@ -276,8 +277,8 @@ int launch_post_accum(d3d_ctx *c) {
     A.map_mean = c->post_map;
     A.map_m2 = c->post_map + (size_t)c->HW * 4;
     A.line = c->line;
-    // MULTI only for K > 1, as every other line kernel
-    if (c->line.K > 1)
+    // MULTI only for K > 1 or a table, as every other line kernel
+    if (d3d::line_multi(c->line))
         return c->post_nt ? launch_post_t<true, true>(c, A) : launch_post_t<true, false>(c, A);
     return c->post_nt ? launch_post_t<false, true>(c, A) : launch_post_t<false, false>(c, A);
 }

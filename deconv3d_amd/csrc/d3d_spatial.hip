@@ -33,7 +33,7 @@ int launch_lines_nt(d3d_ctx *c, double *out, int convolved, const double *params
     const int G = NT / c->HL;
     const unsigned grid = (unsigned)((c->HW + G - 1) / G);
     const size_t lds = (size_t)G * c->N * sizeof(double);
-    if (c->line.K > 1)
+    if (d3d::line_multi(c->line))
         hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_lines<NT, true>), dim3(grid), dim3(NT), lds, c->stream, A,
                            params, c->mask, out, convolved);
     else
@@ -63,10 +63,13 @@ int launch_lines(d3d_ctx *c, double *out, int convolved, const double *params) {
             int L = (int)std::min<long>(8, std::max<long>(1, c->HW / ((long)S * 4096)));
             if (c->lines_rounds > 0) L = std::min(c->lines_rounds, 64 / S);  // (a lane per spaxel of the wavefront)
             const unsigned grid = (unsigned)((c->HW + (long)4 * S * L - 1) / ((long)4 * S * L));
-            if (c->lines_dense == 2 && c->line.K > 1)
+            if (c->lines_dense == 2 && c->line.tab)
+                return fail(D3D_ERR_UNSUPPORTED, "option lines_dense = 2 (the line cube with its own exp) has no "
+                            "tabulated form: the line is a table of %d samples", c->line.n);
+            if (c->lines_dense == 2 && d3d::line_multi(c->line))
                 return fail(D3D_ERR_UNSUPPORTED, "option lines_dense = 2 (the line cube with its own exp) has no "
                             "multiplet form: the line shape has %d components", c->line.K);
-            if (c->line.K > 1)
+            if (d3d::line_multi(c->line))
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_lines_dense<false, true>), dim3(grid), dim3(256),
                                    use_lsf ? lds : 0, c->stream, spectral_args(c), hlg, steps, L,
                                    (const double *)c->lsf_dense, params, (const uint8_t *)c->mask, out,
@@ -88,7 +91,7 @@ int launch_lines(d3d_ctx *c, double *out, int convolved, const double *params) {
     if (c->deep) {
         d3d::SpectralArgs A = spectral_args(c);
         const size_t lds = (size_t)c->N * sizeof(double);
-        auto kern = c->line.K > 1 ? &d3d::k_lines_deep<true> : &d3d::k_lines_deep<false>;
+        auto kern = d3d::line_multi(c->line) ? &d3d::k_lines_deep<true> : &d3d::k_lines_deep<false>;
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3((unsigned)c->HW), dim3(1024), lds, c->stream, A,

@@ -413,6 +413,9 @@ int d3d_mh_sweeps_batch(d3d_ctx **ctxs, int n_ctx, int n_sweeps, int first_sweep
         bool same_line = c->line.K == L->line.K;
         for (int k = 0; k < d3d::LINE_KMAX; ++k)
             same_line = same_line && c->line.off[k] == L->line.off[k] && c->line.ratio[k] == L->line.ratio[k];
+        // (and the table: the leader's device copy serves every chain)
+        same_line = same_line && c->line.n == L->line.n && c->line.support == L->line.support &&
+                    c->h_line_tab == L->h_line_tab;
         NEED(same_line, D3D_ERR_INVALID,
              "ctx %d: another line shape than ctx 0 (the chains share the launch's arguments)", r);
         // (the chains share the leader's pending-layer state, and a from-scratch residual

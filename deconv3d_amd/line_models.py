@@ -3,12 +3,14 @@
 Line-model plugin interface -- same names and contracts as the reference's
 ``lib/line_models.py`` (LineModel :4-61, SingleGaussianLineModel :64-109).
 
-The device kernels implement ``SingleGaussianLineModel`` and
-``GaussianMultipletLineModel`` (amplitude Gibbs-sampled, centre/width
-Metropolis-Hastings).  ``modelize`` below is the host evaluation of the same
+The device kernels implement ``SingleGaussianLineModel``,
+``GaussianMultipletLineModel`` and ``TabulatedLineModel`` (amplitude Gibbs-sampled,
+centre/width Metropolis-Hastings).  ``modelize`` below is the host evaluation of the same
 curve, kept for API parity (plots, user scripts).
 """
+import hashlib
 import math
+import struct
 
 import numpy as np
 
@@ -168,15 +170,130 @@ class GaussianMultipletLineModel(LineModel):
         return a * s
 
 
+class TabulatedLineModel(GaussianMultipletLineModel):
+    """
+    Any line of the location-scale family ``a * phi((x - c) / w)``, ``phi`` read from a table
+    -- an asymmetric Lyman alpha, Lorentzian wings, a fixed Gauss-Hermite shape, a P-Cygni
+    profile -- and, with ``offsets`` / ``ratios`` (the multiplet's rules), a multiplet of it::
+
+        a * sum_k ratios[k] * phi(((x - c) - offsets[k]) / w)
+
+    ``profile``: 8 to 65537 samples of ``phi`` on the uniform grid ``u_j = -support + j h``,
+    ``h = 2 support / (n - 1)``; the constructor divides them by the sample of largest
+    magnitude, which must be positive, so that the peak is 1 and ``a`` stays the peak
+    amplitude.  Negative lobes are allowed; non-finite samples, an all-zero table or a
+    ``support`` that is not finite and > 0 raise ``ValueError``.  The parameters, the Gibbs
+    index and the bounds are those of ``SingleGaussianLineModel``; the device kernels evaluate
+    the line themselves (``d3d_set_line_table``).
+
+    The curve IS the interpolant (:meth:`phi`): the Catmull-Rom cubic through the table padded
+    with one zero on each side, 0 beyond the support.  ``flux_factor``: the trapezoid integral
+    of the normalised table times ``sum(ratios)`` -- the integrated flux is
+    ``F = a w flux_factor``.
+    """
+
+    MIN_SAMPLES, MAX_SAMPLES = 8, 65537
+
+    def __init__(self, profile, support, offsets=(0.,), ratios=(1.,)):
+        GaussianMultipletLineModel.__init__(self, offsets, ratios)
+        try:
+            tab = np.array(profile, dtype=np.float64)
+            support = float(support)
+        except (TypeError, ValueError):
+            raise ValueError("profile must be a sequence of numbers and support a number")
+        if tab.ndim != 1:
+            raise ValueError("profile must be one-dimensional, got shape %s" % (tab.shape,))
+        if not self.MIN_SAMPLES <= tab.size <= self.MAX_SAMPLES:
+            raise ValueError("a line table has %d to %d samples, got %d"
+                             % (self.MIN_SAMPLES, self.MAX_SAMPLES, tab.size))
+        if not (math.isfinite(support) and support > 0.):
+            raise ValueError("support must be finite and > 0, got %r" % support)
+        if not np.isfinite(tab).all():
+            raise ValueError("profile samples must be finite")
+        peak = tab[np.argmax(np.abs(tab))]
+        if peak == 0.:
+            raise ValueError("profile is zero everywhere")
+        if peak < 0.:
+            raise ValueError("the sample of largest magnitude must be positive (a is the peak "
+                             "amplitude), got %g" % peak)
+        tab = tab / peak
+        tab.setflags(write=False)
+        self.table = tab
+        self.support = support
+        self.inv_h = (tab.size - 1) / (2. * support)
+        padded = np.zeros(tab.size + 2)
+        padded[1:-1] = tab
+        self._padded = padded
+        h = 2. * support / (tab.size - 1)
+        # (integral of phi alone: what d3d_set_line_table takes; the device multiplies by the ratios)
+        self.table_integral = float(h * (np.sum(tab) - 0.5 * (tab[0] + tab[-1])))
+        self.flux_factor = self.table_integral * float(sum(self.ratios))
+
+    @classmethod
+    def from_function(cls, phi, support, samples=2049, **kw):
+        """The table of ``samples`` values of the callable ``phi`` on ``[-support, support]``."""
+        samples = int(samples)
+        if samples < 2:
+            raise ValueError("a line table has %d to %d samples, got %d"
+                             % (cls.MIN_SAMPLES, cls.MAX_SAMPLES, samples))
+        u = -float(support) + np.arange(samples) * (2. * float(support) / (samples - 1))
+        return cls(np.array([phi(v) for v in u], dtype=np.float64), support, **kw)
+
+    def phi(self, d, w):
+        """``phi(d / w)``: the interpolant, one IEEE double operation per step in the order of
+        the device's table_line (d3d_kernels.h).  ``w == 0``: the value at 0 where ``d == 0``,
+        0 elsewhere (unit_gaussian's delta rule); NaN and anything beyond the support: 0."""
+        d = np.asarray(d, dtype=np.float64)
+        n = self.table.size
+        with np.errstate(all="ignore"):
+            if w != 0.:
+                u = d / w
+            else:
+                u = np.where(d == 0., 0., np.nan)
+            t = (u + self.support) * self.inv_h
+            inside = (t >= 0.) & (t <= n - 1)
+            tt = np.where(inside, t, 0.)
+            j = np.minimum(np.floor(tt).astype(np.int64), n - 2)
+            s = tt - j
+            p = self._padded
+            p0, p1, p2, p3 = p[j], p[j + 1], p[j + 2], p[j + 3]
+            v = p1 + 0.5 * s * ((p2 - p0) + s * ((2. * p0 - 5. * p1 + 4. * p2 - p3)
+                                                 + s * (3. * (p1 - p2) + (p3 - p0))))
+        return np.where(inside, v, 0.)
+
+    def modelize(self, runner, x, parameters):
+        return self.tabulated(np.asarray(x, dtype=np.float64),
+                              parameters[0], parameters[1], parameters[2])
+
+    def tabulated(self, x, a, c, w):
+        """``a * sum_k r_k phi(((x - c) - d_k) / w)`` in component order -- the order of the
+        device's unit_line."""
+        s = 0.
+        for off, r in zip(self.offsets, self.ratios):
+            s = s + r * self.phi((x - c) - off, w)
+        return a * s
+
+    def digest(self):
+        """SHA-256 over ``n``, ``support`` and the sample bytes: what a checkpoint records."""
+        h = hashlib.sha256()
+        h.update(struct.pack("<qd", self.table.size, self.support))
+        h.update(np.ascontiguousarray(self.table, dtype="<f8").tobytes())
+        return h.hexdigest()
+
+
 SINGLE_LINE_SHAPE = ((0.,), (1.,))
 
 
 def model_is_on_device(model):
     """True when the HIP kernels evaluate ``model`` themselves:
-    ``SingleGaussianLineModel`` or ``GaussianMultipletLineModel`` (subclasses may change
+    ``SingleGaussianLineModel``, ``GaussianMultipletLineModel`` or ``TabulatedLineModel`` (subclasses may change
     names and bounds, but not the curve, the jump hook or the Gibbs index).  Any other
     LineModel plugin is evaluated on the host (host_model.HostModelChain)."""
-    if isinstance(model, GaussianMultipletLineModel):
+    if isinstance(model, TabulatedLineModel):
+        curve = (type(model).modelize is TabulatedLineModel.modelize
+                 and type(model).tabulated is TabulatedLineModel.tabulated
+                 and type(model).phi is TabulatedLineModel.phi)
+    elif isinstance(model, GaussianMultipletLineModel):
         curve = (type(model).modelize is GaussianMultipletLineModel.modelize
                  and type(model).multiplet is GaussianMultipletLineModel.multiplet)
     elif isinstance(model, SingleGaussianLineModel):
@@ -196,3 +313,13 @@ def device_line_shape(model):
     if isinstance(model, GaussianMultipletLineModel):
         return tuple(model.offsets), tuple(model.ratios)
     return SINGLE_LINE_SHAPE
+
+
+def device_line_table(model):
+    """(table, support, flux_factor) of ``Engine.set_line_table`` for a model that runs on the
+    device -- the normalised samples, their support and the integral of phi -- or None for a
+    model of Gaussians."""
+    # (the very table modelize interpolates: the device cannot disagree with the host curve)
+    if isinstance(model, TabulatedLineModel):
+        return model.table, model.support, model.table_integral
+    return None

@@ -40,7 +40,7 @@ from . import _lib, adapt as _adapt, posterior as _posterior, prepare as _prepar
 from .cube import Cube, read_fits
 from .instruments import Instrument
 from .line_models import (LineModel, SingleGaussianLineModel, SINGLE_LINE_SHAPE,
-                          device_line_shape, model_is_on_device)
+                          device_line_shape, device_line_table, model_is_on_device)
 from .math_utils import median_clip
 
 logging.basicConfig(level=logging.INFO)
@@ -339,6 +339,9 @@ class Run:
                 % type(self.model).__name__)
         # (offsets, ratios) of the device's unit line; None for a host-evaluated model
         self.line_shape = None if self._host_model else device_line_shape(self.model)
+        # (table, support, flux_factor) of a tabulated line and the digest a checkpoint records
+        self.line_table = None if self._host_model else device_line_table(self.model)
+        self.line_table_digest = None if self.line_table is None else self.model.digest()
         min_boundaries = np.array(self.model.min_boundaries(self), dtype=np.float64)
         max_boundaries = np.array(self.model.max_boundaries(self), dtype=np.float64)
         names = self.model.parameters()
@@ -466,6 +469,14 @@ class Run:
                                      "ratios %s; this run's model has offsets %s, ratios %s"
                                      % (tuple(np.ravel(saved[0])), tuple(np.ravel(saved[1])),
                                         self.line_shape[0], self.line_shape[1]))
+                # (a checkpoint without a table digest was written by a run of Gaussians)
+                saved_digest = str(state["line_table_digest"]) if "line_table_digest" in files else None
+                if saved_digest != self.line_table_digest:
+                    raise ValueError("resume_state was written with %s; this run's model has %s"
+                                     % ("Gaussian lines" if saved_digest is None
+                                        else "the line table " + saved_digest[:16],
+                                        "Gaussian lines" if self.line_table_digest is None
+                                        else "the line table " + self.line_table_digest[:16]))
 
         # ---- device context ----------------------------------------------
         self.engines = []
@@ -476,6 +487,8 @@ class Run:
             eng.set_data(self.cube.data, self.variance_cube, mask=self.mask)
             if self.line_shape is not None:
                 eng.set_line_shape(*self.line_shape)
+            if self.line_table is not None:
+                eng.set_line_table(*self.line_table)
         self.engine = self.engines[0]
         # ---- searched start (initial_search=): chain 0 from the matched-filter map, chains
         # r > 0 from jittered copies; spaxels without a detection keep their uniform draw
@@ -742,6 +755,8 @@ class Run:
         if self.line_shape is not None:     # (resume_state= checks it)
             state["line_offsets"] = np.array(self.line_shape[0], dtype=np.float64)
             state["line_ratios"] = np.array(self.line_shape[1], dtype=np.float64)
+        if self.line_table_digest is not None:
+            state["line_table_digest"] = np.array(self.line_table_digest)
         if self.prepared is not None:       # (resume_state= checks them)
             state["prepare_settings"] = _prepare.settings_record(self.prepared.settings)
         if self.smoothness is not None:     # (resume_state= checks them)

@@ -22,7 +22,7 @@ import numpy as np
 from . import _lib
 from .instruments import Instrument
 from .line_models import (LineModel, SingleGaussianLineModel, device_line_shape,
-                          model_is_on_device)
+                          device_line_table, model_is_on_device)
 from .math_utils import median_clip
 
 DEFAULT_WIDTH_COUNT = 8
@@ -277,4 +277,7 @@ def line_search(cube, instrument, variance=None, mask=None, model=SingleGaussian
         engine.set_data(cube.data, variance, mask=mask)
         if model_is_on_device(model):
             engine.set_line_shape(*device_line_shape(model))
+            table = device_line_table(model)
+            if table is not None:
+                engine.set_line_table(*table)
         return search_engine(engine, model, runner, centres, widths, lsf)

@@ -223,13 +223,14 @@ def setup_tile_engine(engine, layout, rank):
 
 def make_tile_engine(layout, rank, data, var, mask, fsf, lsf, params, min_b, max_b,
                      jump_amplitude, ra, seed, device=0, err=None, refresh_every=0, options=None,
-                     line_shape=None):
+                     line_shape=None, line_table=None):
     """`_lib.Engine` holding rank's region of the global problem.  The initial
     residual is rebuilt from the region's own parameters (exact on the used cells);
     `err`, a GLOBAL residual cube, overrides it (the bit-identity tests hand every
     tile the very same starting residual as the single device).  `line_shape`:
     (offsets, ratios) of a multiplet (`Engine.set_line_shape`), set before the residual
-    exists -- the call invalidates it."""
+    exists -- the call invalidates it; `line_table`: (table, support, flux_factor) of a
+    tabulated line (`Engine.set_line_table`), set at the same place."""
     from . import _lib
     ry0, ry1, rx0, rx1 = layout.region(rank)
     oy0, oy1, ox0, ox1 = layout.owned(rank)
@@ -238,6 +239,8 @@ def make_tile_engine(layout, rank, data, var, mask, fsf, lsf, params, min_b, max
     eng.set_taps(fsf, lsf)
     if line_shape is not None:
         eng.set_line_shape(*line_shape)
+    if line_table is not None:
+        eng.set_line_table(*line_table)
     eng.set_tile(ry0, rx0, layout.W, oy0 - ry0, oy1 - ry0, ox0 - rx0, ox1 - rx0)
     sub = (slice(None), slice(ry0, ry1), slice(rx0, rx1))
     eng.set_data(np.ascontiguousarray(data[sub]),

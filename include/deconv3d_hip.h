@@ -142,6 +142,26 @@ int d3d_get_params(d3d_ctx *ctx, double *params);
  * proposal / line tables: every later line build (forward model, simulate, MH updates,
  * residual refresh) uses the new shape. */
 int d3d_set_line_shape(d3d_ctx *ctx, int K, const double *offsets, const double *ratios);
+/* A tabulated profile phi in place of the Gaussian of the unit line (lib/line_models.py:17-61,
+ * 92-109: the reference's LineModel plugin, here for any a * phi((z - c) / w)): table holds n
+ * samples of phi on the uniform grid u_j = -support + j h, h = 2 support / (n - 1), and every
+ * component of the line shape becomes ratios[k] * phi(((z - c) - offsets[k]) / w) (python:
+ * TabulatedLineModel).  The curve is the Catmull-Rom cubic through the table padded with one
+ * zero on each side: with u = d / w, t = (u + support) * inv_h, inv_h = (n - 1) / (2 support),
+ * the value is 0 unless 0 <= t <= n - 1 (NaN: 0); else j = min(floor(t), n - 2), s = t - j,
+ * p0..p3 the padded samples j-1 .. j+2 and
+ *   p1 + 0.5 s ((p2 - p0) + s ((2 p0 - 5 p1 + 4 p2 - p3) + s (3 (p1 - p2) + (p3 - p0)))),
+ * one IEEE double operation per step in this order; w == 0: phi(0) where d == 0, else 0.
+ * 8 <= n <= 65537, support finite and > 0, every sample finite, the sample of largest
+ * magnitude equal to 1 (a stays the peak amplitude; negative lobes are allowed), table not
+ * NULL; anything else is D3D_ERR_INVALID and the old table stays.  flux_factor: the integral
+ * of phi over u (the table's trapezoid sum times h), finite: the integrated flux of the
+ * posterior moments and histograms is F = a w flux_factor sum_k ratios[k].  n == 0 (support,
+ * table and flux_factor ignored) returns the ctx to Gaussians.  The ctx keeps its own copy.
+ * d3d_set_line_shape sets offsets and ratios only and leaves the table alone.  Side effects as
+ * d3d_set_line_shape: pending updates written back with the old line, residual, proposal /
+ * line tables and posterior moments invalidated. */
+int d3d_set_line_table(d3d_ctx *ctx, int n, double support, const double *table, double flux_factor);
 
 /* ---- forward model ------------------------------------------------------ */
 
