@@ -102,6 +102,16 @@ SLOT_DATA, SLOT_IVAR, SLOT_ERR, SLOT_SIM, SLOT_TMP0, SLOT_TMP1 = range(6)
 
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED = -1, -2, -3, -4, -5
 
+# read-only options spatial_path / spectral_path / stage_path: the kernel family the dispatcher took
+# last (include/deconv3d_hip.h: D3D_SPATIAL_*, D3D_SPECTRAL_*, D3D_STAGE_*)
+SPATIAL_CONV_ROWS, SPATIAL_CONV_ROWS_ZB, SPATIAL_CONV_ROWS_LSF = 1, 2, 3
+SPATIAL_MARCH_XY, SPATIAL_MARCH_X, SPATIAL_MARCH = 10, 11, 12
+SPATIAL_SEP, SPATIAL_SEP_LSF, SPATIAL_MARCH_EXPERIMENT = 13, 14, 15
+SPATIAL_GENERIC, SPATIAL_DEEP = 30, 40
+SPATIAL_TILE = 10000      # the tile kernel k_spatial<NT>: SPATIAL_TILE + NT
+SPECTRAL_BLOCKS, SPECTRAL_DEEP, SPECTRAL_DENSE, SPECTRAL_TAPS, SPECTRAL_SHFL = 1, 2, 3, 4, 5
+STAGE_ZMAJOR, STAGE_TRANSPOSE = 1, 2
+
 
 class HipLibraryMissing(ImportError):
     """libdeconv3d_hip.so has not been built (run __graft_entry__.build())."""

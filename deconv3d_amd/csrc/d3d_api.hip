@@ -876,6 +876,11 @@ int d3d_ctx_get_option(d3d_ctx *c, const char *key, long *value) {
         *value = c->ntaps;
         return D3D_OK;
     }
+    if (!strcmp(key, "spatial_path") || !strcmp(key, "spectral_path") || !strcmp(key, "stage_path")) {
+        // read-only: the kernel family the dispatcher took last (D3D_SPATIAL_* / D3D_SPECTRAL_* / D3D_STAGE_*)
+        *value = key[2] == 'a' ? (key[3] == 't' ? c->spatial_path : c->stage_path) : c->spectral_path;
+        return D3D_OK;
+    }
     if (!strcmp(key, "small_parts")) {    // parts whose colour launches run k_mh_small
         long n = 0;
         for (const d3d_ctx::Part &pt : c->parts) n += d3dh::mh_part_uses_tables(c, pt) ? 1 : 0;
@@ -1353,6 +1358,7 @@ int d3d_stage_convolve(d3d_ctx *c) {
     NEED(c, D3D_ERR_INVALID, "ctx is NULL");
     NEED(c->have_taps, D3D_ERR_STATE, "taps not set");
     HIP_TRY(hipSetDevice(c->device));
+    c->stage_path = zmajor_ok(c) ? D3D_STAGE_ZMAJOR : D3D_STAGE_TRANSPOSE;
     if (zmajor_ok(c)) return launch_zmajor_convolve(c);
     // general taps: through the spectrum-contiguous slot kernels
     int rc = to_device_layout(c, c->stage, c->slot[D3D_SLOT_TMP0]);

@@ -314,6 +314,9 @@ struct d3d_ctx {
     // running-median and channel-statistics kernels (both passes of a rejecting d3d_prepare summed),
     // by HIP events (read-only options prep_median_ns / prep_stats_ns)
     long prep_median_ns = 0, prep_stats_ns = 0;
+    // kernel family the last launch_spatial / launch_spectral / d3d_stage_convolve took (read-only
+    // options spatial_path / spectral_path / stage_path: D3D_SPATIAL_*, D3D_SPECTRAL_*, D3D_STAGE_*)
+    int spatial_path = 0, spectral_path = 0, stage_path = 0;
 };
 
 namespace d3dh {

@@ -124,6 +124,7 @@ int launch_spectral(d3d_ctx *c, const double *in, double *out) {
     if (c->lsf_dense_any && c->spectral_blocks && !(c->lsf_fusable && c->spectral_dense)) {
         const int nzb = (c->Dp + 127) / 128;
         const long nwaves = (long)c->HW * nzb;
+        c->spectral_path = D3D_SPECTRAL_BLOCKS;
         hipLaunchKernelGGL(d3d::k_spectral_blocks, dim3((unsigned)((nwaves + 3) / 4)), dim3(256), 0,
                            c->stream, c->D, c->Dp, c->N, nzb, nwaves, (const double *)c->lsf_dense, in,
                            out);
@@ -133,6 +134,7 @@ int launch_spectral(d3d_ctx *c, const double *in, double *out) {
     if (c->deep) {
         d3d::SpectralArgs A = spectral_args(c);
         const size_t lds = (size_t)c->N * sizeof(double);
+        c->spectral_path = D3D_SPECTRAL_DEEP;
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(d3d::k_spectral_deep),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(d3d::k_spectral_deep, dim3((unsigned)c->HW), dim3(1024), lds, c->stream, A,
@@ -146,6 +148,7 @@ int launch_spectral(d3d_ctx *c, const double *in, double *out) {
         const unsigned grid = (unsigned)((c->HW + G - 1) / G);
 #ifdef D3D_EXPERIMENTS
         if (c->spectral_shfl && c->HL == 64) {  // neighbours by wavefront shuffles, no LDS
+            c->spectral_path = D3D_SPECTRAL_SHFL;
             hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_spectral_shfl<256>), dim3(grid), dim3(NT), 0,
                                c->stream, c->Dp, c->HW, (const double *)c->lsf_dense, in, out);
             HIP_TRY(hipGetLastError());
@@ -153,11 +156,13 @@ int launch_spectral(d3d_ctx *c, const double *in, double *out) {
         }
 #endif
         const size_t lds = (size_t)G * (c->Dp + 2 * d3d::LSF_RL) * sizeof(double);
+        c->spectral_path = D3D_SPECTRAL_DENSE;
         hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_spectral_dense<256>), dim3(grid), dim3(NT), lds,
                            c->stream, c->Dp, c->HL, c->HW, (const double *)c->lsf_dense, in, out);
         HIP_TRY(hipGetLastError());
         return 0;
     }
+    c->spectral_path = D3D_SPECTRAL_TAPS;
     switch (pick_nt(c->HL)) {
         case 256: return launch_spectral_nt<256>(c, in, out);
         case 512: return launch_spectral_nt<512>(c, in, out);
@@ -171,6 +176,7 @@ int launch_spatial_fw(d3d_ctx *c, const d3d::SpatialArgs &A, const double *in, d
     const int S = NT / c->HL;
     const long strips = (long)c->H * ((c->W + TX - 1) / TX);
     const unsigned grid = (unsigned)((strips + S - 1) / S);
+    c->spatial_path = D3D_SPATIAL_TILE + NT;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_spatial<NT, FW, TX>), dim3(grid), dim3(NT), 0,
                        c->stream, A, in, out);
     HIP_TRY(hipGetLastError());
@@ -185,6 +191,8 @@ int launch_march(d3d_ctx *c, const d3d::SpatialArgs &A, const double *in, double
     const unsigned grid = (unsigned)((items + S - 1) / S);
     const size_t lds =
         FUSE ? (size_t)S * TX * (c->Dp + 2 * d3d::LSF_RL) * sizeof(double) : 0;
+    c->spatial_path = FUSE ? D3D_SPATIAL_MARCH_EXPERIMENT
+                           : SYMX ? (SYMY ? D3D_SPATIAL_MARCH_XY : D3D_SPATIAL_MARCH_X) : D3D_SPATIAL_MARCH;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_spatial_march<NT, FS, TX, SYMX, UNI, FUSE, SYMY>),
                        dim3(grid), dim3(NT), lds, c->stream, A, in, out, HY);
     HIP_TRY(hipGetLastError());
@@ -204,6 +212,7 @@ int launch_march_stamped(d3d_ctx *c, d3d::SpatialArgs A, const double *in, doubl
     unsigned long long *dbg = nullptr;
     HIP_TRY(hipMalloc(&dbg, nw * 8 * sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(dbg, 0, nw * 8 * sizeof(unsigned long long), c->stream));
+    c->spatial_path = D3D_SPATIAL_MARCH_EXPERIMENT;
     A.dbg = dbg;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_spatial_march<NT, FS, TX, true, true, false, true, true>),
                        dim3(grid), dim3(NT), 0, c->stream, A, in, out, HY);
@@ -243,6 +252,7 @@ int launch_sep_lsf(d3d_ctx *c, const d3d::SpatialArgs &A, const double *in, doub
     const long items = (long)((c->W + TX - 1) / TX) * ((c->H + HY - 1) / HY);
     const unsigned grid = (unsigned)((items + S - 1) / S);
     const size_t lds = (size_t)S * TX * (c->Dp + 2 * d3d::LSF_RL) * sizeof(double);
+    c->spatial_path = D3D_SPATIAL_SEP_LSF;
     if ((c->HL % 64) == 0)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_spatial_sep_lsf<NT, FS, TX, true>), dim3(grid),
                            dim3(NT), lds, c->stream, A, in, out, HY);
@@ -261,6 +271,7 @@ int launch_sep(d3d_ctx *c, const d3d::SpatialArgs &A, const double *in, double *
     const int HY = c->march_hy;
     const long items = (long)((c->W + TX - 1) / TX) * ((c->H + HY - 1) / HY);
     const unsigned grid = (unsigned)((items + S - 1) / S);
+    c->spatial_path = D3D_SPATIAL_SEP;
     if ((c->HL % 64) == 0)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_spatial_sep<NT, FS, TX, true>), dim3(grid),
                            dim3(NT), 0, c->stream, A, in, out, HY);
@@ -283,6 +294,7 @@ int launch_march_fs(d3d_ctx *c, const d3d::SpatialArgs &A, const double *in, dou
         // one channel per lane: 3 (TX = 3) or 4 (TX = 2) wavefronts per SIMD
         const int HY = c->march_hy;
         const int S = NT / c->Dp;
+        c->spatial_path = D3D_SPATIAL_MARCH_EXPERIMENT;
         if (c->march_one == 3) {
             const long items = (long)((c->W + 2) / 3) * ((c->H + HY - 1) / HY);
             hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_spatial_march1<NT, FS, 3, 3>),
@@ -301,6 +313,7 @@ int launch_march_fs(d3d_ctx *c, const d3d::SpatialArgs &A, const double *in, dou
         // software-pipelined variant (next-row loads interleaved with the FMAs)
         const int HY = c->march_hy;
         const int S = NT / c->HL;
+        c->spatial_path = D3D_SPATIAL_MARCH_EXPERIMENT;
         if (c->march_pf == 3) {
             const long items = (long)((c->W + 2) / 3) * ((c->H + HY - 1) / HY);
             hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_spatial_march_pf<NT, FS, 3>),
@@ -405,6 +418,7 @@ int launch_spatial_nt(d3d_ctx *c, const double *in, double *out, const double *d
     }
     const int S = NT / c->HL;
     const unsigned grid = (unsigned)((c->HW + S - 1) / S);
+    c->spatial_path = D3D_SPATIAL_GENERIC;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_spatial_generic<NT>), dim3(grid), dim3(NT), 0,
                        c->stream, A, in, out);
     HIP_TRY(hipGetLastError());
@@ -459,6 +473,7 @@ int launch_conv_rows_t(d3d_ctx *c, const double *in, double *out, const double *
     if (c->conv_hy_opt >= 1) A.HY = c->conv_hy_opt;
     A.ngy = (c->H + A.HY - 1) / A.HY;
     A.xcd_remap = 1;
+    c->spatial_path = LSF ? D3D_SPATIAL_CONV_ROWS_LSF : ZB ? D3D_SPATIAL_CONV_ROWS_ZB : D3D_SPATIAL_CONV_ROWS;
     auto kern = d3d::k_conv_rows<FS, NW, LSF, LSYM, RESID, TSYM, DPS, ZB>;
     constexpr size_t lds = d3d::conv_rows_lds_bytes<FS, NW, DPS>();
     // > 64 KB of dynamic LDS has to be allowed per function AND per device: set on every
@@ -569,6 +584,7 @@ int launch_spatial(d3d_ctx *c, const double *in, double *out, const double *data
         A.fw = c->fw;
         A.fsf = c->fsf;
         A.data = data;
+        c->spatial_path = D3D_SPATIAL_DEEP;
         hipLaunchKernelGGL(d3d::k_spatial_deep, dim3((unsigned)c->HW, (unsigned)((c->HL + 255) / 256)),
                            dim3(256), 0, c->stream, A, in, out);
         HIP_TRY(hipGetLastError());

@@ -75,7 +75,9 @@ int d3d_device_count(int *count);
 int d3d_ctx_create(d3d_ctx **ctx, int device, int D, int H, int W, int fh, int fw);
 int d3d_ctx_destroy(d3d_ctx *ctx);
 /* Run on a caller-owned HIP stream (e.g. torch's current stream) instead of
- * the ctx's own; NULL restores the own stream. */
+ * the ctx's own; NULL restores the own stream.  The handle must come from the HIP runtime
+ * this library is linked to: a stream of a second copy of the runtime in the process (a
+ * PyTorch wheel that bundles its own libamdhip64) means nothing to this one. */
 int d3d_ctx_set_stream(d3d_ctx *ctx, void *hip_stream);
 /* Block until everything queued on the ctx stream has finished. */
 int d3d_sync(d3d_ctx *ctx);
@@ -102,7 +104,34 @@ int d3d_timer_stop(d3d_ctx *ctx, double *elapsed_ms);
  * ctx's parts run their sweeps as one launch of persistent workgroups (k_mh_chain), and
  * "search_bank_ns" / "search_kernel_ns": device time of the last d3d_line_search call's bank build
  * and of its search kernel, and "prep_median_ns" / "prep_stats_ns": device time of the running-median
- * and channel-statistics kernels of the last d3d_running_median / d3d_channel_stats / d3d_prepare. */
+ * and channel-statistics kernels of the last d3d_running_median / d3d_channel_stats / d3d_prepare.
+ * Three more read-only keys name the kernel family the dispatcher took LAST (a host-side int per
+ * ctx, 0 before the first launch; the tests assert them, nothing in the library reads them):
+ * "spatial_path" (the last FSF pass -- d3d_convolve_slots, d3d_forward, d3d_residual, d3d_simulate,
+ * a residual rebuilt by the sweeps), "spectral_path" (the last stand-alone LSF pass of
+ * d3d_convolve_slots) and "stage_path" (the last d3d_stage_convolve / d3d_convolve): the
+ * D3D_SPATIAL_*, D3D_SPECTRAL_* and D3D_STAGE_* codes below. */
+enum {
+    D3D_SPATIAL_CONV_ROWS = 1,     /* k_conv_rows, FSF only, one block of <= 128 channels */
+    D3D_SPATIAL_CONV_ROWS_ZB = 2,  /* k_conv_rows in z-blocks of 128 channels (FSF only) */
+    D3D_SPATIAL_CONV_ROWS_LSF = 3, /* k_conv_rows with the LSF epilogue */
+    D3D_SPATIAL_MARCH_XY = 10,     /* k_spatial_march<SYMX, SYMY>: both mirror symmetries */
+    D3D_SPATIAL_MARCH_X = 11,      /* k_spatial_march<SYMX>: x symmetry only */
+    D3D_SPATIAL_MARCH = 12,        /* k_spatial_march without symmetry */
+    D3D_SPATIAL_SEP = 13,          /* k_spatial_sep: outer-product FSF */
+    D3D_SPATIAL_SEP_LSF = 14,      /* k_spatial_sep_lsf: outer-product FSF and LSF in one pass */
+    D3D_SPATIAL_MARCH_EXPERIMENT = 15, /* a march variant of a `make EXPERIMENTS=1` build */
+    D3D_SPATIAL_GENERIC = 30,      /* k_spatial_generic: any FSF shape */
+    D3D_SPATIAL_DEEP = 40,         /* k_spatial_deep: more than 1024 channels */
+    D3D_SPATIAL_TILE = 10000,      /* k_spatial<NT> (tile kernel): D3D_SPATIAL_TILE + NT */
+    D3D_SPECTRAL_BLOCKS = 1,       /* k_spectral_blocks */
+    D3D_SPECTRAL_DEEP = 2,         /* k_spectral_deep */
+    D3D_SPECTRAL_DENSE = 3,        /* k_spectral_dense */
+    D3D_SPECTRAL_TAPS = 4,         /* k_spectral (tap list) */
+    D3D_SPECTRAL_SHFL = 5,         /* k_spectral_shfl (`make EXPERIMENTS=1`) */
+    D3D_STAGE_ZMAJOR = 1,          /* k_spectral_z / k_spatial_z in the reference layout */
+    D3D_STAGE_TRANSPOSE = 2        /* transpose, slot kernels (d3d_convolve_slots), transpose back */
+};
 int d3d_ctx_set_option(d3d_ctx *ctx, const char *key, long value);
 int d3d_ctx_get_option(d3d_ctx *ctx, const char *key, long *value);
 /* 1 when the library was built with `make EXPERIMENTS=1` (the measured-but-not-faster

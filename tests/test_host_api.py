@@ -41,6 +41,19 @@ def test_library_exports_every_declared_symbol():
     assert lib.d3d_version() >= 100
 
 
+def test_path_codes_of_the_binding_equal_the_header():
+    """The read-only options spatial_path / spectral_path / stage_path answer with the header's
+    D3D_SPATIAL_* / D3D_SPECTRAL_* / D3D_STAGE_* codes; the tests name them through _lib."""
+    text = open(os.path.join(ROOT, "include", "deconv3d_hip.h")).read()
+    codes = {k: int(v) for k, v in re.findall(r"\bD3D_((?:SPATIAL|SPECTRAL|STAGE)_[A-Z_]+) = (\d+)", text)}
+    assert len(codes) == 19
+    for name, value in codes.items():
+        assert getattr(_lib, name) == value, name
+    for family in ("SPATIAL", "SPECTRAL", "STAGE"):     # a code names ONE family
+        values = [v for k, v in codes.items() if k.startswith(family + "_")]
+        assert len(set(values)) == len(values) and 0 not in values
+
+
 def test_every_entry_point_cites_the_reference():
     text = open(os.path.join(ROOT, "include", "deconv3d_hip.h")).read()
     assert text.count("lib/run.py:") >= 15
