@@ -43,6 +43,7 @@ SYMBOLS = [
     "d3d_prior_begin", "d3d_prior_get", "d3d_prior_end", "d3d_prior_energy",
     "d3d_line_search",
     "d3d_running_median", "d3d_channel_stats", "d3d_prepare",
+    "d3d_temper_create", "d3d_temper_swap", "d3d_temper_get", "d3d_temper_last", "d3d_temper_destroy",
 ]
 
 # posterior moments (a table, so that tools/posterior_time.py can load the PARENT commit's library,
@@ -91,6 +92,17 @@ PREP_PROTOTYPES = {
                           C.POINTER(C.c_double), C.POINTER(C.c_int64)],
     "d3d_prepare": [C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.c_int, C.c_double,
                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
+}
+# replica exchange between tempered chains (a table for the same reason; the first argument is the
+# group's handle, d3d_temper_create's the address it is returned through)
+TEMPER_PROTOTYPES = {
+    "d3d_temper_create": [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_double),
+                          C.c_uint64],
+    "d3d_temper_swap": [C.c_void_p, C.c_int64],
+    "d3d_temper_get": [C.c_void_p] + [C.POINTER(C.c_int64)] * 4 + [C.POINTER(C.c_double)] * 2
+                      + [C.POINTER(C.c_int32)],
+    "d3d_temper_last": [C.c_void_p] + [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_int32)],
+    "d3d_temper_destroy": [C.c_void_p],
 }
 POST_CLEAN, POST_CONVOLVED = 1, 2                     # d3d_post_begin: bits of `what`
 POST_PARAMETERS, POST_CLEAN_CUBE, POST_CONVOLVED_CUBE = 0, 1, 2   # d3d_post_get: `which`
@@ -218,6 +230,8 @@ def load():
                            + list(SEARCH_PROTOTYPES.items()) + list(PREP_PROTOTYPES.items())
                            + list(PRIOR_PROTOTYPES.items()) + list(HIST_PROTOTYPES.items())):
         getattr(lib, name).argtypes = [ctx_p] + argtypes
+    for name, argtypes in TEMPER_PROTOTYPES.items():
+        getattr(lib, name).argtypes = argtypes
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("d3d_version", "d3d_last_error", "d3d_source_hash", "d3d_has_experiments"):
@@ -274,6 +288,70 @@ def mh_sweeps_batch(engines, n_sweeps, first_sweep=1, keep_one_in=1, chains=None
     _check(lib.d3d_mh_sweeps_batch(arr, n, int(n_sweeps), int(first_sweep), int(keep_one_in),
                                    pointers(chains, (3,)), pointers(dlogs, ()), acc))
     return [int(v) for v in acc]
+
+
+class TemperGroup(object):
+    """d3d_temper_*: replica exchange between the chains of ``engines`` -- one geometry, rung r
+    fed ``var / betas[r]`` by its owner -- at inverse temperatures ``betas`` (1 first, strictly
+    decreasing).  ``seed`` keys the swaps' uniforms.  Close the group before its engines."""
+
+    def __init__(self, engines, betas, seed=12345):
+        self._lib = load()
+        self._t = C.c_void_p(None)
+        self.engines = list(engines)          # (kept alive: the group holds their contexts)
+        self.n = len(self.engines)
+        self.betas = np.ascontiguousarray(betas, dtype=np.float64)
+        if self.betas.ndim != 1 or self.betas.shape[0] != self.n:
+            raise ValueError("one beta per engine: %d engine(s), betas of shape %s"
+                             % (self.n, self.betas.shape))
+        arr = (C.c_void_p * max(self.n, 1))(*[e._ctx.value for e in self.engines])
+        _check(self._lib.d3d_temper_create(C.byref(self._t), arr, self.n, _dp(self.betas),
+                                           C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)))
+
+    def close(self):
+        if getattr(self, "_t", None) is not None and self._t.value:
+            self._lib.d3d_temper_destroy(self._t)
+            self._t = C.c_void_p(None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def swap(self, round):
+        """One exchange round (asynchronous): the pairs (i, i + 1) with i of ``round``'s parity."""
+        _check(self._lib.d3d_temper_swap(self._t, int(round)))
+
+    def get(self):
+        """dict(rounds, attempts, accepts (n-1), energy_n, energy_mean, energy_m2, labels (n))."""
+        n = self.n
+        rounds = C.c_int64(0)
+        attempts, accepts = np.zeros(n - 1, dtype=np.int64), np.zeros(n - 1, dtype=np.int64)
+        e_n, labels = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+        mean, m2 = np.zeros(n), np.zeros(n)
+        i64 = C.POINTER(C.c_int64)
+        _check(self._lib.d3d_temper_get(self._t, C.byref(rounds), attempts.ctypes.data_as(i64),
+                                        accepts.ctypes.data_as(i64), e_n.ctypes.data_as(i64), _dp(mean),
+                                        _dp(m2), labels.ctypes.data_as(C.POINTER(C.c_int32))))
+        return dict(rounds=int(rounds.value), attempts=attempts, accepts=accepts, energy_n=e_n,
+                    energy_mean=mean, energy_m2=m2, labels=labels)
+
+    def last(self):
+        """The last round: dict(energy (n), u, logu (n-1, NaN where not proposed), decided (n-1:
+        1 accepted, 0 rejected, -1 not proposed))."""
+        n = self.n
+        energy, u, logu = np.zeros(n), np.zeros(n - 1), np.zeros(n - 1)
+        decided = np.zeros(n - 1, dtype=np.int32)
+        _check(self._lib.d3d_temper_last(self._t, _dp(energy), _dp(u), _dp(logu),
+                                         decided.ctypes.data_as(C.POINTER(C.c_int32))))
+        return dict(energy=energy, u=u, logu=logu, decided=decided)
 
 
 def device_count():

@@ -2,7 +2,8 @@
 // functions shared by the library's translation units (d3d_api.hip: C ABI and host
 // logic; d3d_spatial.hip: line / LSF / FSF kernels; d3d_mh.hip: the MH-within-Gibbs
 // kernels; d3d_sweep.hip: the sweep driver; d3d_post.hip: posterior moments; d3d_search.hip: the
-// matched-filter line search; d3d_prep.hip: continuum removal and channel noise of a raw cube).
+// matched-filter line search; d3d_prep.hip: continuum removal and channel noise of a raw cube;
+// d3d_temper.hip: replica exchange between tempered chains).
 // Not installed: the public interface is include/deconv3d_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -418,5 +419,11 @@ int launch_philox(d3d_ctx *c, long n, const uint32_t *counters, const uint32_t *
 int launch_mh_flow(d3d_ctx *c, uint32_t sweep);
 int launch_mh_pair(d3d_ctx *c, int ka, uint32_t sweep);
 #endif
+
+// ---- d3d_temper.hip: replica exchange between tempered chains -----------------------------
+// One round of a group on its leader's stream: the chains' energies, the decisions of the pairs of
+// the round's parity, the exchange of the accepted pairs' residuals and parameters (three launches,
+// nothing but device memory between them).  The caller has written the pending layers back.
+int temper_round(d3d_temper *t, int64_t round);
 
 }  // namespace d3dh

@@ -36,7 +36,7 @@ from os.path import splitext
 import numpy as np
 
 from . import _lib, adapt as _adapt, posterior as _posterior, prepare as _prepare, prior as _prior, \
-    search as _search
+    search as _search, tempering as _tempering
 from .cube import Cube, read_fits
 from .instruments import Instrument
 from .line_models import (LineModel, SingleGaussianLineModel, SINGLE_LINE_SHAPE,
@@ -164,6 +164,27 @@ class Run:
     :class:`deconv3d_amd.prepare.Prepared` (``continuum``, ``sigma``, ...).  ``initial_search=``
     sees the prepared cube.  The checkpoint records the settings; ``resume_state=`` runs the
     preparation again and refuses a state written with other settings.
+
+    ``tempering=`` (default ``None``: off, nothing allocated or launched, the chain is bit for bit
+    what it is without the keyword) runs parallel tempering: a dict with either ``betas=(1, ...)``
+    (strictly decreasing inverse temperatures) or ``rungs=R`` plus ``beta_min=`` (the geometric
+    ladder ``beta_min ** (r / (R - 1))``), and ``swap_every=1``.  Rung r is a chain of the same
+    cube with the variance divided by ``betas[r]`` -- its MH ratio (lib/run.py:426-438) and the
+    likelihood terms of its Gibbs draw (lib/run.py:491-496) scale by ``betas[r]``, the priors stay
+    as they are -- seeded ``seed + r`` and started as chain r of ``chains=R`` is; after every
+    sweep s with ``(s + sweep_origin) % swap_every == 0`` adjacent rungs exchange their states on
+    the device with the Metropolis rule of replica exchange (d3d_temper_swap), so that the cold
+    chain inherits the barrier crossings of the hot ones.  ``run.chain``, ``run.likelihoods``,
+    ``run.parameters`` and the cubes come from rung 0 alone; ``run.chains[r]`` holds rung r's
+    tempered samples, ``run.rhat`` is ``None`` (the rungs sample different distributions), and
+    ``run.tempering`` is a :class:`deconv3d_amd.tempering.TemperingReport` (``betas``,
+    ``swap_attempts``, ``swap_accepts``, ``swap_rates``, ``energy_mean``, ``energy_std``,
+    ``labels``, ``rounds``, ``save(prefix)``).  ``adapt_sweeps`` and ``smoothness`` apply to every
+    rung, ``posterior_burn_in`` / ``posterior_histograms`` to rung 0 only; the acceptance rate of
+    the stopping rule is pooled over the rungs.  ``chains`` must be 1 (the rungs take the chains'
+    place), a host-evaluated line model raises ``NotImplementedError``.  The checkpoint holds the
+    R maps as for ``chains=R`` and records the ladder and ``swap_every``; ``resume_state=`` refuses
+    a state written with others, the round numbering continues, counters and labels start afresh.
     """
 
     def __init__(
@@ -199,6 +220,7 @@ class Run:
         initial_search=None,
         prepare=None,
         smoothness=None,
+        tempering=None,
     ):
         # (before anything else: no device work yet)
         prepare_cfg = _prepare.check_keywords(prepare)
@@ -217,6 +239,7 @@ class Run:
                                  % (posterior_burn_in, adapt_cfg[0]))
         self._adapt_cfg = adapt_cfg
         self.smoothness = _prior.check_keywords(smoothness)
+        temper_cfg = self.tempering_cfg = _tempering.check_keywords(tempering)
         # lib/run.py:112-114
         assert keep_one_in > 0, "keep_one_in= MUST be a positive integer"
         assert write_every > 0, "write_every= MUST be a positive integer"
@@ -227,6 +250,9 @@ class Run:
         self.write_every = int(write_every)
         n_chains = int(chains)
         assert n_chains >= 1, "chains= MUST be a positive integer"
+        _tempering.check_run(temper_cfg, n_chains, False, None)
+        if temper_cfg is not None:          # (the rungs take the chains' place: rung r is chain r)
+            n_chains = len(temper_cfg["betas"])
         self.n_chains = n_chains
         if adapt_cfg is not None and adapt_cfg[0] > 0.8 * self.max_iterations:
             logger.warning("adapt_sweeps=%d is beyond 80 %% of max_iterations=%d: extract_parameters "
@@ -332,6 +358,7 @@ class Run:
                 "smoothness=: the line model %s is evaluated on the host; the device knows the "
                 "prior only for the (a, c, w) of the models it evaluates itself"
                 % type(self.model).__name__)
+        _tempering.check_run(temper_cfg, 1, self._host_model, type(self.model).__name__)
         if adapt_cfg is not None and self._host_model:
             raise NotImplementedError(
                 "adapt_sweeps=: the line model %s is evaluated on the host; the device "
@@ -448,6 +475,7 @@ class Run:
             resumed_adapt = _adapt.check_resume(state, files, adapt_cfg, n_chains,
                                                 (cube_height, cube_width))
             _prior.check_resume(state, files, self.smoothness)
+            _tempering.check_resume(state, files, temper_cfg)
             _prepare.check_resume(state, files,
                                   None if self.prepared is None else self.prepared.settings)
             # totals over every earlier segment (older checkpoints hold one segment's)
@@ -484,7 +512,9 @@ class Run:
             eng = _lib.Engine(cube_shape, self.fsf.shape, device=device)
             self.engines.append(eng)
             eng.set_taps(self.fsf, self.lsf)
-            eng.set_data(self.cube.data, self.variance_cube, mask=self.mask)
+            # (tempering=: rung r samples L^beta_r x prior, the same model with the variance / beta_r)
+            eng.set_data(self.cube.data, self.variance_cube if temper_cfg is None
+                         else self.variance_cube / temper_cfg["betas"][r], mask=self.mask)
             if self.line_shape is not None:
                 eng.set_line_shape(*self.line_shape)
             if self.line_table is not None:
@@ -519,7 +549,7 @@ class Run:
                 eng.mh_config(min_boundaries, max_boundaries, jumping_amplitude,
                               gibbs_apriori_variance, seed=self.seed + r,
                               refresh_every=refresh_every)
-                if posterior_burn_in is not None:
+                if posterior_burn_in is not None and (temper_cfg is None or r == 0):
                     eng.post_begin()
                     eng.post_schedule(posterior_burn_in, posterior_every)
                     if hist_cfg is not None:
@@ -545,7 +575,7 @@ class Run:
                 self.logger.warning("posterior_histograms=: max_iterations=%d leaves %d accumulated sweeps, "
                                     "none beyond the pilot of %d; the histograms will hold no sample"
                                     % (self.max_iterations, reachable, hist_cfg["pilot"]))
-            if n_chains > 1:
+            if n_chains > 1 and temper_cfg is None:
                 self.logger.info("posterior_histograms=: every chain freezes its own ranges; "
                                  "run.posteriors[r].histograms are per chain and the pooled "
                                  "run.posterior.histograms is None")
@@ -553,6 +583,12 @@ class Run:
         if host_chain is None:
             for eng in self.engines:
                 eng.residual(fetch=False)              # lib/run.py:317-334
+        # tempering=: the group that exchanges the rungs' states on the device.  The round of the
+        # exchange after sweep s is (s + sweep_origin) // swap_every: a resumed run continues the
+        # numbering, so no uniform is drawn twice.
+        temper_group, last_swap_round = None, None
+        if temper_cfg is not None:
+            temper_group = _lib.TemperGroup(self.engines, temper_cfg["betas"], seed=self.seed)
 
         # ---- MH within Gibbs loop (lib/run.py:336-537) -------------------------
         cur_iteration = 1
@@ -587,6 +623,10 @@ class Run:
             if max_accepted_count > 0:
                 cur_acceptance_rate = float(accepted_count + self._acc_base) / float(max_accepted_count)
             n = min(sweeps_per_call, max_iterations - cur_iteration)
+            swap_round = None
+            if temper_cfg is not None:      # (a call ends at every sweep an exchange follows)
+                n, swap_round = _tempering.calls_until_swap(n, cur_iteration, self.sweep_origin,
+                                                            temper_cfg["swap_every"])
             self.logger.info("Iteration #%d / %d, %2.0f%%" %
                              (cur_iteration + 1, max_iterations, 100 * cur_acceptance_rate))
             if host_chain is not None:
@@ -610,6 +650,11 @@ class Run:
                 self.mh_seconds += _time.perf_counter() - t_call
                 accepted_count += sum(acc)
                 per_chain_accepted = [a + b for a, b in zip(per_chain_accepted, acc)]
+                if swap_round is not None:     # (the sweep's chain slot is saved: the rungs trade states)
+                    t_call = _time.perf_counter()
+                    temper_group.swap(swap_round)
+                    last_swap_round = swap_round
+                    self.mh_seconds += _time.perf_counter() - t_call
             before = cur_iteration
             cur_iteration += n
             # write_every: documented (lib/run.py:89-92) but never used by the
@@ -650,7 +695,13 @@ class Run:
         # ---- outputs (lib/run.py:539-549) ------------------------------------
         self.likelihoods = likelihoods
         self.all_likelihoods = all_likelihoods
-        self.rhat = self.gelman_rubin() if n_chains > 1 else None
+        # (tempering=: the rungs sample different distributions)
+        self.rhat = self.gelman_rubin() if n_chains > 1 and temper_cfg is None else None
+        self.tempering = None
+        if temper_group is not None:
+            self.tempering = _tempering.TemperingReport.from_group(temper_group, temper_cfg["betas"],
+                                                                   temper_cfg["swap_every"], last_swap_round)
+            temper_group.close()
         self.parameters = self.extract_parameters()
         self.convolved_cube = Cube(data=self.simulate_convolved(cube_shape, self.parameters),
                                    meta=self.cube.meta, x=cube.x, y=cube.y, z=cube.z)
@@ -660,11 +711,11 @@ class Run:
         self.posteriors, self.posterior = None, None
         if posterior_burn_in is not None:
             self.posteriors = [_posterior.PosteriorMoments.from_engine(eng, self.cube, hist_cfg is not None)
-                               for eng in self.engines]
+                               for eng in (self.engines if temper_cfg is None else self.engines[:1])]
             if hist_cfg is not None:
                 for pm in self.posteriors:
                     pm.histograms.pilot, pm.histograms.span = hist_cfg["pilot"], hist_cfg["span"]
-            self.posterior = self.posteriors[0] if n_chains == 1 else \
+            self.posterior = self.posteriors[0] if len(self.posteriors) == 1 else \
                 _posterior.pooled(self.posteriors, self.cube)
             if self.posterior.count == 0:
                 self.logger.warning("posterior_burn_in=%d: the run stopped at iteration %d, before "
@@ -717,8 +768,9 @@ class Run:
         ``percentage`` % of the saved samples of the ``chains=R`` chains, shape (H, W, P):
         sqrt(((n-1)/n W + B/n) / W), W the mean within-chain variance and B/n the variance of
         the chain means.  NaN where a parameter did not move (masked spaxels)."""
-        if self.n_chains < 2:
-            raise ValueError("R-hat needs chains >= 2")
+        if self.n_chains < 2 or self.tempering_cfg is not None:
+            raise ValueError("R-hat needs chains >= 2 (the rungs of tempering= sample different "
+                             "distributions)")
         n_valid = min((self.iterations_done - 1) // self.keep_one_in + 1, self.chain.shape[0])
         if n_valid < 2:                          # (a variance needs two saved samples)
             return np.full(self.chain.shape[1:], np.nan)
@@ -761,6 +813,8 @@ class Run:
             state["prepare_settings"] = _prepare.settings_record(self.prepared.settings)
         if self.smoothness is not None:     # (resume_state= checks them)
             state["smoothness_sigmas"] = _prior.keyword_record(self.smoothness)
+        if self.tempering_cfg is not None:  # (resume_state= checks them; counters and labels start afresh)
+            state.update(_tempering.state_record(self.tempering_cfg))
         if self._adapt_cfg is not None:     # (resume_state= checks the keywords, restores the rest)
             got = [eng.adapt_get() for eng in self.engines]
             state["adapt_keywords"] = _adapt.keyword_record(self._adapt_cfg)
@@ -813,7 +867,7 @@ class Run:
         n_valid = (self.iterations_done - 1) // self.keep_one_in + 1
         n_valid = max(1, min(n_valid, self.chain.shape[0]))
         s = int((100. - percentage) * n_valid / 100.)
-        if self.n_chains == 1:
+        if self.n_chains == 1 or self.tempering_cfg is not None:     # (tempering=: rung 0 alone)
             return np.nanmean(self.chain[s:n_valid, ...], 0)
         # chains=R: the chains are pooled (equal lengths: the mean of their means)
         return np.nanmean(np.stack([np.nanmean(ch[s:n_valid, ...], 0) for ch in self.chains]), 0)

@@ -513,6 +513,57 @@ int d3d_prior_end(d3d_ctx *ctx);
  * device in fp64 in a fixed order: two calls return the same bits.  Works with the prior off. */
 int d3d_prior_energy(d3d_ctx *ctx, const double *params, double energy[3], int64_t *pairs);
 
+/* ---- replica exchange between tempered chains ----------------------------- */
+/* The reference runs one chain whose MH ratio is the likelihood's (lib/run.py:426-438): between
+ * two modes of c -- a wrong line, a neighbour's line, a noise spike -- it does not cross.  These
+ * entries generalise that ratio to parallel tempering: n ctxs of ONE geometry (as
+ * d3d_mh_sweeps_batch takes them) sample L^beta_r x prior at inverse temperatures
+ * 1 = beta_0 > beta_1 > ... > beta_{n-1}, and adjacent rungs trade their states with a Metropolis
+ * rule that leaves every rung's tempered posterior invariant.  The tempered posterior is the same
+ * model with the variance divided by beta: the caller gives rung r d3d_set_data(data, var /
+ * beta_r) and no sweep kernel changes -- the MH log-ratio of lib/run.py:426 scales by beta, the
+ * Gibbs draw of lib/run.py:491-496 becomes ro = ra / (1 + ra beta sum ek^2/var), mu = ro beta sum
+ * ek ul/var, the priors (ra, bounds, d3d_prior_begin) stay untempered.  A ctx that never joins a
+ * group allocates and launches nothing new. */
+typedef struct d3d_temper d3d_temper;
+
+/* A group over ctxs[0..n), rung r at betas[r].  D3D_ERR_INVALID: n outside 2..64; betas[0] != 1,
+ * betas not strictly decreasing, finite and > 0; a ctx that is NULL, appears twice, or differs
+ * from ctxs[0] in device, shape, mask, FSF, LSF, line shape or line table (the comparisons of
+ * d3d_mh_sweeps_batch).  D3D_ERR_UNSUPPORTED: a tiled, partitioned or communicator ctx, or one
+ * driven by d3d_mh_colour_lines.  D3D_ERR_STATE: taps or data not set.  seed keys the swaps'
+ * uniforms.  Allocates one small device block (energies, block partials, flags, counters,
+ * labels; labels[r] = r).  Destroy the group before any of its ctxs. */
+int d3d_temper_create(d3d_temper **t, d3d_ctx **ctxs, int n, const double *betas, uint64_t seed);
+/* One exchange round, asynchronous, on ctxs[0]'s stream (every ctx's own stream is synchronised
+ * first and its pending residual layers are written back, as d3d_mh_sweeps_batch does).  Every
+ * ctx needs a valid carried residual (D3D_ERR_STATE).  Three launches with nothing but device
+ * memory between them:
+ *   1. E_r = (sum_v 1/2 err_r[v]^2 / var_r[v]) / betas[r]: minus log L of state r under the
+ *      untempered variance, summed in fp64 in a fixed order (no floating-point atomics: a run
+ *      reproduces under its seed);
+ *   2. for the pairs (i, i+1) with i = round mod 2 (mod 2): u = the first uniform of Philox4x32-10
+ *      at counter {0xFFFFFFFF, (uint32_t)round, i, 1} under the group's seed (the chains' streams
+ *      have a last counter word of 0), accepted iff log(u) < (betas[i] - betas[i+1]) (E_i -
+ *      E_{i+1}); attempts, accepts and labels follow, and E_r -- of the state at rung r before the
+ *      exchange -- enters rung r's running (n, mean, M2);
+ *   3. an accepted pair trades SLOT_ERR (the raw padded buffer) and the (H,W,3) parameters,
+ *      nothing else: data, 1/variance, jump scales and their counters, accepted counters,
+ *      posterior accumulators, the log ratios of d3d_get_dlog and the seed belong to the RUNG.
+ * Afterwards every ctx's proposal table is stale (as after d3d_set_params) and its residual still
+ * valid; work enqueued later on the other ctxs' streams waits, on the device, for the exchange. */
+int d3d_temper_swap(d3d_temper *t, int64_t round);
+/* Rounds so far, attempts / accepts per pair [n-1], the energy moments per rung [n] (count, mean,
+ * sum of squared deviations) and labels [n]: labels[r] is the rung the state now at rung r
+ * started from.  Any pointer may be NULL.  Waits for the stream. */
+int d3d_temper_get(d3d_temper *t, int64_t *rounds, int64_t *attempts, int64_t *accepts,
+                   int64_t *energy_n, double *energy_mean, double *energy_m2, int32_t *labels);
+/* The last round: energy [n]; u, logu [n-1] (NaN for a pair not proposed); decided [n-1] (1
+ * accepted, 0 rejected, -1 not proposed).  Any pointer may be NULL.  Waits for the stream.
+ * D3D_ERR_STATE before the first round. */
+int d3d_temper_last(d3d_temper *t, double *energy, double *u, double *logu, int32_t *decided);
+int d3d_temper_destroy(d3d_temper *t);
+
 /* ---- spatial tiling (one chain over several GPUs) --------- */
 /* The reference has no counterpart (single process).  What makes tiling possible is
  * that an update at (y,x) touches only its FSF window (lib/run.py:404-419), and that
