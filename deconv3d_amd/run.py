@@ -31,13 +31,16 @@ from __future__ import annotations
 
 import logging
 import math
+import time
+from collections import namedtuple
 from os.path import splitext
 
 import numpy as np
 
-from . import _lib, adapt as _adapt, posterior as _posterior, prepare as _prepare, prior as _prior, \
-    search as _search, tempering as _tempering
+from . import _lib, adapt as _adapt, ensemble, posterior as _posterior, prepare as _prepare, \
+    prior as _prior, search as _search, tempering as _tempering
 from .cube import Cube, read_fits
+from .host_model import HostModelChain
 from .instruments import Instrument
 from .line_models import (LineModel, SingleGaussianLineModel, SINGLE_LINE_SHAPE,
                           device_line_shape, device_line_table, model_is_on_device)
@@ -47,6 +50,68 @@ logging.basicConfig(level=logging.INFO)
 logger = logging.getLogger('deconv3d')
 
 CIRCLE_4TH = np.pi / 2.
+
+# adapt.check_keywords' tuple, by name
+_AdaptKeywords = namedtuple("_AdaptKeywords", "sweeps window target gain scale_range")
+
+
+class _Acceptance:
+    """The accepted proposals the stopping rule counts (lib/run.py:344-359), of the WHOLE chain:
+    ``state`` is the ``resume_state=`` of an earlier segment, whose totals are the base this
+    segment's counts add to.  Iteration 1 of a segment counts as accepted; that of a resumed
+    segment is the resumed state itself, already counted in the state's totals."""
+
+    def __init__(self, spaxels_count, n_chains, state=None):
+        self.spaxels_count, self.n_chains = spaxels_count, n_chains
+        self.accepted_count = spaxels_count * n_chains  # first iteration counts as accepted
+        self.per_chain_accepted = [spaxels_count] * n_chains
+        self._acc_base, self._it_base, self._acc_base_chain = 0, 0, [0] * n_chains
+        if state is None:
+            return
+        files = getattr(state, "files", state)
+        # totals over every earlier segment (older checkpoints hold one segment's)
+        accepted = int(state["total_accepted"] if "total_accepted" in files else state["accepted_count"])
+        iterations = int(state["total_iterations"] if "total_iterations" in files else state["iteration"])
+        # (per chain: what the checkpoint recorded, else an even share of the total)
+        if n_chains > 1 and "per_chain_accepted" in files:
+            per_chain = [int(v) for v in state["per_chain_accepted"]]
+        else:
+            per_chain = [accepted // n_chains] * n_chains
+        self._acc_base = accepted - spaxels_count * n_chains
+        self._it_base = iterations - 1
+        self._acc_base_chain = [a - spaxels_count for a in per_chain]
+
+    def add(self, per_chain_acc):
+        """The accepted counts, one per chain, of the sweeps a call made."""
+        self.accepted_count += sum(per_chain_acc)
+        self.per_chain_accepted = [a + b for a, b in zip(self.per_chain_accepted, per_chain_acc)]
+
+    def running_rate(self, iteration):
+        """The rate the stopping rule sees before the sweep after ``iteration`` (0 while nothing
+        can be accepted: no unmasked spaxel)."""
+        max_accepted_count = self.spaxels_count * self.n_chains * (iteration + self._it_base)
+        if max_accepted_count > 0:
+            return float(self.accepted_count + self._acc_base) / float(max_accepted_count)
+        return 0.
+
+    def final_rates(self, iteration):
+        """``(pooled, [per chain])`` of a run that stopped at ``iteration``."""
+        pooled = float(self.accepted_count + self._acc_base) / \
+            float(max(self.spaxels_count * self.n_chains * (iteration + self._it_base), 1))
+        if self.n_chains == 1:
+            return pooled, [pooled]
+        return pooled, [(a + b) / float(max(self.spaxels_count * (iteration + self._it_base), 1))
+                        for a, b in zip(self.per_chain_accepted, self._acc_base_chain)]
+
+    def state_record(self, iteration):
+        """The entries of a checkpoint's state that a later segment is built from."""
+        record = dict(accepted_count=self.accepted_count,
+                      total_accepted=self.accepted_count + self._acc_base,
+                      total_iterations=iteration + self._it_base)
+        if self.n_chains > 1:
+            record["per_chain_accepted"] = np.array(
+                [a + b for a, b in zip(self.per_chain_accepted, self._acc_base_chain)], dtype=np.int64)
+        return record
 
 
 class Run:
@@ -222,6 +287,36 @@ class Run:
         smoothness=None,
         tempering=None,
     ):
+        prepare_cfg, search_cfg, posterior_burn_in, posterior_every, hist_cfg = self._check_keywords(
+            prepare, initial_search, initial_parameters, resume_state, posterior_burn_in,
+            posterior_every, posterior_histograms, adapt_sweeps, adapt_window, adapt_target,
+            adapt_gain, adapt_scale_range, smoothness, tempering, keep_one_in, write_every,
+            max_iterations, chains)
+        self._read_inputs(cube, prepare_cfg, mask, variance, device)
+        self._read_instrument(instrument)
+        self._read_model(model, jump_amplitude, gibbs_apriori_variance, seed, posterior_burn_in)
+        self._allocate_chains(chain_file)
+        start_rngs = self._starting_maps(initial_parameters)
+        # a resumed run continues the checkpointed run's sweep numbering: sweep s of
+        # this segment draws the random numbers of sweep s + origin
+        self.sweep_origin, resumed, resumed_adapt = self._read_checkpoint(resume_state)
+        self._acceptance = _Acceptance(int(np.sum(self.mask == 1)), self.n_chains, resumed)
+        self._create_engines(device)
+        self._searched_start(search_cfg, start_rngs)
+        temper_group = self._arm(refresh_every, posterior_burn_in, posterior_every, hist_cfg,
+                                 resumed_adapt, resume_state is not None)
+        last_swap_round = self._loop(min_acceptance_rate, sweeps_per_call, checkpoint, temper_group)
+        self._read_adaptation()
+        self._outputs(temper_group, last_swap_round, posterior_burn_in, hist_cfg)
+
+    # THE PHASES OF __init__, IN ITS ORDER ####################################
+
+    def _check_keywords(self, prepare, initial_search, initial_parameters, resume_state,
+                        posterior_burn_in, posterior_every, posterior_histograms, adapt_sweeps,
+                        adapt_window, adapt_target, adapt_gain, adapt_scale_range, smoothness,
+                        tempering, keep_one_in, write_every, max_iterations, chains):
+        """The keywords' own checks.  Returns the checked ``prepare=`` and ``initial_search=``,
+        the posterior schedule and the checked ``posterior_histograms=``."""
         # (before anything else: no device work yet)
         prepare_cfg = _prepare.check_keywords(prepare)
         search_cfg = _search.check_keywords(initial_search, initial_parameters, resume_state)
@@ -231,12 +326,12 @@ class Run:
         hist_cfg = _posterior.check_histograms(posterior_histograms, posterior_burn_in)
         adapt_cfg = None
         if adapt_sweeps is not None:
-            adapt_cfg = _adapt.check_keywords(adapt_sweeps, adapt_window, adapt_target, adapt_gain,
-                                              adapt_scale_range)
-            if posterior_burn_in is not None and posterior_burn_in < adapt_cfg[0]:
+            adapt_cfg = _AdaptKeywords(*_adapt.check_keywords(adapt_sweeps, adapt_window, adapt_target,
+                                                              adapt_gain, adapt_scale_range))
+            if posterior_burn_in is not None and posterior_burn_in < adapt_cfg.sweeps:
                 raise ValueError("posterior_burn_in=%d lies before adapt_sweeps=%d: the moments of a "
                                  "chain that is still adapting are not posterior moments"
-                                 % (posterior_burn_in, adapt_cfg[0]))
+                                 % (posterior_burn_in, adapt_cfg.sweeps))
         self._adapt_cfg = adapt_cfg
         self.smoothness = _prior.check_keywords(smoothness)
         temper_cfg = self.tempering_cfg = _tempering.check_keywords(tempering)
@@ -254,11 +349,15 @@ class Run:
         if temper_cfg is not None:          # (the rungs take the chains' place: rung r is chain r)
             n_chains = len(temper_cfg["betas"])
         self.n_chains = n_chains
-        if adapt_cfg is not None and adapt_cfg[0] > 0.8 * self.max_iterations:
+        if adapt_cfg is not None and adapt_cfg.sweeps > 0.8 * self.max_iterations:
             logger.warning("adapt_sweeps=%d is beyond 80 %% of max_iterations=%d: extract_parameters "
                            "averages the last 20 %% of the chain, part of which is still adapting"
-                           % (adapt_cfg[0], self.max_iterations))
+                           % (adapt_cfg.sweeps, self.max_iterations))
+        return prepare_cfg, search_cfg, posterior_burn_in, posterior_every, hist_cfg
 
+    def _read_inputs(self, cube, prepare_cfg, mask, variance, device):
+        """``run.cube`` (prepared, with ``prepare=``), ``run.mask``, ``run.variance_cube`` and
+        ``run.error_cube``."""
         # ---- input cube (lib/run.py:119-143) --------------------------------
         if isinstance(cube, str):
             cube = Cube.from_fits(cube)
@@ -298,8 +397,6 @@ class Run:
                              % (cube_height, cube_width, str(mask.shape)))
         mask[np.isnan(np.sum(self.cube.data, 0))] = 0
         self.mask = mask
-        spaxels_count = int(np.sum(self.mask == 1))
-        cnt_iterations = int(math.ceil(max_iterations / float(keep_one_in)))
 
         # ---- variance (lib/run.py:170-200) ---------------------------------
         if variance is not None:
@@ -326,7 +423,9 @@ class Run:
         self.variance_cube = variance_cube
         self.error_cube = np.sqrt(self.variance_cube)
 
-        # ---- instrument and taps (lib/run.py:202-224) ------------------------
+    def _read_instrument(self, instrument):
+        """Instrument and taps (lib/run.py:202-224): ``run.instrument``, ``run.lsf``, ``run.fsf``."""
+        cube_depth = self.cube.data.shape[0]
         if not isinstance(instrument, Instrument):
             raise TypeError("Provided instrument is not an Instrument")
         self.instrument = instrument
@@ -339,31 +438,37 @@ class Run:
             raise ValueError("LSF must have the length of the cube's spectral axis (%d), got %s"
                              % (cube_depth, str(self.lsf.shape)))
 
-        # ---- model (lib/run.py:226-265) --------------------------------------
+    def _refuse_host_model(self, what, reason=None):
+        """The refusal of a keyword or method that needs a line model the device evaluates."""
+        sentence = "%s: the line model %s is evaluated on the host" % (what, type(self.model).__name__)
+        raise NotImplementedError(sentence if reason is None else "%s; %s" % (sentence, reason))
+
+    def _read_model(self, model, jump_amplitude, gibbs_apriori_variance, seed, posterior_burn_in):
+        """Model (lib/run.py:226-265): ``run.model``, what the device needs of it, its bounds and
+        the jump amplitudes; and the keywords a host-evaluated model cannot honour."""
         if isinstance(model, LineModel):
             self.model = model
         else:
             self.model = model()
             if not isinstance(self.model, LineModel):
                 raise TypeError("Provided model is not a LineModel")
-        self._host_model = not self._model_is_on_device()
+        # The HIP kernels evaluate SingleGaussianLineModel and GaussianMultipletLineModel
+        # themselves (line_models.model_is_on_device: subclasses may change names/bounds but
+        # not the curve or the Gibbs index); any other LineModel plugin is evaluated on the
+        # host (host_model.HostModelChain): same device kernels for LSF, window statistics,
+        # accept, Gibbs draw and residual, but python-speed proposals and modelize() calls.
+        self._host_model = not model_is_on_device(self.model)
         if posterior_burn_in is not None and self._host_model:
-            raise NotImplementedError(
-                "posterior_burn_in=: the line model %s is evaluated on the host; the device "
-                "accumulates posterior moments only for the models it evaluates itself"
-                % type(self.model).__name__)
+            self._refuse_host_model("posterior_burn_in=", "the device accumulates posterior moments "
+                                    "only for the models it evaluates itself")
         _prior.check_fsf(self.smoothness, self.fsf.shape)
         if self.smoothness is not None and self._host_model:
-            raise NotImplementedError(
-                "smoothness=: the line model %s is evaluated on the host; the device knows the "
-                "prior only for the (a, c, w) of the models it evaluates itself"
-                % type(self.model).__name__)
-        _tempering.check_run(temper_cfg, 1, self._host_model, type(self.model).__name__)
-        if adapt_cfg is not None and self._host_model:
-            raise NotImplementedError(
-                "adapt_sweeps=: the line model %s is evaluated on the host; the device "
-                "adapts jump scales only for the models it evaluates itself"
-                % type(self.model).__name__)
+            self._refuse_host_model("smoothness=", "the device knows the prior only for the "
+                                    "(a, c, w) of the models it evaluates itself")
+        _tempering.check_run(self.tempering_cfg, 1, self._host_model, type(self.model).__name__)
+        if self._adapt_cfg is not None and self._host_model:
+            self._refuse_host_model("adapt_sweeps=", "the device adapts jump scales only for the "
+                                    "models it evaluates itself")
         # (offsets, ratios) of the device's unit line; None for a host-evaluated model
         self.line_shape = None if self._host_model else device_line_shape(self.model)
         # (table, support, flux_factor) of a tabulated line and the digest a checkpoint records
@@ -394,14 +499,17 @@ class Run:
         self.gibbs_apriori_variance = gibbs_apriori_variance
         self.seed = int(seed)
 
-        # ---- chain storage (lib/run.py:267-281), NaN instead of garbage ------
+    def _allocate_chains(self, chain_file):
+        """Chain storage (lib/run.py:267-281), NaN instead of garbage: ``run.chains`` and
+        ``run.all_likelihoods``, in memory or mapped to ``chain_file``'s."""
         # (one chain array per chain; chain r > 0 of a memory-mapped run lives in <prefix>_c<r>_*)
+        cnt_iterations = int(math.ceil(self.max_iterations / float(self.keep_one_in)))
         self._chain_file = chain_file
         self._likelihoods_maps = []
-        self.chains, all_likelihoods = [], []
+        self.chains, self.all_likelihoods = [], []
         try:
-            chain_shape = (cnt_iterations, cube_height, cube_width, parameters_count)
-            for r in range(n_chains):
+            chain_shape = (cnt_iterations,) + self.mask.shape + (len(self.model.parameters()),)
+            for r in range(self.n_chains):
                 if chain_file is not None:
                     # pages are created as saved sweeps arrive; slots never written (early
                     # stop) are NaN-filled at the end like the in-memory chain
@@ -417,18 +525,23 @@ class Run:
                     ch = np.full(chain_shape, np.nan)
                     lk = np.full(chain_shape[:3], np.nan)
                 self.chains.append(ch)
-                all_likelihoods.append(lk)
+                self.all_likelihoods.append(lk)
         except MemoryError:
             self.logger.error("Not enough RAM available for that many iterations. "
                               "Use a higher value in the keep_one_in= parameter.")
             raise
         self.chain = self.chains[0]
-        likelihoods = all_likelihoods[0]
-        self._likelihoods_map = self._likelihoods_maps[0] if self._likelihoods_maps else None
+        self.likelihoods = self.all_likelihoods[0]
 
-        # ---- initial parameters (lib/run.py:293-314) -------------------------
+    def _starting_maps(self, initial_parameters):
+        """Initial parameters (lib/run.py:293-314), slot 0 of every chain: the given map(s), or
+        uniform draws within the bounds.  Returns the generators that drew (one per chain), which
+        ``initial_search=`` goes on drawing from."""
         # (chain r draws its start from the generator of seed + r: it is the chain of
         # Run(..., seed=seed + r))
+        cube_height, cube_width = self.mask.shape
+        parameters_count = self.chain.shape[3]
+        n_chains, start_rngs = self.n_chains, []
         if initial_parameters is not None:
             if isinstance(initial_parameters, str):
                 initial_parameters = np.load(initial_parameters)
@@ -449,67 +562,19 @@ class Run:
             for r in range(n_chains):
                 self.chains[r][0] = initial_parameters[r] if per_chain else initial_parameters
         else:
-            start_rngs = []
             for r in range(n_chains):
                 start_rngs.append(np.random.default_rng(self.seed + r))
                 draws = start_rngs[r].random((cube_height, cube_width, parameters_count))
-                self.chains[r][0] = min_boundaries + (max_boundaries - min_boundaries) * draws
+                self.chains[r][0] = self.min_boundaries + \
+                    (self.max_boundaries - self.min_boundaries) * draws
+        return start_rngs
 
-        # a resumed run continues the checkpointed run's sweep numbering: sweep s of
-        # this segment draws the random numbers of sweep s + origin
-        self.sweep_origin = 0
-        resumed_accepted = None
-        resumed_per_chain = None
-        resumed_adapt = None
-        if resume_state is not None:
-            state = np.load(resume_state) if isinstance(resume_state, str) else resume_state
-            files = getattr(state, "files", state)
-            saved_chains = int(state["n_chains"]) if "n_chains" in files else 1
-            if saved_chains != n_chains:
-                raise ValueError("resume_state holds %d chain(s), this run has chains=%d"
-                                 % (saved_chains, n_chains))
-            if int(state["seed"]) != self.seed:
-                self.logger.warning("resume_state was written with seed %d, this run uses %d"
-                                    % (int(state["seed"]), self.seed))
-            self.sweep_origin = int(state["sweep_origin"]) + int(state["iteration"]) - 1
-            resumed_adapt = _adapt.check_resume(state, files, adapt_cfg, n_chains,
-                                                (cube_height, cube_width))
-            _prior.check_resume(state, files, self.smoothness)
-            _tempering.check_resume(state, files, temper_cfg)
-            _prepare.check_resume(state, files,
-                                  None if self.prepared is None else self.prepared.settings)
-            # totals over every earlier segment (older checkpoints hold one segment's)
-            resumed_accepted = (
-                int(state["total_accepted"] if "total_accepted" in files else state["accepted_count"]),
-                int(state["total_iterations"] if "total_iterations" in files else state["iteration"]))
-            if n_chains > 1 and "per_chain_accepted" in files:
-                resumed_per_chain = [int(v) for v in state["per_chain_accepted"]]
-            # (a checkpoint without a line shape was written by a single-Gaussian run)
-            if self.line_shape is not None:
-                saved = SINGLE_LINE_SHAPE
-                if "line_offsets" in files:
-                    saved = (state["line_offsets"], state["line_ratios"])
-                if not (np.array_equal(np.asarray(saved[0], dtype=np.float64),
-                                       np.asarray(self.line_shape[0], dtype=np.float64))
-                        and np.array_equal(np.asarray(saved[1], dtype=np.float64),
-                                           np.asarray(self.line_shape[1], dtype=np.float64))):
-                    raise ValueError("resume_state was written with the line shape offsets %s, "
-                                     "ratios %s; this run's model has offsets %s, ratios %s"
-                                     % (tuple(np.ravel(saved[0])), tuple(np.ravel(saved[1])),
-                                        self.line_shape[0], self.line_shape[1]))
-                # (a checkpoint without a table digest was written by a run of Gaussians)
-                saved_digest = str(state["line_table_digest"]) if "line_table_digest" in files else None
-                if saved_digest != self.line_table_digest:
-                    raise ValueError("resume_state was written with %s; this run's model has %s"
-                                     % ("Gaussian lines" if saved_digest is None
-                                        else "the line table " + saved_digest[:16],
-                                        "Gaussian lines" if self.line_table_digest is None
-                                        else "the line table " + self.line_table_digest[:16]))
-
-        # ---- device context ----------------------------------------------
+    def _create_engines(self, device):
+        """Device context: ``run.engines``, one per chain, holding the taps, the data and the line."""
+        temper_cfg = self.tempering_cfg
         self.engines = []
-        for r in range(n_chains):
-            eng = _lib.Engine(cube_shape, self.fsf.shape, device=device)
+        for r in range(self.n_chains):
+            eng = _lib.Engine(self.cube.data.shape, self.fsf.shape, device=device)
             self.engines.append(eng)
             eng.set_taps(self.fsf, self.lsf)
             # (tempering=: rung r samples L^beta_r x prior, the same model with the variance / beta_r)
@@ -520,34 +585,40 @@ class Run:
             if self.line_table is not None:
                 eng.set_line_table(*self.line_table)
         self.engine = self.engines[0]
-        # ---- searched start (initial_search=): chain 0 from the matched-filter map, chains
-        # r > 0 from jittered copies; spaxels without a detection keep their uniform draw
+
+    def _searched_start(self, search_cfg, start_rngs):
+        """Searched start (initial_search=), ``run.search``: chain 0 from the matched-filter map, chains
+        r > 0 from jittered copies; spaxels without a detection keep their uniform draw."""
         self.search = None
         if search_cfg is not None:
             self.search = _search.search_engine(self.engine, self.model, self, search_cfg["centres"],
                                                 search_cfg["widths"], self.lsf)
             found = self.search.detected & (self.mask == 1)
-            for r in range(n_chains):
+            for r in range(self.n_chains):
                 start = self.search.parameters if r == 0 else _search.jittered_start(
                     self.search.parameters, search_cfg["jitter"], start_rngs[r],
-                    min_boundaries, max_boundaries)
+                    self.min_boundaries, self.max_boundaries)
                 self.chains[r][0][found] = start[found]
-        host_chain = None
+
+    def _arm(self, refresh_every, posterior_burn_in, posterior_every, hist_cfg, resumed_adapt, resumed):
+        """Everything the first sweep needs: the host chains, or the engines' parameters, sampler
+        settings, accumulators and residual.  Returns the ``tempering=`` group, or None."""
+        n_chains, temper_cfg, adapt_cfg = self.n_chains, self.tempering_cfg, self._adapt_cfg
         if self._host_model:
-            from .host_model import HostModelChain
             self.logger.info("Line model %s is evaluated on the host (slower path)."
                              % type(self.model).__name__)
             # (chains=R: one host chain per engine, seeds seed + r, advanced one after the other)
             self._host_chains = [
-                HostModelChain(self, self.engines[r], self.chains[r][0], min_boundaries,
-                               max_boundaries, jumping_amplitude, gibbs_apriori_variance,
-                               self.seed + r, refresh_every) for r in range(n_chains)]
-            host_chain = self._host_chain = self._host_chains[0]
+                HostModelChain(self, self.engines[r], self.chains[r][0], self.min_boundaries,
+                               self.max_boundaries, self.jumping_amplitude,
+                               self.gibbs_apriori_variance, self.seed + r, refresh_every)
+                for r in range(n_chains)]
+            self._host_chain = self._host_chains[0]
         else:
             for r, eng in enumerate(self.engines):
                 eng.set_params(self.chains[r][0])
-                eng.mh_config(min_boundaries, max_boundaries, jumping_amplitude,
-                              gibbs_apriori_variance, seed=self.seed + r,
+                eng.mh_config(self.min_boundaries, self.max_boundaries, self.jumping_amplitude,
+                              self.gibbs_apriori_variance, seed=self.seed + r,
                               refresh_every=refresh_every)
                 if posterior_burn_in is not None and (temper_cfg is None or r == 0):
                     eng.post_begin()
@@ -557,18 +628,15 @@ class Run:
                 if adapt_cfg is not None:
                     # (the last adapted sweep in the numbering of the whole run: a resumed
                     # segment counts from its sweep origin)
-                    eng.adapt_begin(adapt_cfg[2], adapt_cfg[1], adapt_cfg[0], adapt_cfg[3], adapt_cfg[4])
+                    eng.adapt_begin(adapt_cfg.target, adapt_cfg.window, adapt_cfg.sweeps,
+                                    adapt_cfg.gain, adapt_cfg.scale_range)
                     if resumed_adapt is not None:
                         eng.adapt_set(*resumed_adapt[r])
                 if self.smoothness is not None:
                     eng.prior_begin(_prior.lam_of(self.smoothness))
-        if resume_state is not None:
-            if host_chain is None:
-                for eng in self.engines:
-                    eng.set_sweep_origin(self.sweep_origin)
-            else:
-                for hc in self._host_chains:
-                    hc.set_sweep_origin(self.sweep_origin)
+        if resumed:
+            for chain in self._host_chains if self._host_model else self.engines:
+                chain.set_sweep_origin(self.sweep_origin)
         if hist_cfg is not None:
             reachable = len(range(posterior_burn_in, self.max_iterations, posterior_every))
             if reachable <= hist_cfg["pilot"]:
@@ -580,48 +648,37 @@ class Run:
                                  "run.posteriors[r].histograms are per chain and the pooled "
                                  "run.posterior.histograms is None")
         self.logger.info("Iteration #1")
-        if host_chain is None:
+        if not self._host_model:
             for eng in self.engines:
                 eng.residual(fetch=False)              # lib/run.py:317-334
         # tempering=: the group that exchanges the rungs' states on the device.  The round of the
         # exchange after sweep s is (s + sweep_origin) // swap_every: a resumed run continues the
         # numbering, so no uniform is drawn twice.
-        temper_group, last_swap_round = None, None
         if temper_cfg is not None:
-            temper_group = _lib.TemperGroup(self.engines, temper_cfg["betas"], seed=self.seed)
+            return _lib.TemperGroup(self.engines, temper_cfg["betas"], seed=self.seed)
+        return None
 
-        # ---- MH within Gibbs loop (lib/run.py:336-537) -------------------------
+    def _loop(self, min_acceptance_rate, sweeps_per_call, checkpoint, temper_group):
+        """MH within Gibbs loop (lib/run.py:336-537): the sweeps, up to ``max_iterations`` or to where
+        the stopping rule ends them, and the checkpoints on the way.  Returns the round of the last
+        ``tempering=`` exchange, or None."""
+        max_iterations, temper_cfg, acceptance = self.max_iterations, self.tempering_cfg, self._acceptance
         cur_iteration = 1
         cur_acceptance_rate = 0.
-        accepted_count = spaxels_count * n_chains  # first iteration counts as accepted
-        per_chain_accepted = [spaxels_count] * n_chains
-        # (accepted, iterations) of earlier segments: the running acceptance rate of the
-        # stopping rule (lib/run.py:344-359) is that of the WHOLE chain.  This segment's
-        # iteration 1 is the resumed state itself, already counted there.
-        self._resumed_from = resumed_accepted
-        import time as _time
+        last_swap_round = None
         self.mh_seconds = 0.0                      # wall time of the device calls of the loop
-        self._acc_base = resumed_accepted[0] - spaxels_count * n_chains if resumed_accepted else 0
-        self._it_base = resumed_accepted[1] - 1 if resumed_accepted else 0
-        # (per chain: what the checkpoint recorded, else an even share of the total)
-        if resumed_accepted and resumed_per_chain is None:
-            resumed_per_chain = [resumed_accepted[0] // n_chains] * n_chains
-        self._acc_base_chain = [a - spaxels_count for a in resumed_per_chain] if resumed_accepted \
-            else [0] * n_chains
         # the reference re-evaluates the stopping rule (and logs) every sweep
         # (lib/run.py:344-364): one sweep per device call whenever the rule is
         # armed, so that the run stops exactly where the reference would; with
         # min_acceptance_rate <= 0 sweeps are batched up to the next saved one
         if sweeps_per_call is None:
-            sweeps_per_call = 1 if min_acceptance_rate > 0 else max(1, min(int(keep_one_in), 64))
-        if host_chain is not None:
+            sweeps_per_call = 1 if min_acceptance_rate > 0 else max(1, min(self.keep_one_in, 64))
+        if self._host_model:
             sweeps_per_call = 1
         self.iterations_done = 1
         while cur_iteration < max_iterations and \
                 (cur_acceptance_rate > min_acceptance_rate or cur_acceptance_rate == 0.):
-            max_accepted_count = spaxels_count * n_chains * (cur_iteration + self._it_base)
-            if max_accepted_count > 0:
-                cur_acceptance_rate = float(accepted_count + self._acc_base) / float(max_accepted_count)
+            cur_acceptance_rate = acceptance.running_rate(cur_iteration)
             n = min(sweeps_per_call, max_iterations - cur_iteration)
             swap_round = None
             if temper_cfg is not None:      # (a call ends at every sweep an exchange follows)
@@ -629,56 +686,60 @@ class Run:
                                                             temper_cfg["swap_every"])
             self.logger.info("Iteration #%d / %d, %2.0f%%" %
                              (cur_iteration + 1, max_iterations, 100 * cur_acceptance_rate))
-            if host_chain is not None:
-                save = cur_iteration % keep_one_in == 0
-                slot = cur_iteration // keep_one_in
-                acc = [hc.sweep(cur_iteration, all_likelihoods[r][slot] if save else None)
-                       for r, hc in enumerate(self._host_chains)]
-                accepted_count += sum(acc)
-                per_chain_accepted = [a + b for a, b in zip(per_chain_accepted, acc)]
-                if save:
-                    for r, hc in enumerate(self._host_chains):
-                        self.chains[r][slot] = hc.params
-            elif n_chains == 1:
-                t_call = _time.perf_counter()
-                accepted_count += self.engine.mh_sweeps(n, cur_iteration, keep_one_in,
-                                                        self.chain, likelihoods)
-                self.mh_seconds += _time.perf_counter() - t_call
-            else:
-                t_call = _time.perf_counter()
-                acc = self._sweep_chains(n, cur_iteration, all_likelihoods)
-                self.mh_seconds += _time.perf_counter() - t_call
-                accepted_count += sum(acc)
-                per_chain_accepted = [a + b for a, b in zip(per_chain_accepted, acc)]
-                if swap_round is not None:     # (the sweep's chain slot is saved: the rungs trade states)
-                    t_call = _time.perf_counter()
-                    temper_group.swap(swap_round)
-                    last_swap_round = swap_round
-                    self.mh_seconds += _time.perf_counter() - t_call
+            acceptance.add(self._advance(n, cur_iteration, temper_group, swap_round))
+            if swap_round is not None:
+                last_swap_round = swap_round
             before = cur_iteration
             cur_iteration += n
             # write_every: documented (lib/run.py:89-92) but never used by the
             # reference; here it is the checkpoint cadence when a path is given
-            if checkpoint is not None and before // write_every != cur_iteration // write_every:
+            if checkpoint is not None and \
+                    before // self.write_every != cur_iteration // self.write_every:
                 self.iterations_done = cur_iteration
-                self._write_checkpoint(checkpoint, cur_iteration, accepted_count, per_chain_accepted)
+                self._write_checkpoint(checkpoint, cur_iteration)
         self.iterations_done = cur_iteration
-        self.acceptance_rate = float(accepted_count + self._acc_base) / \
-            float(max(spaxels_count * n_chains * (cur_iteration + self._it_base), 1))
-        if n_chains > 1:
-            self.acceptance_rates = [(a + b) / float(max(spaxels_count * (cur_iteration + self._it_base), 1))
-                                     for a, b in zip(per_chain_accepted, self._acc_base_chain)]
-        else:
-            self.acceptance_rates = [self.acceptance_rate]
-        if chain_file is not None:
-            n_valid = (cur_iteration - 1) // self.keep_one_in + 1
-            for ch, lk in zip(self.chains, all_likelihoods):
+        self.acceptance_rate, self.acceptance_rates = acceptance.final_rates(cur_iteration)
+        if self._chain_file is not None:
+            n_valid = self._n_valid(cur_iteration)
+            for ch, lk in zip(self.chains, self.all_likelihoods):
                 ch[n_valid:] = np.nan
                 lk[n_valid:] = np.nan
                 ch.flush()
                 lk.flush()
+        return last_swap_round
 
-        # ---- jump scales and acceptance-rate maps (adapt_sweeps=) ----------------
+    def _advance(self, n, first, temper_group=None, swap_round=None):
+        """Sweeps ``first .. first + n - 1`` of every chain, whatever carries them, and then the
+        exchange of round ``swap_round`` between the rungs.  Returns the accepted counts, one per
+        chain.  ``run.mh_seconds`` takes the wall time of the device calls; the host-evaluated
+        chains (one sweep per call) are not timed."""
+        if self._host_model:
+            save = first % self.keep_one_in == 0
+            slot = first // self.keep_one_in
+            acc = [hc.sweep(first, self.all_likelihoods[r][slot] if save else None)
+                   for r, hc in enumerate(self._host_chains)]
+            if save:
+                for r, hc in enumerate(self._host_chains):
+                    self.chains[r][slot] = hc.params
+            return acc
+        if self.n_chains == 1:
+            t_call = time.perf_counter()
+            acc = self.engine.mh_sweeps(n, first, self.keep_one_in, self.chain, self.likelihoods)
+            self.mh_seconds += time.perf_counter() - t_call
+            return [acc]
+        t_call = time.perf_counter()
+        acc = self._sweep_chains(n, first, self.all_likelihoods)
+        self.mh_seconds += time.perf_counter() - t_call
+        if swap_round is not None:     # (the sweep's chain slot is saved: the rungs trade states)
+            t_call = time.perf_counter()
+            temper_group.swap(swap_round)
+            self.mh_seconds += time.perf_counter() - t_call
+        return acc
+
+    def _read_adaptation(self):
+        """Jump scales and acceptance-rate maps (adapt_sweeps=): ``run.jump_scales``,
+        ``run.acceptance_maps`` and ``run.adapted_until``."""
+        adapt_cfg = self._adapt_cfg
         self.jump_scales = self.acceptance_maps = None
         self.jump_scale = self.acceptance_map = self.adapted_until = None
         if adapt_cfg is not None:
@@ -689,14 +750,15 @@ class Run:
                     rate = acc / float(n_win) if n_win > 0 else np.full(scale.shape, np.nan)
                 self.jump_scales.append(scale)
                 self.acceptance_maps.append(np.where(self.mask == 1, rate, np.nan))
-                self.adapted_until = int(k) * adapt_cfg[1]
+                self.adapted_until = int(k) * adapt_cfg.window
             self.jump_scale, self.acceptance_map = self.jump_scales[0], self.acceptance_maps[0]
 
-        # ---- outputs (lib/run.py:539-549) ------------------------------------
-        self.likelihoods = likelihoods
-        self.all_likelihoods = all_likelihoods
+    def _outputs(self, temper_group, last_swap_round, posterior_burn_in, hist_cfg):
+        """Outputs (lib/run.py:539-549): ``run.rhat``, ``run.tempering``, ``run.parameters``, the two
+        cubes and the posteriors."""
+        cube, cube_shape, temper_cfg = self.cube, self.cube.data.shape, self.tempering_cfg
         # (tempering=: the rungs sample different distributions)
-        self.rhat = self.gelman_rubin() if n_chains > 1 and temper_cfg is None else None
+        self.rhat = self.gelman_rubin() if self.n_chains > 1 and temper_cfg is None else None
         self.tempering = None
         if temper_group is not None:
             self.tempering = _tempering.TemperingReport.from_group(temper_group, temper_cfg["betas"],
@@ -724,22 +786,13 @@ class Run:
 
     # ------------------------------------------------------------------------
 
-    def _model_is_on_device(self):
-        """The HIP kernels evaluate SingleGaussianLineModel and GaussianMultipletLineModel
-        themselves (line_models.model_is_on_device: subclasses may change names/bounds but
-        not the curve or the Gibbs index); any other LineModel plugin is evaluated on the
-        host (host_model.HostModelChain): same device kernels for LSF, window statistics,
-        accept, Gibbs draw and residual, but python-speed proposals and modelize() calls."""
-        return model_is_on_device(self.model)
-
     def roughness(self, parameters=None):
         """``(E_a, E_c, E_w, pairs)``: the sums of squared differences between horizontally and
         vertically adjacent unmasked spaxels of an (H, W, 3) parameter map, and the number of such
         pairs -- what ``smoothness=`` penalises, summed on the device (d3d_prior_energy).
         ``parameters=None``: ``run.parameters``, the extracted map."""
         if self._host_model:
-            raise NotImplementedError("roughness(): the line model %s is evaluated on the host"
-                                      % type(self.model).__name__)
+            self._refuse_host_model("roughness()")
         if parameters is None:
             parameters = self.parameters
         parameters = np.asarray(getattr(parameters, "data", parameters), dtype=np.float64)
@@ -750,7 +803,6 @@ class Run:
         library can (d3d_mh_sweeps_batch: cubes up to 256 channels -- a small cube's launch
         carries R times the windows for about the same latency), else the chains' own
         launches on their own streams, enqueued concurrently (ensemble.sweep_chains)."""
-        from . import ensemble
         if getattr(self, "_batched", True):
             try:
                 acc = ensemble.sweep_chains_batched(self.engines, n, first, self.keep_one_in,
@@ -771,7 +823,7 @@ class Run:
         if self.n_chains < 2 or self.tempering_cfg is not None:
             raise ValueError("R-hat needs chains >= 2 (the rungs of tempering= sample different "
                              "distributions)")
-        n_valid = min((self.iterations_done - 1) // self.keep_one_in + 1, self.chain.shape[0])
+        n_valid = min(self._n_valid(self.iterations_done), self.chain.shape[0])
         if n_valid < 2:                          # (a variance needs two saved samples)
             return np.full(self.chain.shape[1:], np.nan)
         first = min(int((100. - percentage) * n_valid / 100.), n_valid - 2)
@@ -782,7 +834,61 @@ class Run:
             between = tail.mean(axis=1).var(axis=0, ddof=1)
             return np.sqrt(((n - 1.) / n * within + between) / within)
 
-    def _write_checkpoint(self, name, iteration, accepted_count, per_chain_accepted=None):
+    def _n_valid(self, iteration):
+        """The chain slots written once sweep ``iteration`` is done: slot 0 is the start."""
+        return (iteration - 1) // self.keep_one_in + 1
+
+    # (what test_gpu_run reads of the whole-chain accounting of a resumed run)
+    _acc_base = property(lambda self: self._acceptance._acc_base)
+    _it_base = property(lambda self: self._acceptance._it_base)
+
+    def _read_checkpoint(self, resume_state):
+        """``resume_state=``, the ``<name>_state.npz`` that `_write_checkpoint` wrote: refuses a
+        state this run cannot continue, and returns the sweep origin of this segment, the state
+        (whose accepted counts `_Acceptance` goes on from) and what `adapt.check_resume` restores
+        per chain -- ``(0, None, None)`` without one.  No device work."""
+        if resume_state is None:
+            return 0, None, None
+        state = np.load(resume_state) if isinstance(resume_state, str) else resume_state
+        files = getattr(state, "files", state)
+        saved_chains = int(state["n_chains"]) if "n_chains" in files else 1
+        if saved_chains != self.n_chains:
+            raise ValueError("resume_state holds %d chain(s), this run has chains=%d"
+                             % (saved_chains, self.n_chains))
+        if int(state["seed"]) != self.seed:
+            self.logger.warning("resume_state was written with seed %d, this run uses %d"
+                                % (int(state["seed"]), self.seed))
+        sweep_origin = int(state["sweep_origin"]) + int(state["iteration"]) - 1
+        resumed_adapt = _adapt.check_resume(state, files, self._adapt_cfg, self.n_chains,
+                                            self.mask.shape)
+        _prior.check_resume(state, files, self.smoothness)
+        _tempering.check_resume(state, files, self.tempering_cfg)
+        _prepare.check_resume(state, files,
+                              None if self.prepared is None else self.prepared.settings)
+        # (a checkpoint without a line shape was written by a single-Gaussian run)
+        if self.line_shape is not None:
+            saved = SINGLE_LINE_SHAPE
+            if "line_offsets" in files:
+                saved = (state["line_offsets"], state["line_ratios"])
+            if not (np.array_equal(np.asarray(saved[0], dtype=np.float64),
+                                   np.asarray(self.line_shape[0], dtype=np.float64))
+                    and np.array_equal(np.asarray(saved[1], dtype=np.float64),
+                                       np.asarray(self.line_shape[1], dtype=np.float64))):
+                raise ValueError("resume_state was written with the line shape offsets %s, "
+                                 "ratios %s; this run's model has offsets %s, ratios %s"
+                                 % (tuple(np.ravel(saved[0])), tuple(np.ravel(saved[1])),
+                                    self.line_shape[0], self.line_shape[1]))
+            # (a checkpoint without a table digest was written by a run of Gaussians)
+            saved_digest = str(state["line_table_digest"]) if "line_table_digest" in files else None
+            if saved_digest != self.line_table_digest:
+                raise ValueError("resume_state was written with %s; this run's model has %s"
+                                 % ("Gaussian lines" if saved_digest is None
+                                    else "the line table " + saved_digest[:16],
+                                    "Gaussian lines" if self.line_table_digest is None
+                                    else "the line table " + self.line_table_digest[:16]))
+        return sweep_origin, state, resumed_adapt
+
+    def _write_checkpoint(self, name, iteration):
         """`<name>_parameters.npy` (current map, reusable as initial_parameters,
         lib/run.py:790-797), `<name>_chain.npy` (slots written so far) and
         `<name>_state.npz` (iteration, seed, accepted count, `n_valid` = chain slots
@@ -793,17 +899,11 @@ class Run:
         ``chains=R``: the parameter file holds the R maps, (R, H, W, P) -- what
         `initial_parameters=` takes for R chains --, chain r > 0 goes to
         `<name>_c<r>_chain.npy`, and the state records the chains' own accepted counts."""
-        n_valid = (iteration - 1) // self.keep_one_in + 1
-        state = dict(iteration=iteration, seed=self.seed,
-                     accepted_count=accepted_count, sweep_origin=self.sweep_origin,
-                     keep_one_in=self.keep_one_in,
-                     total_accepted=accepted_count + self._acc_base,
-                     total_iterations=iteration + self._it_base,
-                     n_valid=n_valid, n_chains=self.n_chains,
+        n_valid = self._n_valid(iteration)
+        state = dict(iteration=iteration, seed=self.seed, sweep_origin=self.sweep_origin,
+                     keep_one_in=self.keep_one_in, n_valid=n_valid, n_chains=self.n_chains,
                      chain_file="" if self._chain_file is None else str(self._chain_file))
-        if self.n_chains > 1:
-            state["per_chain_accepted"] = np.array(
-                [a + b for a, b in zip(per_chain_accepted, self._acc_base_chain)], dtype=np.int64)
+        state.update(self._acceptance.state_record(iteration))
         if self.line_shape is not None:     # (resume_state= checks it)
             state["line_offsets"] = np.array(self.line_shape[0], dtype=np.float64)
             state["line_ratios"] = np.array(self.line_shape[1], dtype=np.float64)
@@ -839,7 +939,7 @@ class Run:
                 prefix = name if r == 0 else "%s_c%d" % (name, r)
                 np.save("%s_chain.npy" % prefix, ch[:n_valid])
         self.logger.info("checkpoint at iteration %d (%d accepted) -> %s_*.npy"
-                         % (iteration, accepted_count, name))
+                         % (iteration, state["accepted_count"], name))
 
     # ITERATORS ###############################################################
 
@@ -864,8 +964,7 @@ class Run:
     def extract_parameters(self, percentage=20.):
         """Mean of the last ``percentage`` % of the saved chain -- of every chain with
         ``chains=R`` -- (lib/run.py:581-593); slots never written (early stop) are ignored."""
-        n_valid = (self.iterations_done - 1) // self.keep_one_in + 1
-        n_valid = max(1, min(n_valid, self.chain.shape[0]))
+        n_valid = max(1, min(self._n_valid(self.iterations_done), self.chain.shape[0]))
         s = int((100. - percentage) * n_valid / 100.)
         if self.n_chains == 1 or self.tempering_cfg is not None:     # (tempering=: rung 0 alone)
             return np.nanmean(self.chain[s:n_valid, ...], 0)
