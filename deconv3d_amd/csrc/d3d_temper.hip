@@ -35,6 +35,8 @@ struct TemperBlock {
 // order: every lane walks the cube in double2 steps of the whole grid, the wavefront adds its 64
 // lanes by shuffles, the workgroup its four wavefronts through LDS.  The padded channels of the
 // (HW, Dp) layout are read like the others: they hold zero residual, as k_chi2_map relies on.
+// (elems = HW * Dp and Dp is always even, so the odd-element branches below cannot be reached
+// through the C ABI and no test runs them; they keep the kernel right for any span.)
 static __global__ __launch_bounds__(TEMPER_NT) void k_temper_energy(TemperChains C, size_t elems,
                                                                     double *__restrict__ partials) {
     __shared__ double part[TEMPER_NT / 64];
@@ -135,7 +137,8 @@ static __global__ __launch_bounds__(TEMPER_NT) void k_temper_decide(TemperChains
     }
 }
 
-// a[0..n) <-> b[0..n) in 16-byte steps of the whole grid; an odd last element by one thread
+// a[0..n) <-> b[0..n) in 16-byte steps of the whole grid; an odd last element by one thread (the
+// parameter map of an odd number of spaxels: HW * 3 odd; never the cube, whose Dp is even)
 __device__ __forceinline__ void swap_span(double *__restrict__ a, double *__restrict__ b, size_t n, size_t tid,
                                           size_t stride) {
     const size_t nvec = n >> 1;

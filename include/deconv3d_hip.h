@@ -544,7 +544,9 @@ int d3d_temper_create(d3d_temper **t, d3d_ctx **ctxs, int n, const double *betas
  *      reproduces under its seed);
  *   2. for the pairs (i, i+1) with i = round mod 2 (mod 2): u = the first uniform of Philox4x32-10
  *      at counter {0xFFFFFFFF, (uint32_t)round, i, 1} under the group's seed (the chains' streams
- *      have a last counter word of 0), accepted iff log(u) < (betas[i] - betas[i+1]) (E_i -
+ *      have a last counter word of 0; only the low 32 bits of round enter the counter, so rounds
+ *      2^32 apart draw the same uniforms, while both 32-bit words of the seed key them),
+ *      accepted iff log(u) < (betas[i] - betas[i+1]) (E_i -
  *      E_{i+1}); attempts, accepts and labels follow, and E_r -- of the state at rung r before the
  *      exchange -- enters rung r's running (n, mean, M2);
  *   3. an accepted pair trades SLOT_ERR (the raw padded buffer) and the (H,W,3) parameters,

@@ -25,6 +25,79 @@ def energy(st, beta):
     return O.half_chi2(st.err, st.var) / beta
 
 
+def reference_energy(err, var, beta, data=None):
+    """E = (1/2 sum err^2 / (var / beta)) / beta of a downloaded residual, summed in extended
+    precision (np.longdouble), in another order than the device's; ``var`` is the UNTEMPERED
+    variance (a cube or one number).  Voxels where ``data`` is NaN are skipped: the device gives
+    them 1/var = 0 (d3d_set_data)."""
+    terms = np.asarray(err, dtype=np.float64) ** 2 / (np.asarray(var, dtype=np.float64) / beta)
+    if data is not None:
+        terms = terms[~np.isnan(data)]
+    return float(0.5 * np.sum(terms, dtype=np.longdouble) / np.longdouble(beta))
+
+
+def sources(decided):
+    """src (n): after a round rung r holds the state that rung src[r] held before it."""
+    n = len(decided) + 1
+    src = list(range(n))
+    for i in range(n - 1):
+        if decided[i] == 1:
+            src[i], src[i + 1] = i + 1, i
+    return src
+
+
+class Book(object):
+    """What d3d_temper_get must report after the rounds it was shown: labels, attempts, accepts."""
+
+    def __init__(self, n):
+        self.n = n
+        self.labels = list(range(n))
+        self.attempts = np.zeros(n - 1, dtype=np.int64)
+        self.accepts = np.zeros(n - 1, dtype=np.int64)
+        self.rounds = 0
+
+    def enter(self, round_, decided):
+        """One round's decisions; AssertionError where a pair's -1 does not follow the parity."""
+        proposed = proposed_pairs(self.n, round_)
+        for i in range(self.n - 1):
+            assert (decided[i] == -1) == (i not in proposed), (round_, i, decided[i])
+            if decided[i] == -1:
+                continue
+            self.attempts[i] += 1
+            if decided[i] == 1:
+                self.accepts[i] += 1
+                self.labels[i], self.labels[i + 1] = self.labels[i + 1], self.labels[i]
+        self.rounds += 1
+
+
+def caps_case(D, H, W, seed=5):
+    """Noise plus three blobs of one line, a 3 x 3 Gaussian FSF, a short LSF, per-voxel variance.
+    The recipe of the grid-cap test (128 x 184 x 184 on the device; tests/test_tempering_cpu.py
+    runs it at 16 x 15 x 14 on the oracle)."""
+    rng = np.random.default_rng(seed)
+    g = np.exp(-0.5 * (np.arange(-1, 2) / 0.8) ** 2)
+    fsf = np.outer(g, g) / np.sum(np.outer(g, g))
+    lsf = O.gaussian_lsf_vector(D, 0.7)
+    z = np.arange(D)[:, None, None]
+    y, x = np.indices((H, W))
+    data = rng.normal(0., 1., size=(D, H, W))
+    for _ in range(3):
+        cy, cx, cz = rng.random(3) * (H, W, D)
+        data += 8. * np.exp(-0.5 * (((y - cy) / (H / 5.)) ** 2 + ((x - cx) / (W / 5.)) ** 2)) \
+            * np.exp(-0.5 * ((z - cz) / 2.) ** 2)
+    var = (0.5 + rng.random((D, H, W))) ** 2
+    min_b, max_b = O.model_min_boundaries(), O.model_max_boundaries(data, fsf)
+    init = min_b + (max_b - min_b) * rng.random((H, W, 3))
+    init[..., 2] = np.maximum(init[..., 2], 0.3)
+    return dict(D=D, H=H, W=W, fsf=fsf, lsf=lsf, data=data, var=var, mask=np.ones((H, W)), min_b=min_b,
+                max_b=max_b, init=init)
+
+
+def scaled_starts(case, scales):
+    """One start per rung: the case's, its amplitudes times ``scales[r]``."""
+    return [case["init"] * np.array([s, 1., 1.]) for s in scales]
+
+
 def proposed_pairs(n, round_):
     p = int(round_) & 1
     return [i for i in range(n - 1) if i % 2 == p]

@@ -33,23 +33,24 @@ def tempered_case(name):
     return case
 
 
-def make_engines(case, betas, options=None):
+def make_engines(case, betas, options=None, seed=SEED, inits=None, refresh_every=0):
+    """One engine per rung: variance / beta_r, seed + r, start ``inits[r]`` (default: the case's)."""
     D, H, W = case["D"], case["H"], case["W"]
     uniform = bool(np.all(case["var"] == case["var"].flat[0]))
     engines = []
     for r, b in enumerate(betas):
         eng = _lib.Engine((D, H, W), case["fsf"].shape, options=options)
+        engines.append(eng)
         eng.set_taps(case["fsf"], case["lsf"])
         if uniform:
             eng.set_data(case["data"], None, var_scalar=float(case["var"].flat[0] / b), mask=case["mask"])
             assert eng.variance_is_uniform()
         else:
             eng.set_data(case["data"], case["var"] / b, mask=case["mask"])
-        eng.set_params(case["init"])
-        eng.mh_config(case["min_b"], case["max_b"], 0.1, float(case["max_b"][0] ** 2), seed=SEED + r,
-                      refresh_every=0)
+        eng.set_params(case["init"] if inits is None else inits[r])
+        eng.mh_config(case["min_b"], case["max_b"], 0.1, float(case["max_b"][0] ** 2), seed=seed + r,
+                      refresh_every=refresh_every)
         eng.residual(fetch=False)
-        engines.append(eng)
     return engines
 
 

@@ -203,3 +203,55 @@ def test_detailed_balance_of_the_rule_on_a_toy_by_exact_enumeration(betas):
             if delta >= 0.:
                 assert decided[0] == 1
         assert TO.decide(betas, (E[s0], E[s1]), 99, 1)[0][0] == -1             # odd round: pair 0 rests
+
+
+# ---- the helpers of the GPU tests ---------------------------------------------------------------
+
+def test_reference_energy_sources_and_book():
+    rng = np.random.default_rng(3)
+    err, var = rng.normal(size=(5, 4, 3)), 0.5 + rng.random((5, 4, 3))
+    data = rng.normal(size=(5, 4, 3))
+    want = math.fsum((0.5 * err ** 2 / var).ravel())
+    for beta in (1., 0.3):                    # E does not depend on the rung the state sits at
+        assert abs(TO.reference_energy(err, var, beta) - want) <= 4e-16 * want
+        assert abs(TO.reference_energy(err, var, beta, data) - want) <= 4e-16 * want
+    assert abs(TO.reference_energy(err, 0.7, 0.3) - math.fsum((0.5 * err ** 2 / 0.7).ravel())) <= 1e-15 * want
+    data[2, 1, 0] = np.nan                    # a NaN voxel is skipped, whatever its residual
+    err[2, 1, 0] = 1e9
+    keep = ~np.isnan(data)
+    got = TO.reference_energy(err, var, 0.3, data)
+    assert abs(got - math.fsum((0.5 * err ** 2 / var)[keep])) <= 4e-16 * got
+    assert TO.sources([1, -1, 0]) == [1, 0, 2, 3] and TO.sources([-1, 1, -1]) == [0, 2, 1, 3]
+    assert TO.sources([-1]) == [0, 1] and TO.sources([1, -1, 1, -1]) == [1, 0, 3, 2, 4]
+    book = TO.Book(4)
+    book.enter(0, [1, -1, 0])
+    book.enter(1, [-1, 1, -1])
+    book.enter(2 ** 32 + 2, [0, -1, 1])
+    assert book.labels == [1, 2, 3, 0] and book.rounds == 3
+    np.testing.assert_array_equal(book.attempts, [2, 1, 2])
+    np.testing.assert_array_equal(book.accepts, [1, 1, 1])
+    with pytest.raises(AssertionError):
+        book.enter(3, [0, -1, 0])             # an odd round proposes pair 1 alone
+
+
+def test_scaled_starts_make_both_outcomes_of_the_grid_cap_case_certain():
+    """The recipe of the 128 x 184 x 184 device test at 16 x 15 x 14: two sweeps after a start from
+    amplitudes 50 times smaller a rung lies lower than one started from the drawn map, whichever
+    of the two is hotter.  delta > 0 is accepted whatever u; delta < -5 is refused unless
+    u < exp(-5), and the difference grows with the number of spaxels (161 times as many there)."""
+    case = TO.caps_case(16, 15, 14)
+    assert case["fsf"].shape == (3, 3) and abs(case["fsf"].sum() - 1.) < 1e-15
+    for betas, scales, rounds, want in (((1., .5), (1., .02), (0, 1, 2), [[1], [-1], [0]]),
+                                        ((1., .5, .25), (1., .02, 1.), (0, 1), [[1, -1], [-1, 0]])):
+        starts = TO.scaled_starts(case, scales)
+        np.testing.assert_array_equal(starts[1][..., 1:], case["init"][..., 1:])
+        np.testing.assert_array_equal(starts[1][..., 0], case["init"][..., 0] * .02)
+        lad = TO.Ladder(case, betas, 77, inits=starts)
+        for s in (1, 2):
+            lad.sweep(s)
+        for k, row in zip(rounds, want):
+            decided, u, logu, E = lad.swap(k)
+            assert list(decided) == row
+            for i in TO.proposed_pairs(len(betas), k):
+                delta = (betas[i] - betas[i + 1]) * (E[i] - E[i + 1])
+                assert delta > 0. if decided[i] == 1 else delta < -5.
