@@ -44,6 +44,7 @@ SYMBOLS = [
     "d3d_line_search",
     "d3d_running_median", "d3d_channel_stats", "d3d_prepare",
     "d3d_temper_create", "d3d_temper_swap", "d3d_temper_get", "d3d_temper_last", "d3d_temper_destroy",
+    "d3d_temper_set_patch", "d3d_temper_last_patches", "d3d_temper_get_patches",
 ]
 
 # posterior moments (a table, so that tools/posterior_time.py can load the PARENT commit's library,
@@ -103,6 +104,10 @@ TEMPER_PROTOTYPES = {
                       + [C.POINTER(C.c_int32)],
     "d3d_temper_last": [C.c_void_p] + [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_int32)],
     "d3d_temper_destroy": [C.c_void_p],
+    "d3d_temper_set_patch": [C.c_void_p, C.c_int],
+    "d3d_temper_last_patches": [C.c_void_p, C.POINTER(C.c_int32)] + [C.POINTER(C.c_double)] * 3
+                               + [C.POINTER(C.c_int32)],
+    "d3d_temper_get_patches": [C.c_void_p] + [C.POINTER(C.c_int64)] * 2,
 }
 POST_CLEAN, POST_CONVOLVED = 1, 2                     # d3d_post_begin: bits of `what`
 POST_PARAMETERS, POST_CLEAN_CUBE, POST_CONVOLVED_CUBE = 0, 1, 2   # d3d_post_get: `which`
@@ -293,9 +298,11 @@ def mh_sweeps_batch(engines, n_sweeps, first_sweep=1, keep_one_in=1, chains=None
 class TemperGroup(object):
     """d3d_temper_*: replica exchange between the chains of ``engines`` -- one geometry, rung r
     fed ``var / betas[r]`` by its owner -- at inverse temperatures ``betas`` (1 first, strictly
-    decreasing).  ``seed`` keys the swaps' uniforms.  Close the group before its engines."""
+    decreasing).  ``seed`` keys the swaps' uniforms.  ``patch``: None (whole cubes trade places) or
+    the side p >= 1 of the tiles whose spaxels do (d3d_temper_set_patch).  Close the group before its
+    engines."""
 
-    def __init__(self, engines, betas, seed=12345):
+    def __init__(self, engines, betas, seed=12345, patch=None):
         self._lib = load()
         self._t = C.c_void_p(None)
         self.engines = list(engines)          # (kept alive: the group holds their contexts)
@@ -307,6 +314,15 @@ class TemperGroup(object):
         arr = (C.c_void_p * max(self.n, 1))(*[e._ctx.value for e in self.engines])
         _check(self._lib.d3d_temper_create(C.byref(self._t), arr, self.n, _dp(self.betas),
                                            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)))
+        self.patch = None
+        if patch is not None:
+            self.set_patch(patch)
+
+    def set_patch(self, patch):
+        """d3d_temper_set_patch: None or 0 for whole cubes, p >= 1 for tiles of p x p spaxels."""
+        p = 0 if patch is None else int(patch)
+        _check(self._lib.d3d_temper_set_patch(self._t, p))
+        self.patch = p if p > 0 else None
 
     def close(self):
         if getattr(self, "_t", None) is not None and self._t.value:
@@ -352,6 +368,29 @@ class TemperGroup(object):
         _check(self._lib.d3d_temper_last(self._t, _dp(energy), _dp(u), _dp(logu),
                                          decided.ctypes.data_as(C.POINTER(C.c_int32))))
         return dict(energy=energy, u=u, logu=logu, decided=decided)
+
+    def last_patches(self):
+        """The last round, a patch round: dict(oy, ox, nty, ntx, my, mx, terms (n-1, nty, ntx, 5: sum
+        ivar_i e_i delta, sum ivar_j e_j delta, 1/2 sum ivar_i delta^2, 1/2 sum ivar_j delta^2, the
+        prior's term), u, logu (n-1, nty, ntx; NaN where not proposed), decided (n-1, nty, ntx: 1, 0,
+        -1 = not proposed))."""
+        geom = np.zeros(6, dtype=np.int32)
+        i32 = C.POINTER(C.c_int32)
+        _check(self._lib.d3d_temper_last_patches(self._t, geom.ctypes.data_as(i32), None, None, None, None))
+        oy, ox, nty, ntx, my, mx = (int(v) for v in geom)
+        shape = (self.n - 1, nty, ntx)
+        terms, u, logu = np.zeros(shape + (5,)), np.zeros(shape), np.zeros(shape)
+        decided = np.zeros(shape, dtype=np.int32)
+        _check(self._lib.d3d_temper_last_patches(self._t, None, _dp(terms), _dp(u), _dp(logu),
+                                                 decided.ctypes.data_as(i32)))
+        return dict(oy=oy, ox=ox, nty=nty, ntx=ntx, my=my, mx=mx, terms=terms, u=u, logu=logu, decided=decided)
+
+    def get_patches(self):
+        """dict(attempts, accepts (n-1)): the patches proposed and accepted per pair so far."""
+        attempts, accepts = np.zeros(self.n - 1, dtype=np.int64), np.zeros(self.n - 1, dtype=np.int64)
+        i64 = C.POINTER(C.c_int64)
+        _check(self._lib.d3d_temper_get_patches(self._t, attempts.ctypes.data_as(i64), accepts.ctypes.data_as(i64)))
+        return dict(attempts=attempts, accepts=accepts)
 
 
 def device_count():

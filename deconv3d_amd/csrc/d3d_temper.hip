@@ -80,8 +80,10 @@ static __global__ __launch_bounds__(TEMPER_NT) void k_temper_energy(TemperChains
 // shuffles), E_r = total_r / beta_r -- minus log L of state r under the untempered variance.  Then
 // thread i decides pair (i, i + 1) where i has the round's parity, and thread r folds E_r -- of the
 // state at rung r BEFORE the exchange -- into that rung's moments.
+// whole == 0 (patch exchange, d3d_temper_set_patch): the energies and their moments only; every pair's
+// whole-cube record reads "not proposed".
 static __global__ __launch_bounds__(TEMPER_NT) void k_temper_decide(TemperChains C, TemperBlock T, int n, int nblk,
-                                                                    long long round, uint64_t seed) {
+                                                                    long long round, uint64_t seed, int whole) {
 #pragma clang fp contract(off)
     __shared__ double E[TEMPER_MAX];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -109,7 +111,7 @@ static __global__ __launch_bounds__(TEMPER_NT) void k_temper_decide(TemperChains
     }
     if (i < n - 1) {
         const int p = (int)(round & 1);
-        if ((i & 1) != p) {
+        if ((i & 1) != p || !whole) {
             T.decided[i] = -1;
             T.u[i] = __longlong_as_double(0x7ff8000000000000LL);
             T.logu[i] = __longlong_as_double(0x7ff8000000000000LL);
@@ -169,6 +171,271 @@ static __global__ __launch_bounds__(TEMPER_NT) void k_temper_exchange(TemperChai
     swap_span(C.params[i], C.params[i + 1], par_elems, tid, stride);
 }
 
+
+// ---- exchange of PATCHES of spaxels (d3d_temper_set_patch) ------------------------------------
+// The field is cut into tiles of p x p spaxels from a per-round origin; a tile's unmasked spaxels
+// are one patch.  Rungs i and j = i + 1 propose to trade the parameters of the patch; with
+// delta = sum_{s in P} [contribution(s, x_i[s]) - contribution(s, x_j[s])] (supported on the tile
+// dilated by the FSF) the residuals become e_i + delta and e_j - delta, and the log ratio is local.
+
+// The LSF-convolved lines of every rung of a proposed pair, (HW, Dp), zero at masked spaxels:
+// launch_lines into the rung's SLOT_TMP0 once per round (a spaxel lies in one tile, a tile in one
+// colour, so the lines of a round's start serve all of its colours).
+struct PatchLines {
+    const double *lines[TEMPER_MAX];
+};
+
+struct PatchBlock {
+    double *terms;   // [n-1][ntiles][5]
+    double *u, *logu;  // [n-1][ntiles]
+    int *decided;    // [n-1][ntiles]
+    unsigned long long *attempts, *accepts;  // [n-1] patch totals
+};
+
+struct PatchArgs {
+    int D, Dp, H, W, fh, fw;
+    int p, oy, ox, nty, ntx, my, mx;
+    int cy, cx, nkx;  // the launch's colour; tiles of that colour along x
+    int parity, prior;
+    double lam[3];
+    long long round;
+    uint64_t seed;
+    const double *fsf;
+    const uint8_t *mask;
+    PatchBlock B;
+};
+
+static __global__ __launch_bounds__(TEMPER_NT) void k_patch_clear(PatchBlock B, long nrec) {
+    const long r = (long)blockIdx.x * TEMPER_NT + threadIdx.x;
+    if (r >= nrec) return;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    for (int k = 0; k < 5; ++k) B.terms[r * 5 + k] = nan;
+    B.u[r] = nan;
+    B.logu[r] = nan;
+    B.decided[r] = -1;
+}
+
+struct PatchTile {
+    int ty0, ty1, tx0, tx1;  // the tile, clipped to the field
+    int fy0, fy1, fx0, fx1;  // its footprint: dilated by the FSF's half sizes, clipped
+};
+
+// Eight wavefronts per tile, two per SIMD (a colour of 300 x 300 spaxels at p = 10 is 240 workgroups,
+// one per CU at most).  Sixteen leave 64 architectural registers a lane and spill 43.
+constexpr int PATCH_NT = 512;
+// The staged form: the tile's line differences of one z-block in LDS, a wavefront along z.  Tiles of
+// up to PATCH_LDS_SPAXELS spaxels (60 KiB of static LDS beside the reduction's) take it; larger ones
+// read the two line cubes through the caches.
+constexpr int PATCH_ZB = 64;
+constexpr int PATCH_UNROLL = 4;
+constexpr int PATCH_LDS_SPAXELS = 120;
+
+// delta at voxel (y, x, z): the tile's line differences through the FSF, sources row-major.  A
+// contribution at (sy + dy, sx + dx) carries fsf[fhh + dy, fhw + dx].  One IEEE operation per step,
+// and the staged difference is the same subtraction: the deciding pass, the updating pass and both
+// forms get the same bits.
+template <bool STAGED>
+__device__ __forceinline__ double patch_delta(const PatchArgs &A, const PatchTile &T, const double *__restrict__ Li,
+                                              const double *__restrict__ Lj, const double *dl, int y, int x, int z,
+                                              int zz) {
+#pragma clang fp contract(off)
+    const int fhh = (A.fh - 1) / 2, fhw = (A.fw - 1) / 2;
+    const int sy0 = max(T.ty0, y - fhh), sy1 = min(T.ty1, y + fhh + 1);
+    const int sx0 = max(T.tx0, x - fhw), sx1 = min(T.tx1, x + fhw + 1);
+    const int tw = T.tx1 - T.tx0;
+    double d = 0.0;
+    for (int sy = sy0; sy < sy1; ++sy) {
+        const double *__restrict__ frow = A.fsf + (size_t)(fhh + y - sy) * A.fw + (fhw + x);
+        for (int sx = sx0; sx < sx1; ++sx) {
+            double v;
+            if constexpr (STAGED) {
+                v = dl[((sy - T.ty0) * tw + (sx - T.tx0)) * PATCH_ZB + zz];
+            } else {
+                const size_t o = ((size_t)sy * A.W + sx) * A.Dp + z;
+                v = Li[o] - Lj[o];
+            }
+            d += frow[-sx] * v;
+        }
+    }
+    return d;
+}
+
+// One walk over the footprint in z-blocks of PATCH_ZB channels: a wavefront takes one footprint
+// spaxel at a time with its lanes along z, so every load of residual, 1/variance and lines is
+// coalesced and the spaxel -- with it the FSF taps and the bounds of the source loop -- is the
+// same in all lanes (scalar loads, no divergence).  UPDATE = false: the four sums into acc, per
+// thread in the order of its spaxels.  UPDATE = true: delta into both residuals.  (The caller has a
+// barrier between two walks: the staging of the second does not overtake the first's reads.)
+template <bool STAGED, bool UPDATE>
+__device__ __forceinline__ void patch_walk(const PatchArgs &A, const PatchTile &T, double *__restrict__ ei,
+                                           double *__restrict__ ej, const double *__restrict__ vi,
+                                           const double *__restrict__ vj, const double *__restrict__ Li,
+                                           const double *__restrict__ Lj, double *dl, double acc[5]) {
+#pragma clang fp contract(off)
+    const int tw = T.tx1 - T.tx0, nsp = (T.ty1 - T.ty0) * tw;
+    const int fwid = T.fx1 - T.fx0, nf = (T.fy1 - T.fy0) * fwid;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int nzb = (A.D + PATCH_ZB - 1) / PATCH_ZB;
+    for (int zb = 0; zb < nzb; ++zb) {
+        const int z0 = zb * PATCH_ZB;
+        const int zn = min(PATCH_ZB, A.D - z0);
+        if constexpr (STAGED) {
+            if (zb) __syncthreads();
+            for (int q = threadIdx.x; q < nsp * PATCH_ZB; q += PATCH_NT) {
+                const int s = q / PATCH_ZB, zz = q - s * PATCH_ZB;
+                const size_t o = ((size_t)(T.ty0 + s / tw) * A.W + T.tx0 + s % tw) * A.Dp + z0 + zz;
+                dl[q] = (zz < zn) ? Li[o] - Lj[o] : 0.0;
+            }
+            __syncthreads();
+        }
+        // PATCH_UNROLL spaxels per step, their loads first: a tile's workgroup has a CU to itself, and
+        // one spaxel's loads per wavefront in flight leave the walk waiting for memory
+        for (int f0 = wave; f0 < nf; f0 += PATCH_UNROLL * (PATCH_NT / 64)) {
+            double e_i[PATCH_UNROLL], e_j[PATCH_UNROLL], w_i[PATCH_UNROLL], w_j[PATCH_UNROLL];
+#pragma unroll
+            for (int k = 0; k < PATCH_UNROLL; ++k) {
+                const int f = f0 + k * (PATCH_NT / 64);
+                if (f < nf && lane < zn) {
+                    const size_t o = ((size_t)(T.fy0 + f / fwid) * A.W + T.fx0 + f % fwid) * A.Dp + z0 + lane;
+                    e_i[k] = ei[o];
+                    e_j[k] = ej[o];
+                    if constexpr (!UPDATE) {
+                        w_i[k] = vi ? vi[o] : 1.0;
+                        w_j[k] = vj ? vj[o] : 1.0;
+                    }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < PATCH_UNROLL; ++k) {
+                const int f = f0 + k * (PATCH_NT / 64);
+                if (f < nf && lane < zn) {
+                    const int y = T.fy0 + f / fwid, x = T.fx0 + f % fwid, z = z0 + lane;
+                    const double d = patch_delta<STAGED>(A, T, Li, Lj, dl, y, x, z, lane);
+                    if constexpr (UPDATE) {
+                        const size_t o = ((size_t)y * A.W + x) * A.Dp + z;
+                        ei[o] = e_i[k] + d;
+                        ej[o] = e_j[k] - d;
+                    } else {
+                        acc[0] += w_i[k] * (e_i[k] * d);
+                        acc[1] += w_j[k] * (e_j[k] * d);
+                        acc[2] += w_i[k] * (d * d);
+                        acc[3] += w_j[k] * (d * d);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// One workgroup per (tile of the launch's colour, proposed pair): blockIdx.x = the tile's ordinal
+// among those of its colour, blockIdx.y = the pair's.  Pass 1 walks the footprint and sums e_i delta,
+// e_j delta and the two delta^2 per thread, per wavefront by shuffles, per workgroup through LDS: a
+// fixed order.  Thread 0 adds the prior's term, draws u and decides.  Pass 2, accepted tiles only:
+// delta again into both residuals, then the patch's parameters trade places.  Footprints of one
+// colour are disjoint and, with a prior on (FSFs of three spaxels and more), the tiles not adjacent.
+template <bool STAGED>
+static __global__ __launch_bounds__(PATCH_NT) void k_temper_patch(TemperChains C, PatchLines Ls, PatchArgs A) {
+#pragma clang fp contract(off)
+    __shared__ double dl[STAGED ? PATCH_LDS_SPAXELS * PATCH_ZB : 1];
+    __shared__ double red[PATCH_NT / 64][5];
+    __shared__ int s_ok;
+    const int ky = (int)blockIdx.x / A.nkx, kx = (int)blockIdx.x - ky * A.nkx;
+    const int ty = A.cy + ky * A.my, tx = A.cx + kx * A.mx;
+    const int i = A.parity + 2 * (int)blockIdx.y, j = i + 1;
+    const int fhh = (A.fh - 1) / 2, fhw = (A.fw - 1) / 2;
+    PatchTile T;
+    T.ty0 = max(0, ty * A.p - A.p + A.oy);
+    T.ty1 = min(A.H, ty * A.p + A.oy);
+    T.tx0 = max(0, tx * A.p - A.p + A.ox);
+    T.tx1 = min(A.W, tx * A.p + A.ox);
+    if (T.ty0 >= T.ty1 || T.tx0 >= T.tx1) return;  // (the first row or column of tiles under a zero shift)
+    T.fy0 = max(0, T.ty0 - fhh);
+    T.fy1 = min(A.H, T.ty1 + fhh);
+    T.fx0 = max(0, T.tx0 - fhw);
+    T.fx1 = min(A.W, T.tx1 + fhw);
+    const int tw = T.tx1 - T.tx0, nsp = (T.ty1 - T.ty0) * tw;
+    if (STAGED && nsp > PATCH_LDS_SPAXELS) return;  // (the host picks the form from the largest tile: never taken)
+    int live = 0;
+    for (int s = threadIdx.x; s < nsp; s += PATCH_NT)
+        live |= A.mask[(size_t)(T.ty0 + s / tw) * A.W + T.tx0 + s % tw] != 0;
+    if (!__syncthreads_or(live)) return;  // no unmasked spaxel: not proposed (k_patch_clear's record stands)
+
+    double *__restrict__ ei = C.err[i], *__restrict__ ej = C.err[j];
+    const double *__restrict__ vi = C.ivar[i], *__restrict__ vj = C.ivar[j];
+    const double *__restrict__ Li = Ls.lines[i], *__restrict__ Lj = Ls.lines[j];
+    double *__restrict__ pi = C.params[i], *__restrict__ pj = C.params[j];
+    double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    patch_walk<STAGED, false>(A, T, ei, ej, vi, vj, Li, Lj, dl, acc);
+    if (A.prior) {  // the pairs <s, t> with s in the patch, t an unmasked 4-neighbour outside the tile
+        for (int q = threadIdx.x; q < 4 * nsp; q += PATCH_NT) {
+            const int s = q >> 2, dir = q & 3;
+            const int sy = T.ty0 + s / tw, sx = T.tx0 + s % tw;
+            const int ny = sy + (dir == 0 ? -1 : dir == 1 ? 1 : 0), nx = sx + (dir == 2 ? -1 : dir == 3 ? 1 : 0);
+            if (ny < 0 || ny >= A.H || nx < 0 || nx >= A.W) continue;
+            if (ny >= T.ty0 && ny < T.ty1 && nx >= T.tx0 && nx < T.tx1) continue;
+            const size_t so = (size_t)sy * A.W + sx, to = (size_t)ny * A.W + nx;
+            if (!A.mask[so] || !A.mask[to]) continue;
+            for (int k = 0; k < 3; ++k) {
+                const double xis = pi[so * 3 + k], xjs = pj[so * 3 + k];
+                const double xit = pi[to * 3 + k], xjt = pj[to * 3 + k];
+                const double a = xjs - xit, b = xis - xit, c = xis - xjt, e = xjs - xjt;
+                acc[4] += A.lam[k] * (((a * a - b * b) + c * c) - e * e);
+            }
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const double w = wave_sum(acc[k]);
+        if (lane == 0) red[wave][k] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            double v = 0.0;
+            for (int w = 0; w < PATCH_NT / 64; ++w) v += red[w][k];
+            t[k] = v;
+        }
+        const double si = vi ? 1.0 : C.ivar_uniform[i], sj = vj ? 1.0 : C.ivar_uniform[j];
+        t[0] = si * t[0];
+        t[1] = sj * t[1];
+        t[2] = 0.5 * (si * t[2]);
+        t[3] = 0.5 * (sj * t[3]);
+        t[4] = -0.5 * t[4];
+        const int tile = ty * A.ntx + tx;
+        uint32_t w[4];
+        philox4x32_10(0xFFFFFFFFu, (uint32_t)A.round, (uint32_t)i, 2u + (uint32_t)tile, (uint32_t)A.seed,
+                      (uint32_t)(A.seed >> 32), w);
+        const double u = u64_to_unit(((uint64_t)w[1] << 32) | w[0]);
+        const double logu = log(u);
+        const double delta = (-(t[0] + t[2]) - (t[3] - t[1])) + t[4];
+        const int ok = logu < delta ? 1 : 0;
+        const size_t rec = (size_t)i * A.nty * A.ntx + tile;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) A.B.terms[rec * 5 + k] = t[k];
+        A.B.u[rec] = u;
+        A.B.logu[rec] = logu;
+        A.B.decided[rec] = ok;
+        atomicAdd(A.B.attempts + i, 1ull);  // (integer totals: any order gives the same)
+        if (ok) atomicAdd(A.B.accepts + i, 1ull);
+        s_ok = ok;
+    }
+    __syncthreads();
+    if (!s_ok) return;
+    patch_walk<STAGED, true>(A, T, ei, ej, vi, vj, Li, Lj, dl, acc);
+    for (int q = threadIdx.x; q < 3 * nsp; q += PATCH_NT) {
+        const int s = q / 3, k = q - 3 * s;
+        const size_t so = (size_t)(T.ty0 + s / tw) * A.W + T.tx0 + s % tw;
+        if (!A.mask[so]) continue;
+        const double a = pi[so * 3 + k];
+        pi[so * 3 + k] = pj[so * 3 + k];
+        pj[so * 3 + k] = a;
+    }
+}
+
 }  // namespace d3d
 
 struct d3d_temper {
@@ -183,6 +450,14 @@ struct d3d_temper {
     void *dev = nullptr;  // the group's one device block
     d3d::TemperBlock T = {};
     hipEvent_t done = nullptr;  // end of the last round on the leader's stream
+    // exchange of patches (d3d_temper_set_patch): nothing allocated before the first such round
+    int patch = 0;               // 0: whole cubes
+    void *pcount = nullptr;      // [2][n-1] patch attempts | accepts
+    void *prec = nullptr;        // the per-tile record of the last round, prec_cap records per pair
+    size_t prec_cap = 0;
+    d3d::PatchBlock P = {};
+    int pgeom[6] = {0, 0, 0, 0, 0, 0};  // oy, ox, nty, ntx, my, mx of the last patch round
+    bool plast = false;          // the last round was a patch round
 };
 
 namespace {
@@ -209,6 +484,134 @@ void fill_chains(const d3d_temper *t, d3d::TemperChains &C) {
     }
 }
 
+// Philox4x32-10 on the host (the round's origin shift is launch geometry): d3d_rng.h's function.
+void philox_host(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t m0 = (uint64_t)0xD2511F53u * c0, m1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(m1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(m0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)m1;
+        c3 = (uint32_t)m0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0;
+    out[1] = c1;
+    out[2] = c2;
+    out[3] = c3;
+}
+
+// The patch block for `nrec` records per pair (grown, never shrunk); the counters once.
+int ensure_patch_block(d3d_temper *t, size_t nrec) {
+    const size_t np = (size_t)t->n - 1;
+    if (!t->pcount) {
+        HIP_TRY(hipMalloc(&t->pcount, 2 * np * 8));
+        HIP_TRY(hipMemsetAsync(t->pcount, 0, 2 * np * 8, t->ctxs[0]->stream));
+        t->P.attempts = static_cast<unsigned long long *>(t->pcount);
+        t->P.accepts = t->P.attempts + np;
+    }
+    if (nrec > t->prec_cap) {
+        if (t->prec) {
+            HIP_TRY(hipStreamSynchronize(t->ctxs[0]->stream));
+            HIP_TRY(hipFree(t->prec));
+            t->prec = nullptr;
+            t->prec_cap = 0;
+        }
+        HIP_TRY(hipMalloc(&t->prec, np * nrec * (7 * 8 + 4)));
+        t->prec_cap = nrec;
+    }
+    // (laid out for this round's record count: d3d_temper_last_patches reads it the same way)
+    double *d = static_cast<double *>(t->prec);
+    t->P.terms = d;
+    d += np * nrec * 5;
+    t->P.u = d;
+    d += np * nrec;
+    t->P.logu = d;
+    d += np * nrec;
+    t->P.decided = reinterpret_cast<int *>(d);
+    return 0;
+}
+
+// One patch round on the leader's stream: the energies and their moments (no whole-cube decision),
+// the lines of the rungs of the proposed pairs, the cleared record, one launch per tile colour.
+int patch_round(d3d_temper *t, int64_t round) {
+    d3d_ctx *L = t->ctxs[0];
+    const int n = t->n, p = t->patch, H = L->H, W = L->W;
+    d3d::TemperChains C;
+    fill_chains(t, C);
+    hipLaunchKernelGGL(d3d::k_temper_energy, dim3((unsigned)t->nblk, (unsigned)n), dim3(d3d::TEMPER_NT), 0, L->stream,
+                       C, t->cube_elems, t->T.partials);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(d3d::k_temper_decide, dim3(1), dim3(d3d::TEMPER_NT), 0, L->stream, C, t->T, n, t->nblk,
+                       (long long)round, t->seed, 0);
+    HIP_TRY(hipGetLastError());
+    uint32_t w[4];
+    philox_host(0xFFFFFFFEu, (uint32_t)round, 0u, 1u, (uint32_t)t->seed, (uint32_t)(t->seed >> 32), w);
+    const int oy = (int)(w[0] % (uint32_t)p), ox = (int)(w[1] % (uint32_t)p);
+    const int nty = (H - 1 + p - oy) / p + 1, ntx = (W - 1 + p - ox) / p + 1;
+    const int my = 1 + (L->fh - 1 + p - 1) / p, mx = 1 + (L->fw - 1 + p - 1) / p;
+    const int g[6] = {oy, ox, nty, ntx, my, mx};
+    memcpy(t->pgeom, g, sizeof g);
+    const size_t nrec = (size_t)nty * ntx;
+    if (int rc = ensure_patch_block(t, nrec)) return rc;
+    const long all = (long)((size_t)(n - 1) * nrec);
+    hipLaunchKernelGGL(d3d::k_patch_clear, dim3((unsigned)((all + d3d::TEMPER_NT - 1) / d3d::TEMPER_NT)),
+                       dim3(d3d::TEMPER_NT), 0, L->stream, t->P, all);
+    HIP_TRY(hipGetLastError());
+    const int parity = (int)(round & 1);
+    const int pairs = (n - parity) / 2;
+    if (pairs <= 0) return 0;
+    d3d::PatchLines Ls;
+    memset(&Ls, 0, sizeof Ls);
+    for (int r = parity; r < parity + 2 * pairs; ++r) {
+        d3d_ctx *c = t->ctxs[r];
+        if (int rc = d3dh::launch_lines(c, c->slot[D3D_SLOT_TMP0], 1)) return rc;
+        Ls.lines[r] = c->slot[D3D_SLOT_TMP0];
+    }
+    d3d::PatchArgs A;
+    memset(&A, 0, sizeof A);
+    A.D = L->D;
+    A.Dp = L->Dp;
+    A.H = H;
+    A.W = W;
+    A.fh = L->fh;
+    A.fw = L->fw;
+    A.p = p;
+    A.oy = oy;
+    A.ox = ox;
+    A.nty = nty;
+    A.ntx = ntx;
+    A.my = my;
+    A.mx = mx;
+    A.parity = parity;
+    A.prior = L->prior_on && (L->prior_lam[0] != 0.0 || L->prior_lam[1] != 0.0 || L->prior_lam[2] != 0.0);
+    for (int k = 0; k < 3; ++k) A.lam[k] = L->prior_on ? L->prior_lam[k] : 0.0;
+    A.round = (long long)round;
+    A.seed = t->seed;
+    A.fsf = L->fsf;
+    A.mask = L->mask;
+    A.B = t->P;
+    // the staged form where the largest tile's line differences of a z-block fit its LDS
+    const bool staged = std::min(p, H) * (long)std::min(p, W) <= d3d::PATCH_LDS_SPAXELS;
+    for (int cy = 0; cy < my; ++cy)
+        for (int cx = 0; cx < mx; ++cx) {
+            const int nky = (nty - cy + my - 1) / my, nkx = (ntx - cx + mx - 1) / mx;
+            if (nky <= 0 || nkx <= 0) continue;
+            A.cy = cy;
+            A.cx = cx;
+            A.nkx = nkx;
+            if (staged)
+                hipLaunchKernelGGL(d3d::k_temper_patch<true>, dim3((unsigned)(nky * nkx), (unsigned)pairs),
+                                   dim3(d3d::PATCH_NT), 0, L->stream, C, Ls, A);
+            else
+                hipLaunchKernelGGL(d3d::k_temper_patch<false>, dim3((unsigned)(nky * nkx), (unsigned)pairs),
+                                   dim3(d3d::PATCH_NT), 0, L->stream, C, Ls, A);
+            HIP_TRY(hipGetLastError());
+        }
+    return 0;
+}
+
 }  // namespace
 
 // The three launches of one round on the leader's stream (d3d_temper_swap has validated the group
@@ -221,7 +624,7 @@ int d3dh::temper_round(d3d_temper *t, int64_t round) {
                        L->stream, C, t->cube_elems, t->T.partials);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(d3d::k_temper_decide, dim3(1), dim3(d3d::TEMPER_NT), 0, L->stream, C, t->T, t->n, t->nblk,
-                       (long long)round, t->seed);
+                       (long long)round, t->seed, 1);
     HIP_TRY(hipGetLastError());
     const int parity = (int)(round & 1);
     const int pairs = (t->n - parity) / 2;  // pairs (i, i + 1), i = parity, parity + 2, ..., i + 1 < n
@@ -353,7 +756,20 @@ int d3d_temper_swap(d3d_temper *t, int64_t round) {
     }
     for (int r = 0; r < t->n; ++r)
         if (int rc = d3dh::flush_pending(t->ctxs[r])) return rc;
-    if (int rc = d3dh::temper_round(t, round)) return rc;
+    if (t->patch > 0) {
+        for (int r = 1; r < t->n; ++r) {
+            const d3d_ctx *c = t->ctxs[r];
+            bool same = c->prior_on == L->prior_on;
+            for (int k = 0; k < 3; ++k) same = same && (!c->prior_on || c->prior_lam[k] == L->prior_lam[k]);
+            NEED(same, D3D_ERR_INVALID,
+                 "ctx %d: another smoothness prior than ctx 0 (the prior's term of a patch exchange cancels "
+                 "only between rungs of one prior)", r);
+        }
+        if (int rc = patch_round(t, round)) return rc;
+    } else if (int rc = d3dh::temper_round(t, round)) {
+        return rc;
+    }
+    t->plast = t->patch > 0;
     // what the other contexts enqueue next on their own streams waits for the exchange (on the
     // device: the host goes on)
     HIP_TRY(hipEventRecord(t->done, L->stream));
@@ -396,10 +812,53 @@ int d3d_temper_last(d3d_temper *t, double *energy, double *u, double *logu, int3
     return D3D_OK;
 }
 
+int d3d_temper_set_patch(d3d_temper *t, int p) {
+    NEED(t, D3D_ERR_INVALID, "group is NULL");
+    NEED(p >= 0 && p <= (1 << 24), D3D_ERR_INVALID,
+         "patch size %d: 0 (whole cubes) or the side of a tile in spaxels, 2^24 at most", p);
+    t->patch = p;
+    return D3D_OK;
+}
+
+int d3d_temper_last_patches(d3d_temper *t, int32_t geometry[6], double *terms, double *u, double *logu,
+                            int32_t *decided) {
+    NEED(t, D3D_ERR_INVALID, "group is NULL");
+    NEED(t->rounds > 0 && t->plast, D3D_ERR_STATE, "the last round (if any) exchanged no patches");
+    HIP_TRY(hipSetDevice(t->device));
+    hipStream_t s = t->ctxs[0]->stream;
+    if (geometry)
+        for (int k = 0; k < 6; ++k) geometry[k] = t->pgeom[k];
+    const size_t nrec = (size_t)(t->n - 1) * t->pgeom[2] * t->pgeom[3];
+    if (terms) HIP_TRY(hipMemcpyAsync(terms, t->P.terms, nrec * 5 * 8, hipMemcpyDeviceToHost, s));
+    if (u) HIP_TRY(hipMemcpyAsync(u, t->P.u, nrec * 8, hipMemcpyDeviceToHost, s));
+    if (logu) HIP_TRY(hipMemcpyAsync(logu, t->P.logu, nrec * 8, hipMemcpyDeviceToHost, s));
+    if (decided) HIP_TRY(hipMemcpyAsync(decided, t->P.decided, nrec * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return D3D_OK;
+}
+
+int d3d_temper_get_patches(d3d_temper *t, int64_t *attempts, int64_t *accepts) {
+    NEED(t, D3D_ERR_INVALID, "group is NULL");
+    const size_t np = (size_t)t->n - 1;
+    if (!t->pcount) {  // no patch round yet
+        if (attempts) memset(attempts, 0, np * 8);
+        if (accepts) memset(accepts, 0, np * 8);
+        return D3D_OK;
+    }
+    HIP_TRY(hipSetDevice(t->device));
+    hipStream_t s = t->ctxs[0]->stream;
+    if (attempts) HIP_TRY(hipMemcpyAsync(attempts, t->P.attempts, np * 8, hipMemcpyDeviceToHost, s));
+    if (accepts) HIP_TRY(hipMemcpyAsync(accepts, t->P.accepts, np * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return D3D_OK;
+}
+
 int d3d_temper_destroy(d3d_temper *t) {
     if (!t) return D3D_OK;
     (void)hipSetDevice(t->device);
     (void)hipEventSynchronize(t->done);  // (a round may still be running)
+    if (t->pcount) (void)hipFree(t->pcount);
+    if (t->prec) (void)hipFree(t->prec);
     if (t->done) (void)hipEventDestroy(t->done);
     if (t->dev) (void)hipFree(t->dev);
     delete t;

@@ -250,6 +250,12 @@ class Run:
     place), a host-evaluated line model raises ``NotImplementedError``.  The checkpoint holds the
     R maps as for ``chains=R`` and records the ladder and ``swap_every``; ``resume_state=`` refuses
     a state written with others, the round numbering continues, counters and labels start afresh.
+    ``patch=p`` in the dict (default ``None``: whole cubes) makes a round trade PATCHES instead:
+    the unmasked spaxels of tiles of p x p spaxels, cut from an origin drawn per round, each
+    decided by itself from an energy difference that lives in the tile dilated by the FSF
+    (d3d_temper_set_patch), so that a coarse ladder swaps where whole cubes never would.  The
+    report then counts ``patch_attempts`` / ``patch_accepts`` / ``patch_rates`` per pair, its
+    ``labels`` is ``None``, and ``resume_state=`` refuses a state written with another patch size.
     """
 
     def __init__(
@@ -655,7 +661,8 @@ class Run:
         # exchange after sweep s is (s + sweep_origin) // swap_every: a resumed run continues the
         # numbering, so no uniform is drawn twice.
         if temper_cfg is not None:
-            return _lib.TemperGroup(self.engines, temper_cfg["betas"], seed=self.seed)
+            return _lib.TemperGroup(self.engines, temper_cfg["betas"], seed=self.seed,
+                                    patch=temper_cfg.get("patch"))
         return None
 
     def _loop(self, min_acceptance_rate, sweeps_per_call, checkpoint, temper_group):
@@ -762,7 +769,8 @@ class Run:
         self.tempering = None
         if temper_group is not None:
             self.tempering = _tempering.TemperingReport.from_group(temper_group, temper_cfg["betas"],
-                                                                   temper_cfg["swap_every"], last_swap_round)
+                                                                   temper_cfg["swap_every"], last_swap_round,
+                                                                   temper_cfg.get("patch"))
             temper_group.close()
         self.parameters = self.extract_parameters()
         self.convolved_cube = Cube(data=self.simulate_convolved(cube_shape, self.parameters),

@@ -13,7 +13,7 @@ import math
 
 import numpy as np
 
-KEYS = ("betas", "rungs", "beta_min", "swap_every")
+KEYS = ("betas", "rungs", "beta_min", "swap_every", "patch")
 MAX_RUNGS = 64            # d3d_temper_create
 
 
@@ -31,7 +31,9 @@ def _integer(name, v, least):
 def check_keywords(tempering):
     """``tempering=`` as ``dict(betas=(1., ...), swap_every=n)``, or None when the keyword is None;
     ValueError otherwise.  A dict with either ``betas`` (1 first, strictly decreasing, finite and
-    > 0) or ``rungs`` plus ``beta_min`` (the geometric ladder), and ``swap_every`` (default 1)."""
+    > 0) or ``rungs`` plus ``beta_min`` (the geometric ladder), ``swap_every`` (default 1) and
+    ``patch`` (default None: the rungs trade whole cubes; an integer p >= 1: the unmasked spaxels of
+    tiles of p x p spaxels, d3d_temper_set_patch)."""
     if tempering is None:
         return None
     if not isinstance(tempering, dict):
@@ -73,7 +75,10 @@ def check_keywords(tempering):
         if r and not b < betas[r - 1]:
             raise ValueError("tempering betas= MUST be strictly decreasing, got %r after %r" % (b, betas[r - 1]))
     swap_every = _integer("swap_every", tempering.get("swap_every", 1), 1)
-    return dict(betas=betas, swap_every=swap_every)
+    cfg = dict(betas=betas, swap_every=swap_every)
+    if tempering.get("patch") is not None:      # (no key: whole cubes, the dict of a run without it)
+        cfg["patch"] = _integer("patch", tempering["patch"], 1)
+    return cfg
 
 
 def check_run(cfg, n_chains, host_model, model_name):
@@ -105,10 +110,16 @@ class TemperingReport(object):
     rung before each exchange; what thermodynamic integration would need --, ``energy_count``,
     ``labels`` (R: the rung whose start the state now at rung r descends from) and ``rounds``;
     ``last_round`` is the number of the last exchange round (None: none yet) and ``last`` its
-    ``energy`` (R), ``u``, ``logu`` and ``decided`` (R - 1; NaN / -1 for a pair not proposed)."""
+    ``energy`` (R), ``u``, ``logu`` and ``decided`` (R - 1; NaN / -1 for a pair not proposed).
+    With ``patch`` (the tile side; None: whole cubes) the rungs trade patches of spaxels:
+    ``patch_attempts`` / ``patch_accepts`` / ``patch_rates`` per pair count the patches proposed
+    and accepted, the ``swap_*`` counters stand still, ``labels`` is None (states no longer travel
+    whole) and ``last_patches`` is the per-tile record of the last round
+    (``TemperGroup.last_patches``)."""
 
     def __init__(self, betas, swap_every, rounds, attempts, accepts, energy_n, energy_mean, energy_m2, labels,
-                 last_round=None, last=None):
+                 last_round=None, last=None, patch=None, patch_attempts=None, patch_accepts=None,
+                 last_patches=None):
         self.betas = np.array(betas, dtype=np.float64)
         self.swap_every = int(swap_every)
         self.rounds = int(rounds)
@@ -123,23 +134,37 @@ class TemperingReport(object):
             self.energy_std = np.where(self.energy_count > 1,
                                        np.sqrt(np.array(energy_m2, dtype=np.float64)
                                                / np.maximum(self.energy_count - 1, 1)), np.nan)
-        self.labels = np.array(labels, dtype=np.int32)
+        self.patch = None if patch is None else int(patch)
+        self.labels = np.array(labels, dtype=np.int32) if self.patch is None else None
         self.last_round = None if last_round is None else int(last_round)
         self.last = last
+        n_pairs = len(self.betas) - 1
+        self.patch_attempts = np.zeros(n_pairs, dtype=np.int64) if patch_attempts is None \
+            else np.array(patch_attempts, dtype=np.int64)
+        self.patch_accepts = np.zeros(n_pairs, dtype=np.int64) if patch_accepts is None \
+            else np.array(patch_accepts, dtype=np.int64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            self.patch_rates = np.where(self.patch_attempts > 0,
+                                        self.patch_accepts / self.patch_attempts.astype(np.float64), np.nan)
+        self.last_patches = last_patches
 
     @classmethod
-    def from_group(cls, group, betas, swap_every, last_round=None):
+    def from_group(cls, group, betas, swap_every, last_round=None, patch=None):
         got = group.get()
+        patches = group.get_patches() if patch is not None else dict(attempts=None, accepts=None)
         return cls(betas, swap_every, got["rounds"], got["attempts"], got["accepts"], got["energy_n"],
                    got["energy_mean"], got["energy_m2"], got["labels"], last_round,
-                   group.last() if got["rounds"] > 0 else None)
+                   group.last() if got["rounds"] > 0 else None, patch, patches["attempts"], patches["accepts"],
+                   group.last_patches() if patch is not None and got["rounds"] > 0 else None)
 
     def save(self, prefix):
         """``<prefix>_tempering.npz``."""
         np.savez("%s_tempering.npz" % prefix, betas=self.betas, swap_every=self.swap_every, rounds=self.rounds,
                  swap_attempts=self.swap_attempts, swap_accepts=self.swap_accepts, swap_rates=self.swap_rates,
                  energy_count=self.energy_count, energy_mean=self.energy_mean, energy_std=self.energy_std,
-                 labels=self.labels)
+                 labels=np.zeros(0, dtype=np.int32) if self.labels is None else self.labels,
+                 patch=0 if self.patch is None else self.patch, patch_attempts=self.patch_attempts,
+                 patch_accepts=self.patch_accepts, patch_rates=self.patch_rates)
 
 
 def _fmt(values):
@@ -147,13 +172,15 @@ def _fmt(values):
 
 
 def state_record(cfg):
-    """What a checkpoint's state holds of the keyword."""
+    """What a checkpoint's state holds of the keyword (``tempering_patch``: 0 for whole cubes)."""
     return dict(tempering_betas=np.array(cfg["betas"], dtype=np.float64),
-                swap_every=np.array(cfg["swap_every"], dtype=np.int64))
+                swap_every=np.array(cfg["swap_every"], dtype=np.int64),
+                tempering_patch=np.array(cfg.get("patch") or 0, dtype=np.int64))
 
 
 def check_resume(state, files, cfg):
-    """ValueError when ``resume_state`` was written with another ladder or cadence than this run's."""
+    """ValueError when ``resume_state`` was written with another ladder, cadence or patch size than
+    this run's (a state without ``tempering_patch`` was written with whole-cube exchanges)."""
     saved = "tempering_betas" in files
     if cfg is None and not saved:
         return
@@ -170,3 +197,8 @@ def check_resume(state, files, cfg):
     if int(state["swap_every"]) != cfg["swap_every"]:
         raise ValueError("resume_state was written with tempering swap_every=%d; this run has swap_every=%d"
                          % (int(state["swap_every"]), cfg["swap_every"]))
+    old_patch = int(state["tempering_patch"]) if "tempering_patch" in files else 0
+    new_patch = cfg.get("patch") or 0
+    if old_patch != new_patch:
+        raise ValueError("resume_state was written with tempering patch=%s; this run has patch=%s"
+                         % (old_patch or None, new_patch or None))

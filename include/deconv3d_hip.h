@@ -564,6 +564,51 @@ int d3d_temper_get(d3d_temper *t, int64_t *rounds, int64_t *attempts, int64_t *a
  * accepted, 0 rejected, -1 not proposed).  Any pointer may be NULL.  Waits for the stream.
  * D3D_ERR_STATE before the first round. */
 int d3d_temper_last(d3d_temper *t, double *energy, double *u, double *logu, int32_t *decided);
+/* Exchange PATCHES of spaxels instead of whole cubes.  The energy gap of two rungs grows with the
+ * parameters of the whole field, so whole-cube swaps need a ladder as fine as sqrt(2 / parameters);
+ * a patch of p x p spaxels carries 3 p^2 parameters and its energy difference lives in the patch
+ * dilated by the FSF, so a coarse ladder swaps.  p = 0 (the default): whole cubes, exactly the three
+ * launches above.  p >= 1: later d3d_temper_swap calls run the rule below.  D3D_ERR_INVALID below 0
+ * (and above 2^24).
+ * The device block of the per-tile record is allocated by the first patch round.
+ *
+ * A patch round of rungs i, j = i + 1 (the pairs of the round's parity, as above):
+ *   tiles     (oy, ox) = (w0 mod p, w1 mod p), w = Philox4x32-10 at {0xFFFFFFFE, (uint32_t)round, 0, 1}
+ *             under the group's seed; spaxel (y, x) lies in tile (ty, tx) = ((y + p - oy) / p,
+ *             (x + p - ox) / p); nty = (H - 1 + p - oy) / p + 1, ntx likewise.  A PATCH P is the set
+ *             of unmasked spaxels of one tile; a tile without one is not proposed.
+ *   colours   my = 1 + ceil((fh - 1) / p), mx = 1 + ceil((fw - 1) / p): the tiles with
+ *             (ty mod my, tx mod mx) = (cy, cx) have disjoint FSF-dilated footprints (and for fh, fw
+ *             >= 3 are not adjacent).  One launch per colour, in ascending cy mx + cx; one workgroup
+ *             per (tile, pair), which decides by itself.
+ *   proposal  trade the parameters of P.  delta = sum_{s in P} [contribution(s, x_i[s]) -
+ *             contribution(s, x_j[s])] (the LSF-convolved line times the FSF: a contribution at
+ *             (y + dy, x + dx) carries fsf[fhh + dy, fhw + dx]); e_i' = e_i + delta, e_j' = e_j - delta.
+ *   ratio     Delta = (-(t0 + t2) - (t3 - t1)) + t4 with the five terms t0 = sum ivar_i e_i delta,
+ *             t1 = sum ivar_j e_j delta, t2 = 1/2 sum ivar_i delta^2, t3 = 1/2 sum ivar_j delta^2 (ivar_r
+ *             the rung's own 1/variance, beta_r / var) and t4 = Delta_prior: with d3d_prior_begin on
+ *             (every rung the same lam, D3D_ERR_INVALID otherwise), over the adjacent pairs <s, t> with
+ *             s in P, t unmasked outside the tile, -1/2 sum_k lam_k [(x_j[s] - x_i[t])^2 - (x_i[s] -
+ *             x_i[t])^2 + (x_i[s] - x_j[t])^2 - (x_j[s] - x_j[t])^2]; 0 with the prior off.  Bounds and
+ *             ra cancel.  Sums in fp64 in a fixed order, no floating-point atomics.
+ *   decision  u = the first uniform of Philox at {0xFFFFFFFF, (uint32_t)round, i, 2 + ty ntx + tx}
+ *             (word 1 is the whole-cube swap, word 0 the chains); accepted iff log(u) < Delta.  Then
+ *             e_i += delta, e_j -= delta and the (a, c, w) of the spaxels of P trade places.
+ * The round still computes E_r and folds it -- of the state before the exchange -- into the rungs'
+ * moments, but takes no whole-cube decision: d3d_temper_last reports every pair as not proposed,
+ * the whole-cube attempts / accepts stand still, and labels stay as created (states no longer
+ * travel whole).  Every rung's SLOT_TMP0 is overwritten (the lines of the round). */
+int d3d_temper_set_patch(d3d_temper *t, int p);
+/* The last round, when it was a patch round (D3D_ERR_STATE otherwise): geometry = {oy, ox, nty,
+ * ntx, my, mx}; per (pair i, tile ty ntx + tx), i major: terms [n-1][nty ntx][5] = t0 .. t4 above,
+ * u, logu [n-1][nty ntx] and decided [n-1][nty ntx] (1 accepted, 0 rejected, -1 not proposed: the
+ * other parity, or no unmasked spaxel; NaN terms, u, logu there).  Any pointer may be NULL: ask for
+ * the geometry first to size the rest.  Waits for the stream. */
+int d3d_temper_last_patches(d3d_temper *t, int32_t geometry[6], double *terms, double *u, double *logu,
+                            int32_t *decided);
+/* Patches proposed and accepted per pair [n-1] since the group was made (zeros before the first
+ * patch round).  Any pointer may be NULL.  Waits for the stream. */
+int d3d_temper_get_patches(d3d_temper *t, int64_t *attempts, int64_t *accepts);
 int d3d_temper_destroy(d3d_temper *t);
 
 /* ---- spatial tiling (one chain over several GPUs) --------- */

@@ -7,7 +7,12 @@ spaxel started at the truth with its centre `off` channels away: the line it sho
 the reach of a local step, and the neighbours -- started wrong alike -- explain part of its flux.  The
 share of the bright spaxels (a > 3) whose mean c over the last quarter of the chain lies within one
 channel of the truth, without tempering and with it (cold rung), at equal sweeps per rung; the swap
-rates per pair and the rungs' mean energies.  Reported as measured: DESIGN.md section 8i."""
+rates per pair and the rungs' mean energies.  Reported as measured: DESIGN.md section 8i.
+
+    python tools/temper_modes.py --patch P [...]
+
+adds the same ladder with the exchange of patches of P x P spaxels (Run(tempering=dict(..., patch=P)):
+DESIGN.md section 8j); `--patch 1,2,4,10` runs one after the other."""
 import os
 import sys
 import time
@@ -19,6 +24,9 @@ sys.path.insert(0, ROOT)
 from deconv3d_amd import MUSE, Run, _lib  # noqa: E402
 
 args = dict(a.split("=", 1) for a in sys.argv[1:] if "=" in a)
+if "--patch" in sys.argv:
+    args["patch"] = sys.argv[sys.argv.index("--patch") + 1]
+patches = [int(v) for v in args["patch"].split(",")] if args.get("patch") else []
 sweeps, rungs = int(args.get("sweeps", 1000)), int(args.get("rungs", 6))
 beta_min, off = float(args.get("beta_min", 0.02)), float(args.get("off", 10))
 D = 64
@@ -46,7 +54,9 @@ kw = dict(variance=np.full(clean.shape, sigma ** 2), max_iterations=sweeps, min_
           sweeps_per_call=64)
 for label, more in (("without tempering", {}),
                     ("tempering, %d rungs down to beta %g, swap_every 1" % (rungs, beta_min),
-                     dict(tempering=dict(rungs=rungs, beta_min=beta_min)))):
+                     dict(tempering=dict(rungs=rungs, beta_min=beta_min)))) + tuple(
+        ("tempering, %d rungs down to beta %g, patch %d" % (rungs, beta_min, p),
+         dict(tempering=dict(rungs=rungs, beta_min=beta_min, patch=p))) for p in patches):
     t0 = time.perf_counter()
     run = Run(cube, inst, **dict(kw, **more))
     dt = time.perf_counter() - t0
@@ -60,3 +70,6 @@ for label, more in (("without tempering", {}),
             np.round(run.tempering.betas, 4), np.round(run.tempering.swap_rates, 3),
             np.round(run.tempering.energy_mean, 1), np.round(run.tempering.energy_std, 1), run.tempering.labels),
             flush=True)
+        if run.tempering.patch is not None:
+            print("    patch rates %s of %s proposed" % (np.round(run.tempering.patch_rates, 3),
+                                                        run.tempering.patch_attempts), flush=True)

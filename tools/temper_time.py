@@ -13,7 +13,14 @@ and beside them one sweep of all rungs (d3d_mh_sweeps_batch), the work a round s
 
 HIP events on the leader's stream around the call, median of 7 repetitions (20 rounds per repetition
 where none is accepted); the wall clock of the call with the wait for the stream beside it.
-profiles/temper_time.txt."""
+profiles/temper_time.txt.
+
+    python tools/temper_time.py --patch P [shapes=...]
+
+times the exchange of patches of P x P spaxels instead (d3d_temper_set_patch: the energies, the
+lines of the proposed rungs, one k_temper_patch launch per tile colour), the same two states -- the
+round right after arming, in which (nearly) every patch is accepted, and the same round repeated,
+in which (nearly) none is; the shares are printed -- and writes profiles/patch_time.txt."""
 import os
 import sys
 import time
@@ -23,6 +30,15 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 args = dict(a.split("=", 1) for a in sys.argv[1:] if "=" in a)
+if "--patch" in sys.argv:
+    args["patch"] = sys.argv[sys.argv.index("--patch") + 1]
+PATCH = int(args.get("patch", 0))
+LINES = []
+
+
+def report(line):
+    print(line, flush=True)
+    LINES.append(line)
 SHAPES = [tuple(int(v) for v in s.split(",")) for s in args.get("shapes", "64,64,64,8;128,300,300,2").split(";")]
 REPS = 7
 
@@ -58,30 +74,43 @@ def measure(D, H, W, R):
         ms = lead.timer_stop()
         return ms * 1e3 / per, (time.perf_counter() - t0) * 1e6 / per
 
-    with _lib.TemperGroup(engines, betas, seed=1) as group:
+    def share():
+        d = group.last_patches()["decided"]
+        return int((d == 1).sum()), int((d >= 0).sum())
+
+    with _lib.TemperGroup(engines, betas, seed=1, patch=PATCH or None) as group:
         arm()
         group.swap(0)                                  # warm-up: code objects, first launches
-        assert (group.last()["decided"][0::2] == 1).all()
-        acc, rej = [], []
+        assert PATCH or (group.last()["decided"][0::2] == 1).all()
+        acc, rej, shares = [], [], [None, None]
         for _ in range(REPS):
             arm()
             acc.append(timed(lambda: group.swap(0)))
-            assert (group.last()["decided"][0::2] == 1).all()
+            assert PATCH or (group.last()["decided"][0::2] == 1).all()
+            shares[0] = share() if PATCH else None
             rej.append(timed(lambda: group.swap(0), per=20))
-            assert (group.last()["decided"][0::2] == 0).all()
+            assert PATCH or (group.last()["decided"][0::2] == 0).all()
+            shares[1] = share() if PATCH else None
         _lib.mh_sweeps_batch(engines, 2, first_sweep=1)
         sweep = [timed(lambda: _lib.mh_sweeps_batch(engines, 1, first_sweep=3)) for _ in range(REPS)]
     for eng in engines:
         eng.close()
     pairs = R // 2
     moved = pairs * 4 * (lead.shape[1] * lead.shape[2] * ((D + 1) // 2 * 2 + 3)) * 8 / 1e6
-    for name, rows in (("every pair accepted", acc), ("no pair accepted", rej), ("one sweep of all rungs", sweep)):
+    names = ("every pair accepted", "no pair accepted") if not PATCH else (
+        "patch %d, %d of %d patches accepted" % ((PATCH,) + shares[0]),
+        "patch %d, %d of %d patches accepted" % ((PATCH,) + shares[1]))
+    for name, rows in ((names[0], acc), (names[1], rej), ("one sweep of all rungs", sweep)):
         dev, wall = np.median([r[0] for r in rows]), np.median([r[1] for r in rows])
-        print("%dx%dx%d x %d rungs, %d pair(s) proposed  %-24s %10.1f us on the device  %10.1f us wall clock"
-              % (W, H, D, R, pairs, name, dev, wall), flush=True)
-    print("    (an accepted round reads and writes %.1f MB of residuals and parameters; the energies read %.1f MB)"
-          % (moved, R * 2 * H * W * ((D + 1) // 2 * 2) * 8 / 1e6), flush=True)
+        report("%dx%dx%d x %d rungs, %d pair(s) proposed  %-40s %10.1f us on the device  %10.1f us wall clock"
+               % (W, H, D, R, pairs, name, dev, wall))
+    if not PATCH:
+        report("    (an accepted round reads and writes %.1f MB of residuals and parameters; the energies read %.1f MB)"
+               % (moved, R * 2 * H * W * ((D + 1) // 2 * 2) * 8 / 1e6))
 
 
 for shape in SHAPES:
     measure(*shape)
+if PATCH:
+    with open(os.path.join(ROOT, "profiles", "patch_time.txt"), "w") as f:
+        f.write("\n".join(LINES) + "\n")
