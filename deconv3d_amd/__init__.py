@@ -15,6 +15,8 @@ from . import posterior  # noqa: F401
 from .posterior import PosteriorHistograms, PosteriorMoments  # noqa: F401
 from . import prepare  # noqa: F401
 from .prepare import Prepared, prepare_cube  # noqa: F401
+from . import regions  # noqa: F401
+from .regions import RegionPosterior  # noqa: F401
 from .run import Run, logger  # noqa: F401
 from . import search  # noqa: F401
 from .search import LineSearch, line_search  # noqa: F401

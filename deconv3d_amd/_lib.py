@@ -39,6 +39,7 @@ SYMBOLS = [
     "d3d_post_begin", "d3d_post_schedule", "d3d_post_accumulate", "d3d_post_count", "d3d_post_get",
     "d3d_post_end",
     "d3d_hist_begin", "d3d_hist_count", "d3d_hist_get", "d3d_hist_quantiles", "d3d_hist_end",
+    "d3d_region_begin", "d3d_region_count", "d3d_region_get", "d3d_region_end",
     "d3d_adapt_begin", "d3d_adapt_get", "d3d_adapt_set", "d3d_adapt_end",
     "d3d_prior_begin", "d3d_prior_get", "d3d_prior_end", "d3d_prior_energy",
     "d3d_line_search",
@@ -65,6 +66,13 @@ HIST_PROTOTYPES = {
     "d3d_hist_quantiles": [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                            C.POINTER(C.c_double)],
     "d3d_hist_end": [],
+}
+# region posteriors (a table for the same reason: tools/region_time.py loads the parent's library)
+REGION_PROTOTYPES = {
+    "d3d_region_begin": [C.POINTER(C.c_int32), C.c_int, C.c_int64, C.c_int],
+    "d3d_region_count": [C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "d3d_region_get": [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)],
+    "d3d_region_end": [],
 }
 # per-spaxel jump scales (a table for the same reason: tools that load the parent's library)
 ADAPT_PROTOTYPES = {
@@ -111,6 +119,7 @@ TEMPER_PROTOTYPES = {
 }
 POST_CLEAN, POST_CONVOLVED = 1, 2                     # d3d_post_begin: bits of `what`
 POST_PARAMETERS, POST_CLEAN_CUBE, POST_CONVOLVED_CUBE = 0, 1, 2   # d3d_post_get: `which`
+REGION_SPECTRA = 1                                    # d3d_region_begin: bit of `what`
 
 PLAN_PARAMS = 16          # D3D_PLAN_PARAMS
 COMM_UID_BYTES = 128      # D3D_COMM_UID_BYTES
@@ -233,7 +242,8 @@ def load():
     lib.d3d_apply_updates.argtypes = [ctx_p, C.c_int, dbl_p]
     for name, argtypes in (list(POST_PROTOTYPES.items()) + list(ADAPT_PROTOTYPES.items())
                            + list(SEARCH_PROTOTYPES.items()) + list(PREP_PROTOTYPES.items())
-                           + list(PRIOR_PROTOTYPES.items()) + list(HIST_PROTOTYPES.items())):
+                           + list(PRIOR_PROTOTYPES.items()) + list(HIST_PROTOTYPES.items())
+                           + list(REGION_PROTOTYPES.items())):
         getattr(lib, name).argtypes = [ctx_p] + argtypes
     for name, argtypes in TEMPER_PROTOTYPES.items():
         getattr(lib, name).argtypes = argtypes
@@ -889,6 +899,47 @@ class Engine(object):
 
     def hist_end(self):
         _check(self._lib.d3d_hist_end(self._ctx))
+
+    # -- region posteriors ----------------------------------------------------------
+    def region_begin(self, labels, K=None, capacity=0, spectra=True):
+        """Lay out the regions 1 .. ``K`` (default: the largest label) of the int32 (H, W) map
+        ``labels`` (0: no region), allocate a series of ``capacity`` samples of their (F, C, S) and,
+        with ``spectra``, their summed clean spectra's moments (include/deconv3d_hip.h:
+        d3d_region_begin), and start the moments afresh.  Needs post_begin."""
+        labels = np.asarray(labels)
+        if labels.shape != self.shape[1:] or labels.dtype.kind not in "iu":
+            raise ValueError("labels: an integer array of shape %s, got %s of %s"
+                             % (self.shape[1:], labels.dtype, labels.shape))
+        if labels.size and (labels.min() < -2 ** 31 or labels.max() >= 2 ** 31):
+            raise ValueError("labels: beyond int32")
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        K = int(lab.max()) if K is None else int(K)
+        _check(self._lib.d3d_region_begin(self._ctx, lab.ctypes.data_as(C.POINTER(C.c_int32)), K, int(capacity),
+                                          REGION_SPECTRA if spectra else 0))
+        self._region = (K, bool(spectra))
+
+    def region_count(self):
+        """(samples taken, rows of the series): the second stops at the capacity."""
+        n, stored = C.c_int64(0), C.c_int64(0)
+        _check(self._lib.d3d_region_count(self._ctx, C.byref(n), C.byref(stored)))
+        return n.value, stored.value
+
+    def region_get(self):
+        """(series (stored, K, 3) = F | C | S, spectrum mean (K, D), spectrum M2 (K, D), sizes (K));
+        the spectra are None when they were not begun."""
+        K, spectra = getattr(self, "_region", None) or (0, False)
+        stored = self.region_count()[1]
+        series = np.empty((stored, K, 3), dtype=np.float64)
+        mean = np.empty((K, self.shape[0]), dtype=np.float64) if spectra else None
+        m2 = np.empty((K, self.shape[0]), dtype=np.float64) if spectra else None
+        sizes = np.empty(K, dtype=np.int32)
+        _check(self._lib.d3d_region_get(self._ctx, _dp(series), _dp(mean) if spectra else None,
+                                        _dp(m2) if spectra else None, sizes.ctypes.data_as(C.POINTER(C.c_int32))))
+        return series, mean, m2, sizes
+
+    def region_end(self):
+        _check(self._lib.d3d_region_end(self._ctx))
+        self._region = None
 
     # -- per-spaxel jump scales ---------------------------------------------------
     def adapt_begin(self, target=0.25, window=50, last_sweep=0, gain=2.0, scale_range=(1e-3, 1e3)):

@@ -406,8 +406,24 @@ void hist_free(d3d_ctx *c) {
     c->hist_on = c->hist_frozen = false;
 }
 
+void region_free(d3d_ctx *c) {
+    void *ptrs[] = {c->reg_member, c->reg_chunk, c->reg_first, c->reg_part, c->reg_fc, c->reg_series, c->reg_spart,
+                    c->reg_spec};
+    for (void *p : ptrs)
+        if (p) (void)hipFree(p);
+    c->reg_member = c->reg_first = nullptr;
+    c->reg_chunk = nullptr;
+    c->reg_part = c->reg_fc = c->reg_series = c->reg_spart = c->reg_spec = nullptr;
+    c->reg_on = false;
+    c->reg_K = c->reg_what = c->reg_nchunks = 0;
+    c->reg_cap = 0;
+    c->h_reg_labels.clear();
+    c->h_reg_sizes.clear();
+}
+
 void post_free(d3d_ctx *c) {
     hist_free(c);
+    region_free(c);
     for (double *&p : c->post_cube) {
         if (p) (void)hipFree(p);
         p = nullptr;
@@ -471,6 +487,49 @@ int post_reset(d3d_ctx *c) {
         HIP_TRY(hipMemsetAsync(c->hist_tails, 0, nser * 2 * sizeof(uint32_t), c->stream));
         HIP_TRY(hipMemsetAsync(c->hist_range, 0xff, nser * 2 * sizeof(double), c->stream));
     }
+    if (c->reg_on) {  // series and spectra zero; the count is the moments'
+        if (c->reg_series)
+            HIP_TRY(hipMemsetAsync(c->reg_series, 0, (size_t)c->reg_cap * c->reg_K * 3 * sizeof(double), c->stream));
+        if (c->reg_spec)
+            HIP_TRY(hipMemsetAsync(c->reg_spec, 0, (size_t)2 * c->reg_K * c->Dp * sizeof(double), c->stream));
+    }
+    return 0;
+}
+
+// The members of the regions under the mask in force, on the device (d3d_region_begin, and
+// d3d_set_data on a context with regions: its mask may have changed).  The tables that depend on
+// the number of chunks are allocated here; on failure the regions are freed.
+int region_members(d3d_ctx *c) {
+    std::vector<int> member, first;
+    std::vector<int4> chunk;
+    region_layout(c, member, chunk, first, c->h_reg_sizes);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    void *old[] = {c->reg_member, c->reg_chunk, c->reg_first, c->reg_part, c->reg_spart};
+    for (void *p : old)
+        if (p) (void)hipFree(p);
+    c->reg_member = c->reg_first = nullptr;
+    c->reg_chunk = nullptr;
+    c->reg_part = c->reg_spart = nullptr;
+    c->reg_nchunks = (int)chunk.size();
+    const size_t nm = std::max<size_t>(member.size(), 1), nc = std::max<size_t>(chunk.size(), 1);
+    hipError_t e = hipMalloc(&c->reg_member, nm * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&c->reg_chunk, nc * sizeof(int4));
+    if (e == hipSuccess) e = hipMalloc(&c->reg_first, first.size() * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&c->reg_part, nc * 4 * sizeof(double));
+    if (e == hipSuccess && (c->reg_what & 1)) e = hipMalloc(&c->reg_spart, nc * c->Dp * sizeof(double));
+    if (e == hipSuccess && !member.empty())
+        e = hipMemcpyAsync(c->reg_member, member.data(), member.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && !chunk.empty())
+        e = hipMemcpyAsync(c->reg_chunk, chunk.data(), chunk.size() * sizeof(int4), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(c->reg_first, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the host vectors go out of scope
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // the context stays usable for the chain and the moments
+        region_free(c);
+        return fail(D3D_ERR_HIP, "region posteriors (%zu members in %zu chunks): %s", member.size(), chunk.size(),
+                    hipGetErrorString(e));
+    }
     return 0;
 }
 
@@ -486,6 +545,8 @@ int d3dh::post_sample(d3d_ctx *c) {
         if (int rc = forward_into(c, c->slot[D3D_SLOT_SIM], false)) return rc;
     }
     if (int rc = launch_post_accum(c)) return rc;
+    if (c->reg_on)  // d3d_region_begin: the same sample, the same number
+        if (int rc = launch_region_sample(c)) return rc;
     ++c->post_n;
     if (c->hist_on) {  // d3d_hist_begin: the pilot's last sample freezes the ranges, later ones are binned
         if (c->post_n == c->hist_pilot) {
@@ -749,6 +810,7 @@ int d3d_ctx_destroy(d3d_ctx *c) {
         if (p) (void)hipFree(p);
     if (c->post_map) (void)hipFree(c->post_map);
     hist_free(c);
+    region_free(c);
     adapt_free(c);
     if (c->prior_part) (void)hipFree(c->prior_part);
     for (hipEvent_t e : c->halo_ev) (void)hipEventDestroy(e);
@@ -1165,6 +1227,8 @@ int d3d_set_data(d3d_ctx *c, const double *data, const double *var, double var_s
     c->have_data = true;
     c->err_valid = false;
     pend_clear(c);
+    if (c->reg_on)  // the members of a region are its unmasked spaxels
+        if (int rc2 = region_members(c)) return rc2;
     return post_reset(c);  // moments over two data sets mean nothing
 }
 
@@ -1672,6 +1736,78 @@ int d3d_hist_end(d3d_ctx *c) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     hist_free(c);
+    return D3D_OK;
+}
+
+int d3d_region_begin(d3d_ctx *c, const int32_t *labels, int K, int64_t capacity, int what) {
+    NEED(c && labels, D3D_ERR_INVALID, "NULL argument");
+    NEED(K >= 1, D3D_ERR_INVALID, "K = %d: at least one region", K);
+    NEED(capacity >= 0, D3D_ERR_INVALID, "capacity = %lld is negative", (long long)capacity);
+    NEED(what >= 0 && what <= 1, D3D_ERR_INVALID, "what = %d: bit 0 the spectra (0..1)", what);
+    for (long s = 0; s < c->HW; ++s)
+        NEED(labels[s] >= 0 && labels[s] <= K, D3D_ERR_INVALID, "labels[%ld] = %d lies outside 0 .. K = %d", s,
+             (int)labels[s], K);
+    NEED(!c->tiled, D3D_ERR_UNSUPPORTED,
+         "region posteriors on a tile: the parameters of its frame belong to other ranks");
+    NEED(c->post_on, D3D_ERR_STATE, "posterior moments not begun (d3d_post_begin)");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    region_free(c);
+    c->reg_K = K;
+    c->reg_what = what;
+    c->reg_cap = capacity;
+    c->h_reg_labels.assign(labels, labels + c->HW);
+    const size_t series_bytes = (size_t)capacity * K * 3 * sizeof(double);
+    const size_t spec_bytes = (what & 1) ? (size_t)2 * K * c->Dp * sizeof(double) : 0;
+    hipError_t e = hipMalloc(&c->reg_fc, (size_t)K * 2 * sizeof(double));
+    if (e == hipSuccess && series_bytes) e = hipMalloc(&c->reg_series, series_bytes);
+    if (e == hipSuccess && spec_bytes) e = hipMalloc(&c->reg_spec, spec_bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // the context stays usable for the chain and the moments
+        region_free(c);
+        return fail(D3D_ERR_HIP, "region posteriors (%zu bytes): %s", series_bytes + spec_bytes,
+                    hipGetErrorString(e));
+    }
+    if (int rc = region_members(c)) return rc;
+    c->reg_on = true;
+    return post_reset(c);  // the series' rows are the moments' samples
+}
+
+int d3d_region_count(d3d_ctx *c, int64_t *n, int64_t *stored) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    if (n) *n = c->reg_on ? c->post_n : 0;
+    if (stored) *stored = c->reg_on ? std::min<int64_t>(c->post_n, c->reg_cap) : 0;
+    return D3D_OK;
+}
+
+int d3d_region_get(d3d_ctx *c, double *series, double *spec_mean, double *spec_m2, int32_t *sizes) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    NEED(c->reg_on, D3D_ERR_STATE, "region posteriors not begun (d3d_region_begin)");
+    NEED(c->reg_spec || (!spec_mean && !spec_m2), D3D_ERR_STATE,
+         "the regions' spectra were not begun (d3d_region_begin what = %d)", c->reg_what);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t stored = (size_t)std::min<int64_t>(c->post_n, c->reg_cap);
+    if (series && stored)
+        HIP_TRY(hipMemcpyAsync(series, c->reg_series, stored * c->reg_K * 3 * sizeof(double), hipMemcpyDeviceToHost,
+                               c->stream));
+    // (K, Dp) on the device, (K, D) for the caller: the pad channel of an odd depth stays behind
+    const size_t row = (size_t)c->D * sizeof(double), pitch = (size_t)c->Dp * sizeof(double);
+    if (spec_mean)
+        HIP_TRY(hipMemcpy2DAsync(spec_mean, row, c->reg_spec, pitch, row, (size_t)c->reg_K, hipMemcpyDeviceToHost,
+                                 c->stream));
+    if (spec_m2)
+        HIP_TRY(hipMemcpy2DAsync(spec_m2, row, c->reg_spec + (size_t)c->reg_K * c->Dp, pitch, row, (size_t)c->reg_K,
+                                 hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (sizes) std::copy(c->h_reg_sizes.begin(), c->h_reg_sizes.end(), sizes);
+    return D3D_OK;
+}
+
+int d3d_region_end(d3d_ctx *c) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    region_free(c);
     return D3D_OK;
 }
 

@@ -1,7 +1,8 @@
 // Internal header of libdeconv3d_hip.so: the context struct and the launch
 // functions shared by the library's translation units (d3d_api.hip: C ABI and host
 // logic; d3d_spatial.hip: line / LSF / FSF kernels; d3d_mh.hip: the MH-within-Gibbs
-// kernels; d3d_sweep.hip: the sweep driver; d3d_post.hip: posterior moments; d3d_search.hip: the
+// kernels; d3d_sweep.hip: the sweep driver; d3d_post.hip: posterior moments; d3d_region.hip: region
+// posteriors; d3d_search.hip: the
 // matched-filter line search; d3d_prep.hip: continuum removal and channel noise of a raw cube;
 // d3d_temper.hip: replica exchange between tempered chains).
 // Not installed: the public interface is include/deconv3d_hip.h.
@@ -291,6 +292,23 @@ struct d3d_ctx {
     uint32_t *hist_bins = nullptr;   // [HW*4][64]
     uint32_t *hist_tails = nullptr;  // [HW*4][2]: below | above
     double *hist_range = nullptr;    // [HW*4][2]: lo | hi (NaN: not frozen yet, or masked)
+    // region posteriors (d3d_region_*): per sample of the moments the (F, C, S) of every labelled set
+    // of spaxels into a series, and its summed clean spectrum into a mean and M2 (d3d_region.hip).
+    // Nothing is allocated before d3d_region_begin.
+    bool reg_on = false;
+    int reg_K = 0, reg_what = 0;   // regions 1..K; bit 0 of what: the spectra
+    int64_t reg_cap = 0;           // rows of the series
+    int reg_nchunks = 0;
+    std::vector<int32_t> h_reg_labels;  // the caller's (H,W) map: d3d_set_data lays the members out again
+    std::vector<int32_t> h_reg_sizes;   // [K] members of every region
+    int *reg_member = nullptr;     // [members] spaxels, region after region
+    int4 *reg_chunk = nullptr;     // [chunks] {first member, members, region, -}
+    int *reg_first = nullptr;      // [K + 1] first chunk of every region
+    double *reg_part = nullptr;    // [chunks][4] scalar partials
+    double *reg_fc = nullptr;      // [K][2] F and C between the passes
+    double *reg_series = nullptr;  // [reg_cap][K][3]
+    double *reg_spart = nullptr;   // [chunks][Dp] spectrum partials (spectra on)
+    double *reg_spec = nullptr;    // [2][K][Dp] mean | M2 (spectra on)
     // per-spaxel jump scales (d3d_adapt_*): every `adapt_window` sweeps of d3d_mh_sweeps each
     // spaxel's scale moves towards the target acceptance rate (k_mh_adapt), up to sweep
     // adapt_last; the counters then go on counting.  Nothing is allocated before d3d_adapt_begin.
@@ -344,6 +362,13 @@ int launch_post_accum(d3d_ctx *c);
 int launch_hist_freeze(d3d_ctx *c);
 int launch_hist_accum(d3d_ctx *c);
 int launch_hist_quantiles(d3d_ctx *c, int n_q, const double *q, double *quantiles, double *mode, double *outside);
+// d3d_post.hip: F = a w flux_factor(c)
+double flux_factor(const d3d_ctx *c);
+// d3d_region.hip: the members, chunks and chunk offsets of c->h_reg_labels under c->h_mask; one
+// sample (the chain state) into the series and the spectra, as sample number c->post_n + 1
+void region_layout(const d3d_ctx *c, std::vector<int> &member, std::vector<int4> &chunk, std::vector<int> &first,
+                   std::vector<int32_t> &sizes);
+int launch_region_sample(d3d_ctx *c);
 // d3d_mh.hip: after sweep `s` of a d3d_mh_sweeps call (d3d_adapt_begin): the sweep is counted and,
 // where it fills a window at or before the last adapted sweep, the jump scales take a step
 int adapt_after_sweep(d3d_ctx *c, int s);

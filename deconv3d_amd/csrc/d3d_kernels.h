@@ -164,6 +164,15 @@ __device__ __forceinline__ double unit_line(const LineShape &L, double z, double
     return s;
 }
 
+// Welford's update of (mean, M2) with sample m, the n-th: plain IEEE operations in this order
+// (no contraction: the moments do not depend on what the compiler fuses).
+__device__ __forceinline__ void welford(double &mean, double &m2, double m, double n) {
+#pragma clang fp contract(off)
+    const double delta = m - mean;
+    mean += delta / n;
+    m2 += delta * (m - mean);
+}
+
 struct SpectralArgs {
     int D, Dp, HL, N, ntaps;
     long nspax;

@@ -45,15 +45,6 @@ __device__ __forceinline__ void post_store(double *p, double2 v) {
     }
 }
 
-// Welford's update of (mean, M2) with sample m, the n-th: plain IEEE operations in this order
-// (no contraction: the moments do not depend on what the compiler fuses).
-__device__ __forceinline__ void welford(double &mean, double &m2, double m, double n) {
-#pragma clang fp contract(off)
-    const double delta = m - mean;
-    mean += delta / n;
-    m2 += delta * (m - mean);
-}
-
 template <bool NTV>
 __device__ __forceinline__ void welford_pair(double *mean, double *m2, double2 m, double n) {
     double2 mu = post_load<NTV>(mean), s = post_load<NTV>(m2);
@@ -252,7 +243,7 @@ static int launch_post_t(d3d_ctx *c, const d3d::PostArgs &A) {
 }
 
 // F = a w flux_k
-static double flux_factor(const d3d_ctx *c) {
+double flux_factor(const d3d_ctx *c) {
     double ratios = 0.0;
     for (int k = 0; k < c->line.K; ++k) ratios += c->line.ratio[k];
     if (c->line.tab) return c->line_tab_flux * ratios;  // (the table's own integral: d3d_set_line_table)

@@ -90,6 +90,7 @@ class PosteriorMoments(object):
         self._template = template
         self._cache = {}
         self.histograms = histograms    # a PosteriorHistograms, or None
+        self.regions = None             # a regions.RegionPosterior (Run(regions=...)), or None
 
     @classmethod
     def from_engine(cls, engine, template=None, histograms=False):
@@ -162,7 +163,8 @@ class PosteriorMoments(object):
     def save(self, prefix, clobber=False):
         """``<prefix>_posterior_{clean,convolved}_{mean,std}.fits`` and
         ``<prefix>_posterior_parameters.npz`` (count, parameters_mean, parameters_std,
-        flux_mean, flux_std), beside the files of ``Run.save(prefix)``."""
+        flux_mean, flux_std), beside the files of ``Run.save(prefix)``; with regions their
+        ``<prefix>_posterior_regions.npz``."""
         for name in ("clean", "convolved"):
             for kind in ("mean", "std"):
                 self._cube(getattr(self, "%s_%s" % (name, kind))).to_fits(
@@ -170,6 +172,8 @@ class PosteriorMoments(object):
         np.savez("%s_posterior_parameters.npz" % prefix, count=self.count,
                  parameters_mean=self.parameters_mean, parameters_std=self.parameters_std,
                  flux_mean=self.flux_mean, flux_std=self.flux_std)
+        if self.regions is not None:
+            self.regions.save(prefix)
 
 
 class PosteriorHistograms(object):

@@ -38,6 +38,7 @@ from os.path import splitext
 import numpy as np
 
 from . import _lib, adapt as _adapt, ensemble, posterior as _posterior, prepare as _prepare, \
+    regions as _regions, \
     prior as _prior, search as _search, tempering as _tempering
 from .cube import Cube, read_fits
 from .host_model import HostModelChain
@@ -180,6 +181,23 @@ class Run:
     (the chains' ranges differ).  A run that cannot accumulate more than ``pilot`` samples logs a
     warning.  Not part of a checkpoint, like the moments.  Costs 1120 bytes per spaxel and chain.
 
+    ``regions=`` (default ``None``: off, nothing allocated or launched, the chain is bit for bit
+    what it is without the keyword; needs ``posterior_burn_in``) follows SETS of spaxels: an (H, W)
+    integer label map (0: no region, any positive value names one;
+    :func:`deconv3d_amd.regions.blocks` and :func:`deconv3d_amd.regions.annuli` build some) or
+    ``dict(labels=, spectra=True)``.  For every accumulated sample the device sums, in a fixed
+    order, each region's flux ``F = sum F_i``, flux-weighted centre ``C = sum F_i c_i / F`` and
+    width ``S = sqrt(sum F_i (w_i^2 + (c_i - C)^2) / F)`` over its unmasked spaxels into a series,
+    and (``spectra``) folds the region's summed clean spectrum into a mean and a standard deviation
+    (d3d_region_*).  ``run.posterior.regions`` is a :class:`deconv3d_amd.regions.RegionPosterior`
+    (``ids``, ``sizes``, ``count``, the series ``flux`` / ``centre`` / ``width`` (n, K), their
+    ``*_mean`` / ``*_std``, ``quantiles(qs)``, ``flux_covariance()``, ``spectrum_mean``,
+    ``spectrum_std``, ``save(prefix)``); ``run.posterior.save`` writes it too.  With ``chains=R``
+    every chain keeps its own, ``run.posteriors[r].regions``, and the pooled one concatenates the
+    series chain by chain and pools the spectra; ``tempering=`` follows rung 0 only.  A
+    host-evaluated line model raises ``NotImplementedError``.  Not part of a checkpoint, like the
+    moments.  Costs ``24 K`` bytes per accumulated sample and chain.
+
     ``adapt_sweeps=N`` (default ``None``: off, nothing allocated or launched, the chain is bit for
     bit what it is without the keyword) gives every spaxel its own multiplicative jump scale: the
     reference proposes all of them with the one ``jump_amplitude`` (lib/run.py:251-262, 570-579),
@@ -292,12 +310,13 @@ class Run:
         prepare=None,
         smoothness=None,
         tempering=None,
+        regions=None,
     ):
         prepare_cfg, search_cfg, posterior_burn_in, posterior_every, hist_cfg = self._check_keywords(
             prepare, initial_search, initial_parameters, resume_state, posterior_burn_in,
             posterior_every, posterior_histograms, adapt_sweeps, adapt_window, adapt_target,
             adapt_gain, adapt_scale_range, smoothness, tempering, keep_one_in, write_every,
-            max_iterations, chains)
+            max_iterations, chains, regions)
         self._read_inputs(cube, prepare_cfg, mask, variance, device)
         self._read_instrument(instrument)
         self._read_model(model, jump_amplitude, gibbs_apriori_variance, seed, posterior_burn_in)
@@ -320,7 +339,7 @@ class Run:
     def _check_keywords(self, prepare, initial_search, initial_parameters, resume_state,
                         posterior_burn_in, posterior_every, posterior_histograms, adapt_sweeps,
                         adapt_window, adapt_target, adapt_gain, adapt_scale_range, smoothness,
-                        tempering, keep_one_in, write_every, max_iterations, chains):
+                        tempering, keep_one_in, write_every, max_iterations, chains, regions):
         """The keywords' own checks.  Returns the checked ``prepare=`` and ``initial_search=``,
         the posterior schedule and the checked ``posterior_histograms=``."""
         # (before anything else: no device work yet)
@@ -330,6 +349,8 @@ class Run:
             posterior_burn_in, posterior_every = _posterior.check_schedule(posterior_burn_in,
                                                                            posterior_every)
         hist_cfg = _posterior.check_histograms(posterior_histograms, posterior_burn_in)
+        # (the map's shape is checked against the cube's in _read_inputs)
+        self._regions_cfg = _regions.check_regions(regions, None, posterior_burn_in)
         adapt_cfg = None
         if adapt_sweeps is not None:
             adapt_cfg = _AdaptKeywords(*_adapt.check_keywords(adapt_sweeps, adapt_window, adapt_target,
@@ -371,6 +392,8 @@ class Run:
             raise TypeError("Provided cube is not a HyperspectralCube")
         if cube.is_empty():
             raise ValueError("Provided cube is empty")
+        if self._regions_cfg is not None:
+            _regions.check_shape(self._regions_cfg["labels"], cube.data.shape[1:])
         # ---- prepare=: the continuum-free cube and its per-channel variance take the place of
         # the raw cube and of a variance that was not given (or, rescale=True, of the given one)
         self.prepared = None
@@ -464,6 +487,10 @@ class Run:
         # host (host_model.HostModelChain): same device kernels for LSF, window statistics,
         # accept, Gibbs draw and residual, but python-speed proposals and modelize() calls.
         self._host_model = not model_is_on_device(self.model)
+        # (before posterior_burn_in=, which regions= needs: the refusal names the keyword that asked)
+        if self._regions_cfg is not None and self._host_model:
+            self._refuse_host_model("regions=", "the device follows regions only for the models it "
+                                    "evaluates itself")
         if posterior_burn_in is not None and self._host_model:
             self._refuse_host_model("posterior_burn_in=", "the device accumulates posterior moments "
                                     "only for the models it evaluates itself")
@@ -631,6 +658,10 @@ class Run:
                     eng.post_schedule(posterior_burn_in, posterior_every)
                     if hist_cfg is not None:
                         eng.hist_begin(hist_cfg["pilot"], hist_cfg["span"])
+                    if self._regions_cfg is not None:
+                        eng.region_begin(self._regions_cfg["labels"], len(self._regions_cfg["ids"]),
+                                         len(range(posterior_burn_in, self.max_iterations, posterior_every)),
+                                         self._regions_cfg["spectra"])
                 if adapt_cfg is not None:
                     # (the last adapted sweep in the numbering of the whole run: a resumed
                     # segment counts from its sweep origin)
@@ -787,6 +818,11 @@ class Run:
                     pm.histograms.pilot, pm.histograms.span = hist_cfg["pilot"], hist_cfg["span"]
             self.posterior = self.posteriors[0] if len(self.posteriors) == 1 else \
                 _posterior.pooled(self.posteriors, self.cube)
+            if self._regions_cfg is not None:      # every chain its own; the pooled one concatenates them
+                for pm, eng in zip(self.posteriors, self.engines):
+                    pm.regions = _regions.RegionPosterior.from_engine(eng, self._regions_cfg["ids"])
+                if len(self.posteriors) > 1:
+                    self.posterior.regions = _regions.pooled([pm.regions for pm in self.posteriors])
             if self.posterior.count == 0:
                 self.logger.warning("posterior_burn_in=%d: the run stopped at iteration %d, before "
                                     "the first accumulated sweep; run.posterior holds no sample"

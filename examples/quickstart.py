@@ -23,7 +23,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from deconv3d_amd import MUSE, Run, _lib  # noqa: E402
+from deconv3d_amd import MUSE, Run, _lib, regions  # noqa: E402
 
 iterations = int(sys.argv[1]) if len(sys.argv) > 1 else 5000
 D = H = W = 64
@@ -49,7 +49,8 @@ t0 = time.perf_counter()
 run = Run(cube, inst, variance=np.full(clean.shape, sigma ** 2), max_iterations=iterations,
           keep_one_in=10, min_acceptance_rate=0., jump_amplitude=[0., 0.5, 0.2],
           gibbs_apriori_variance=100., seed=1,   # amplitude prior, as tests/read_mat.py:109-119 sets one
-          posterior_burn_in=max(1, iterations // 2))   # mean / std of the samples' cubes, kept on the device
+          posterior_burn_in=max(1, iterations // 2),   # mean / std of the samples' cubes, kept on the device
+          regions=regions.annuli((H, W), (H / 2., W / 2.), [0., 4., 8., 12., 16.]))   # ... and four rings' (F, C, S)
 dt = time.perf_counter() - t0
 burn = run.chain.shape[0] // 2
 post = run.chain[burn:].mean(axis=0)                # posterior means over the second half
@@ -73,6 +74,16 @@ bright = truth[..., 0] > 3.0
 print("bright spaxels (%d): median |centre - truth| = %.2f channels, |width - truth| = %.2f channels" % (
     bright.sum(), np.median(np.abs(post[..., 1] - truth[..., 1])[bright]),
     np.median(np.abs(post[..., 2] - truth[..., 2])[bright])))
+# What IS determined is a set of spaxels: every ring's summed flux, flux-weighted centre and width per
+# sample (run.posterior.regions, summed on the device in a fixed order) and their scatter over the samples.
+rings = run.posterior.regions
+ring_of = regions.annuli((H, W), (H / 2., W / 2.), [0., 4., 8., 12., 16.])
+F_true = truth[..., 0] * truth[..., 2] * np.sqrt(2. * np.pi)
+for k, label in enumerate(rings.ids):
+    inside = ring_of == label
+    print("ring %d (%4d spaxels): flux %9.2f +- %.2f (truth %9.2f), centre %.3f +- %.3f, width %.3f +- %.3f channels" % (
+        label, rings.sizes[k], rings.flux_mean[k], rings.flux_std[k], F_true[inside].sum(),
+        rings.centre_mean[k], rings.centre_std[k], rings.width_mean[k], rings.width_std[k]))
 
 
 # ---- per-spaxel jump scales: adapt_sweeps=N ----------------------------------------------------

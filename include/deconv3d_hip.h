@@ -374,6 +374,51 @@ int d3d_hist_quantiles(d3d_ctx *ctx, int n_q, const double *q, double *quantiles
 /* Free the counters; the moments go on. */
 int d3d_hist_end(d3d_ctx *ctx);
 
+/* ---- region posteriors ---------------------------------------------------- */
+/* Under an FSF wider than a spaxel neighbours trade flux, and what is well determined is a SET of
+ * spaxels: the flux of an aperture, the flux-weighted velocity and dispersion of a ring, the
+ * integrated deconvolved spectrum of a region.  The reference's only estimator is the mean of the
+ * saved chain per spaxel (Run.extract_parameters, lib/run.py:581-593), and the std of a sum is not
+ * derivable from per-spaxel moments: the covariances between trading neighbours are what matters.
+ * These entries keep, for every sample the moments take (number n, counted from 1) and every region
+ * k = 1..K of an int32 label map (H,W) -- 0: no region --
+ *   F_i = (a_i w_i) flux_k of member i (the F of d3d_post_get's map),
+ *   F_k = sum F_i,   C_k = (sum F_i c_i) / F_k,
+ *   S_k = sqrt((sum F_i (w_i^2 + (c_i - C_k)^2)) / F_k)   (a second pass, with C_k known),
+ *   F_k == 0 (no member, or no flux):  (F, C, S) = (0, NaN, NaN),
+ * as row n - 1 of a series (capacity, K, 3) -- past `capacity` the series stops, nothing else does --
+ * and, with the spectra on, the region's clean spectrum of the sample (lib/run.py:597-621 per
+ * sample, summed over the members)
+ *   s_k(z) = sum_i a_i unit_line(z, c_i, w_i)
+ * into a running mean and M2 (K, D) by the Welford update of the moments.
+ * THE ORDER OF EVERY SUM IS FIXED; it depends on the label map and the mask alone:
+ *   members of region k: its unmasked spaxels in row-major order, m = 0 .. n_k - 1, cut into
+ *     consecutive chunks of 64 (the last may be short);
+ *   a scalar chunk partial: its 64 terms (absent ones +0.0) folded by halves,
+ *     v[0:32] + v[32:64], then v[0:16] + v[16:32], ... down to one;
+ *   a spectrum chunk partial, per channel: the members' terms one after the other in ascending
+ *     m, starting from +0.0;
+ *   a region's sum: its chunk partials one after the other in ascending order, from +0.0.
+ * Every step is a plain IEEE double operation (no contraction), so F, C and S -- only + * / sqrt
+ * -- are reproducible bit for bit on the host (tests/region_oracle.py). */
+
+/* Lay out the members of the K regions of `labels` under the mask in force (d3d_set_data lays
+ * them out again), allocate the series and -- what bit 0 -- the spectra, and start the moments
+ * afresh (count 0).  Needs d3d_post_begin: D3D_ERR_STATE.  A tile ctx is D3D_ERR_UNSUPPORTED.  A
+ * label outside 0..K, K < 1, capacity < 0 or what outside 0..1: D3D_ERR_INVALID.  An allocation
+ * failure is D3D_ERR_HIP, frees what it got and leaves the ctx usable.  Whatever resets the moments
+ * zeroes the series and the spectra; d3d_post_begin and d3d_post_end free them.  A ctx that never
+ * calls it allocates and launches nothing for regions. */
+int d3d_region_begin(d3d_ctx *ctx, const int32_t *labels, int K, int64_t capacity, int what);
+/* *n = samples taken (the moments' count), *stored = rows of the series: min(n, capacity).  Either
+ * may be NULL; both 0 without regions. */
+int d3d_region_count(d3d_ctx *ctx, int64_t *n, int64_t *stored);
+/* series (stored, K, 3) = F | C | S, spec_mean and spec_m2 (K, D) (variance = M2 / (n - 1)), sizes
+ * (K) = members of every region.  Any may be NULL.  Spectra that were not begun: D3D_ERR_STATE. */
+int d3d_region_get(d3d_ctx *ctx, double *series, double *spec_mean, double *spec_m2, int32_t *sizes);
+/* Free them; the moments go on. */
+int d3d_region_end(d3d_ctx *ctx);
+
 /* ---- matched-filter line search ------------------------------------------ */
 /* The reference starts every spaxel from a uniform draw inside the bounds (lib/run.py:310-314) and
  * its only mask helper thresholds the spectrally summed flux (lib/masks.py:17-29).  This entry
