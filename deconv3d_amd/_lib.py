@@ -46,6 +46,7 @@ SYMBOLS = [
     "d3d_running_median", "d3d_channel_stats", "d3d_prepare",
     "d3d_temper_create", "d3d_temper_swap", "d3d_temper_get", "d3d_temper_last", "d3d_temper_destroy",
     "d3d_temper_set_patch", "d3d_temper_last_patches", "d3d_temper_get_patches",
+    "d3d_robust_begin", "d3d_robust_step", "d3d_robust_get", "d3d_robust_end",
 ]
 
 # posterior moments (a table, so that tools/posterior_time.py can load the PARENT commit's library,
@@ -116,6 +117,13 @@ TEMPER_PROTOTYPES = {
     "d3d_temper_last_patches": [C.c_void_p, C.POINTER(C.c_int32)] + [C.POINTER(C.c_double)] * 3
                                + [C.POINTER(C.c_int32)],
     "d3d_temper_get_patches": [C.c_void_p] + [C.POINTER(C.c_int64)] * 2,
+}
+# weights of a Student-t likelihood (a table for the same reason: tools/robust_time.py)
+ROBUST_PROTOTYPES = {
+    "d3d_robust_begin": [C.c_int, C.c_int, C.c_int64, C.c_int64],
+    "d3d_robust_step": [C.c_int64],
+    "d3d_robust_get": [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)],
+    "d3d_robust_end": [],
 }
 POST_CLEAN, POST_CONVOLVED = 1, 2                     # d3d_post_begin: bits of `what`
 POST_PARAMETERS, POST_CLEAN_CUBE, POST_CONVOLVED_CUBE = 0, 1, 2   # d3d_post_get: `which`
@@ -243,7 +251,7 @@ def load():
     for name, argtypes in (list(POST_PROTOTYPES.items()) + list(ADAPT_PROTOTYPES.items())
                            + list(SEARCH_PROTOTYPES.items()) + list(PREP_PROTOTYPES.items())
                            + list(PRIOR_PROTOTYPES.items()) + list(HIST_PROTOTYPES.items())
-                           + list(REGION_PROTOTYPES.items())):
+                           + list(REGION_PROTOTYPES.items()) + list(ROBUST_PROTOTYPES.items())):
         getattr(lib, name).argtypes = [ctx_p] + argtypes
     for name, argtypes in TEMPER_PROTOTYPES.items():
         getattr(lib, name).argtypes = argtypes
@@ -976,6 +984,33 @@ class Engine(object):
 
     def adapt_end(self):
         _check(self._lib.d3d_adapt_end(self._ctx))
+
+    # -- weights of a Student-t likelihood ------------------------------------------------
+    def robust_begin(self, nu, every=1, start=0, accumulate_from=0):
+        """Arm the per-voxel weights of a Student-t likelihood with ``nu`` degrees of freedom
+        (include/deconv3d_hip.h: d3d_robust_begin): after every sweep s >= ``start`` with
+        ``(s - start) % every == 0`` (the run's numbering) the device redraws them from the residual
+        and rewrites 1/variance; the draws of the sweeps from ``accumulate_from`` on enter their
+        running mean.  Needs set_data."""
+        _check(self._lib.d3d_robust_begin(self._ctx, int(nu), int(every), int(start), int(accumulate_from)))
+
+    def robust_step(self, sweep_number):
+        """One draw now, as the one after sweep ``sweep_number`` (the run's numbering)."""
+        _check(self._lib.d3d_robust_step(self._ctx, int(sweep_number)))
+
+    def robust_get(self, weights=True, weight_mean=True):
+        """(current weights (D,H,W), their running mean (D,H,W), accumulated draws); NaN where the
+        voxel carries no information, None for an array that was not asked for."""
+        w = np.empty(self.shape, dtype=np.float64) if weights else None
+        m = np.empty(self.shape, dtype=np.float64) if weight_mean else None
+        n = C.c_int64(0)
+        _check(self._lib.d3d_robust_get(self._ctx, _dp(w) if weights else None,
+                                        _dp(m) if weight_mean else None, C.byref(n)))
+        return w, m, n.value
+
+    def robust_end(self):
+        """Disarm: the base 1/variance back, bit for bit."""
+        _check(self._lib.d3d_robust_end(self._ctx))
 
     # -- smoothness prior between neighbouring spaxels ----------------------------------
     def prior_begin(self, lam):

@@ -535,6 +535,8 @@ int region_members(d3d_ctx *c) {
 
 }  // namespace
 
+int d3dh::download_device_cube(d3d_ctx *c, const double *src, double *host) { return download_cube(c, src, host); }
+
 int d3dh::post_sample(d3d_ctx *c) {
     NEED(c->post_on, D3D_ERR_STATE, "posterior moments not begun (d3d_post_begin)");
     NEED(!c->tiled, D3D_ERR_UNSUPPORTED,
@@ -812,6 +814,7 @@ int d3d_ctx_destroy(d3d_ctx *c) {
     hist_free(c);
     region_free(c);
     adapt_free(c);
+    robust_free(c);
     if (c->prior_part) (void)hipFree(c->prior_part);
     for (hipEvent_t e : c->halo_ev) (void)hipEventDestroy(e);
     for (int s = 0; s < D3D_SLOT_COUNT; ++s)
@@ -1173,6 +1176,7 @@ static int set_taps_impl(d3d_ctx *c, const double *fsf, const double *lsf, doubl
 int d3d_set_data(d3d_ctx *c, const double *data, const double *var, double var_scalar,
                  const uint8_t *mask) {
     NEED(c && data, D3D_ERR_INVALID, "NULL argument");
+    NEED(!c->rb_on, D3D_ERR_STATE, "robust weights are armed on the old variance: d3d_robust_end first");
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)c->D * c->HW;
     // mask: user mask AND no NaN anywhere in the spectrum (lib/run.py:153-162)
@@ -1358,6 +1362,8 @@ int d3d_convolve_slots(d3d_ctx *c, int src, int dst) {
     NEED(c->have_taps, D3D_ERR_STATE, "taps not set");
     NEED(dst != D3D_SLOT_TMP1 && src != D3D_SLOT_TMP1, D3D_ERR_INVALID,
          "SLOT_TMP1 is the convolution's intermediate");
+    NEED(dst != D3D_SLOT_IVAR || !c->rb_on, D3D_ERR_STATE,
+         "SLOT_IVAR is rewritten by the robust weights: d3d_robust_end first");
     HIP_TRY(hipSetDevice(c->device));
     if (src == D3D_SLOT_ERR)
         if (int rc = flush_pending(c)) return rc;
@@ -1377,6 +1383,8 @@ int d3d_convolve_slots(d3d_ctx *c, int src, int dst) {
 int d3d_upload_slot(d3d_ctx *c, int slot, const double *cube) {
     NEED(c && cube, D3D_ERR_INVALID, "NULL argument");
     NEED(slot >= 0 && slot < D3D_SLOT_COUNT, D3D_ERR_INVALID, "bad slot %d", slot);
+    NEED(slot != D3D_SLOT_IVAR || !c->rb_on, D3D_ERR_STATE,
+         "SLOT_IVAR is rewritten by the robust weights: d3d_robust_end first");
     HIP_TRY(hipSetDevice(c->device));
     int rc = upload_cube(c, cube, c->slot[slot]);
     if (rc) return rc;
@@ -2072,6 +2080,8 @@ int d3d_set_tile(d3d_ctx *c, int gy0, int gx0, int Wg, int oy0, int oy1, int ox0
          "per-spaxel jump scales are on (d3d_adapt_begin): not on a tile; call d3d_adapt_end first");
     NEED(!c->prior_on, D3D_ERR_UNSUPPORTED,
          "the smoothness prior is on (d3d_prior_begin): not on a tile; call d3d_prior_end first");
+    NEED(!c->rb_on, D3D_ERR_UNSUPPORTED,
+         "robust weights are armed (d3d_robust_begin): not on a tile; call d3d_robust_end first");
     c->gy0 = gy0;
     c->gx0 = gx0;
     c->Wg = Wg;

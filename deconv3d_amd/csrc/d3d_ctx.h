@@ -4,7 +4,8 @@
 // kernels; d3d_sweep.hip: the sweep driver; d3d_post.hip: posterior moments; d3d_region.hip: region
 // posteriors; d3d_search.hip: the
 // matched-filter line search; d3d_prep.hip: continuum removal and channel noise of a raw cube;
-// d3d_temper.hip: replica exchange between tempered chains).
+// d3d_temper.hip: replica exchange between tempered chains; d3d_robust.hip: the per-voxel weights of
+// a Student-t likelihood).
 // Not installed: the public interface is include/deconv3d_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -325,6 +326,17 @@ struct d3d_ctx {
     bool prior_on = false;
     double prior_lam[3] = {0.0, 0.0, 0.0};
     double *prior_part = nullptr;  // [PRIOR_BLOCKS + 1][4] block partials | totals of k_prior_energy
+    // Student-t likelihood (d3d_robust_*): after the due sweeps k_robust_step redraws one weight per
+    // voxel from the residual and writes SLOT_IVAR = weight * base 1/variance.  Nothing is allocated
+    // before d3d_robust_begin.
+    bool rb_on = false;
+    bool rb_was_uniform = false;   // ivar_is_uniform before arming (false while armed)
+    int rb_nu = 0, rb_every = 1;
+    int64_t rb_start = 0;          // due: s >= start and (s - start) % every == 0, the run's numbering
+    int64_t rb_accum_from = 0;     // draws of the sweeps from this one on enter the weight mean
+    int64_t rb_count = 0;          // draws in the weight mean
+    double *rb_i0 = nullptr;       // the base 1/variance d3d_set_data left in SLOT_IVAR, device layout
+    double *rb_mean = nullptr;     // running mean of the weights, device layout (0 where rb_i0 == 0)
     // d3d_line_search: device time of the last call's bank build (lines + transpose, or the transpose
     // of a host bank) and of its search kernel, by HIP events (read-only options search_bank_ns /
     // search_kernel_ns)
@@ -399,6 +411,13 @@ int post_sample(d3d_ctx *c);               // the chain state as one more sample
 bool post_due(const d3d_ctx *c, int s);    // sweep s (the caller's numbering) is one d3d_post_schedule asked for
 bool plan_has_entries(const d3d_ctx *c, int plan);
 int halo_exchange(d3d_ctx *c, int plan);
+// a cube in the device layout into a host array (D,H,W), synchronously (through c->stage)
+int download_device_cube(d3d_ctx *c, const double *src, double *host);
+
+// ---- d3d_robust.hip: the weights of a Student-t likelihood --------------------------------
+bool robust_due(const d3d_ctx *c, int s);   // sweep s (the caller's numbering) is followed by a draw
+int robust_after_sweep(d3d_ctx *c, int s);  // the pending layers written back, then the draw, where due
+void robust_free(d3d_ctx *c);               // the base cube back into SLOT_IVAR, the buffers freed
 
 // ---- d3d_sweep.hip: local colour residues of colour class `col` (a tile's origin shifts them)
 void colour_residue(const d3d_ctx *c, int col, int *cy, int *cx);

@@ -241,9 +241,10 @@ int end_sweep(d3d_ctx *c, int s, int keep_one_in, SnapQueue &snaps, double *chai
             NEED(c->comm, D3D_ERR_STATE, "parameter gather needs d3d_comm_init");
             if (int rc = halo_exchange(c, D3D_PLAN_PARAMS)) return rc;
         }
-        return forward_into(c, c->slot[D3D_SLOT_ERR], true);
+        if (int rc = forward_into(c, c->slot[D3D_SLOT_ERR], true)) return rc;
     }
-    return 0;
+    // d3d_robust_begin: the weights of a Student-t likelihood, redrawn from the refreshed residual
+    return robust_after_sweep(c, s);
 }
 
 // option halo_timing: the oldest event pair in flight, reduced into halo_ms / halo_count
@@ -318,7 +319,7 @@ int d3d_mh_sweeps(d3d_ctx *c, int n_sweeps, int first_sweep, int keep_one_in, do
             for (int t = s; t <= last; ++t) {
                 const bool saved = t % keep_one_in == 0 && (chain_out || dlog_out);
                 const bool refresh = c->refresh_every > 0 && t % c->refresh_every == 0;
-                if (saved || refresh || post_due(c, t)) {
+                if (saved || refresh || post_due(c, t) || robust_due(c, t)) {
                     last = t;
                     break;
                 }
@@ -426,6 +427,11 @@ int d3d_mh_sweeps_batch(d3d_ctx **ctxs, int n_ctx, int n_sweeps, int first_sweep
         NEED(c->refresh_every == L->refresh_every, D3D_ERR_INVALID,
              "ctx %d: refresh_every %d differs from ctx 0's %d (batched chains rebuild their residuals together)",
              r, c->refresh_every, L->refresh_every);
+        // (and written back at the same sweeps: d3d_robust_begin's draws flush the pending layers)
+        NEED(c->rb_on == L->rb_on && (!c->rb_on || (c->rb_every == L->rb_every && c->rb_start == L->rb_start)),
+             D3D_ERR_INVALID,
+             "ctx %d: robust weights (d3d_robust_begin) armed, every or start differ from ctx 0's (batched chains "
+             "write their pending residual updates back together)", r);
     }
     HIP_TRY(hipSetDevice(L->device));
     // saved sweeps (lib/run.py:353, 430-432, 449-451): every chain streams its samples as

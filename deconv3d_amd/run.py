@@ -39,7 +39,7 @@ import numpy as np
 
 from . import _lib, adapt as _adapt, ensemble, posterior as _posterior, prepare as _prepare, \
     regions as _regions, \
-    prior as _prior, search as _search, tempering as _tempering
+    prior as _prior, robust as _robust, search as _search, tempering as _tempering
 from .cube import Cube, read_fits
 from .host_model import HostModelChain
 from .instruments import Instrument
@@ -274,6 +274,28 @@ class Run:
     (d3d_temper_set_patch), so that a coarse ladder swaps where whole cubes never would.  The
     report then counts ``patch_attempts`` / ``patch_accepts`` / ``patch_rates`` per pair, its
     ``labels`` is ``None``, and ``resume_state=`` refuses a state written with another patch size.
+
+    ``robust=4`` (or ``dict(nu=4, every=1, start=0)``; default ``None``: off, nothing allocated or
+    launched, the chain is bit for bit what it is without the keyword) replaces the reference's
+    Gaussian error of known variance (lib/run.py:171-192, 407-426) by a Student-t error with ``nu``
+    degrees of freedom (an integer from 1 to 30), so that single voxels tens of sigma off -- cosmic
+    rays, sky-line residuals, bad columns -- stop pulling on every spaxel whose FSF window holds
+    them.  Every voxel carries a latent weight: after each sweep s >= ``start`` with
+    ``(s - start) % every == 0`` (the whole run's numbering) the device redraws the weights from
+    ``Gamma((nu + 1)/2, rate (nu + r^2 / variance)/2)``, r the voxel's residual, and the sweeps run
+    on ``variance / weight`` -- an exact Gibbs step (d3d_robust_*).  ``run.robust`` is a
+    :class:`deconv3d_amd.robust.RobustReport` (``nu``, ``every``, ``start``, ``count``,
+    ``weight_mean`` (D, H, W), ``weights``, ``downweighted(threshold)``, ``save(prefix)``); the mean
+    takes the draws from ``posterior_burn_in`` on when that is given, else from ``start``.  With
+    ``chains=R`` every chain draws its own, ``run.robusts[r]``, and ``run.robust`` pools the means by
+    count.  ``run.likelihoods``, ``d3d_chi2_map`` and the window probe of such a run are those of the
+    conditional Gaussian under the current weights.  ``initial_search=`` and ``prepare=`` run before
+    the weights are armed and see the given variance.  Refused with ``tempering=`` (a rung's
+    ``variance / beta`` is not a tempered Student-t); a host-evaluated line model raises
+    ``NotImplementedError``.  The checkpoint records ``nu``, ``every`` and ``start``;
+    ``resume_state=`` refuses a state written with others and re-makes the last due draw at or
+    before the checkpointed sweep from the restored state; the weight mean starts afresh.  Costs
+    two more cubes of device memory per chain.
     """
 
     def __init__(
@@ -311,12 +333,13 @@ class Run:
         smoothness=None,
         tempering=None,
         regions=None,
+        robust=None,
     ):
         prepare_cfg, search_cfg, posterior_burn_in, posterior_every, hist_cfg = self._check_keywords(
             prepare, initial_search, initial_parameters, resume_state, posterior_burn_in,
             posterior_every, posterior_histograms, adapt_sweeps, adapt_window, adapt_target,
             adapt_gain, adapt_scale_range, smoothness, tempering, keep_one_in, write_every,
-            max_iterations, chains, regions)
+            max_iterations, chains, regions, robust)
         self._read_inputs(cube, prepare_cfg, mask, variance, device)
         self._read_instrument(instrument)
         self._read_model(model, jump_amplitude, gibbs_apriori_variance, seed, posterior_burn_in)
@@ -339,7 +362,7 @@ class Run:
     def _check_keywords(self, prepare, initial_search, initial_parameters, resume_state,
                         posterior_burn_in, posterior_every, posterior_histograms, adapt_sweeps,
                         adapt_window, adapt_target, adapt_gain, adapt_scale_range, smoothness,
-                        tempering, keep_one_in, write_every, max_iterations, chains, regions):
+                        tempering, keep_one_in, write_every, max_iterations, chains, regions, robust=None):
         """The keywords' own checks.  Returns the checked ``prepare=`` and ``initial_search=``,
         the posterior schedule and the checked ``posterior_histograms=``."""
         # (before anything else: no device work yet)
@@ -362,6 +385,8 @@ class Run:
         self._adapt_cfg = adapt_cfg
         self.smoothness = _prior.check_keywords(smoothness)
         temper_cfg = self.tempering_cfg = _tempering.check_keywords(tempering)
+        self._robust_cfg = _robust.check_keywords(robust)
+        _robust.check_run(self._robust_cfg, temper_cfg)
         # lib/run.py:112-114
         assert keep_one_in > 0, "keep_one_in= MUST be a positive integer"
         assert write_every > 0, "write_every= MUST be a positive integer"
@@ -499,6 +524,9 @@ class Run:
             self._refuse_host_model("smoothness=", "the device knows the prior only for the "
                                     "(a, c, w) of the models it evaluates itself")
         _tempering.check_run(self.tempering_cfg, 1, self._host_model, type(self.model).__name__)
+        if self._robust_cfg is not None and self._host_model:
+            self._refuse_host_model("robust=", "the device redraws the weights only between the sweeps "
+                                    "it runs itself")
         if self._adapt_cfg is not None and self._host_model:
             self._refuse_host_model("adapt_sweeps=", "the device adapts jump scales only for the "
                                     "models it evaluates itself")
@@ -671,6 +699,12 @@ class Run:
                         eng.adapt_set(*resumed_adapt[r])
                 if self.smoothness is not None:
                     eng.prior_begin(_prior.lam_of(self.smoothness))
+                if self._robust_cfg is not None:
+                    # (the run's numbering; a resumed segment's mean starts with its own sweeps)
+                    cfg = self._robust_cfg
+                    first = cfg["start"] if posterior_burn_in is None else posterior_burn_in + self.sweep_origin
+                    eng.robust_begin(cfg["nu"], cfg["every"], cfg["start"],
+                                     max(first, self.sweep_origin + 1) if resumed else first)
         if resumed:
             for chain in self._host_chains if self._host_model else self.engines:
                 chain.set_sweep_origin(self.sweep_origin)
@@ -688,6 +722,12 @@ class Run:
         if not self._host_model:
             for eng in self.engines:
                 eng.residual(fetch=False)              # lib/run.py:317-334
+            # robust=, resumed: the weights the checkpointed run held were its last due draw
+            last = _robust.last_due(self._robust_cfg, self.sweep_origin) \
+                if resumed and self._robust_cfg is not None else None
+            if last is not None:
+                for eng in self.engines:
+                    eng.robust_step(last)
         # tempering=: the group that exchanges the rungs' states on the device.  The round of the
         # exchange after sweep s is (s + sweep_origin) // swap_every: a resumed run continues the
         # numbering, so no uniform is drawn twice.
@@ -827,6 +867,13 @@ class Run:
                 self.logger.warning("posterior_burn_in=%d: the run stopped at iteration %d, before "
                                     "the first accumulated sweep; run.posterior holds no sample"
                                     % (posterior_burn_in, self.iterations_done))
+        # robust=: the weights (still on the device: fetched on access)
+        self.robusts, self.robust = None, None
+        if self._robust_cfg is not None:
+            self.robusts = [_robust.RobustReport.from_engine(eng, self._robust_cfg, self.cube)
+                            for eng in self.engines]
+            self.robust = self.robusts[0] if len(self.robusts) == 1 else \
+                _robust.pooled(self.robusts, self.cube)
 
     # ------------------------------------------------------------------------
 
@@ -907,6 +954,7 @@ class Run:
                                             self.mask.shape)
         _prior.check_resume(state, files, self.smoothness)
         _tempering.check_resume(state, files, self.tempering_cfg)
+        _robust.check_resume(state, files, self._robust_cfg)
         _prepare.check_resume(state, files,
                               None if self.prepared is None else self.prepared.settings)
         # (a checkpoint without a line shape was written by a single-Gaussian run)
@@ -957,6 +1005,8 @@ class Run:
             state["prepare_settings"] = _prepare.settings_record(self.prepared.settings)
         if self.smoothness is not None:     # (resume_state= checks them)
             state["smoothness_sigmas"] = _prior.keyword_record(self.smoothness)
+        if self._robust_cfg is not None:    # (resume_state= checks them; the weights are redrawn)
+            state["robust_keywords"] = _robust.keyword_record(self._robust_cfg)
         if self.tempering_cfg is not None:  # (resume_state= checks them; counters and labels start afresh)
             state.update(_tempering.state_record(self.tempering_cfg))
         if self._adapt_cfg is not None:     # (resume_state= checks the keywords, restores the rest)

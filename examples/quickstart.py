@@ -86,6 +86,17 @@ for k, label in enumerate(rings.ids):
         rings.centre_mean[k], rings.centre_std[k], rings.width_mean[k], rings.width_std[k]))
 
 
+# ---- cosmic rays: robust=nu ------------------------------------------------------------------------
+# +50 sigma on one voxel in a thousand.  robust=4 gives every voxel a Student-t error: the device redraws
+# a weight per voxel between sweeps, and run.robust.weight_mean says which voxels the run stopped believing.
+hits = rng.random(clean.shape) < 1e-3
+hit_cube = inst.build_cube(cube.data + 50. * sigma * hits)
+r = Run(hit_cube, inst, variance=np.full(clean.shape, sigma ** 2), max_iterations=min(iterations, 500),
+        min_acceptance_rate=0., gibbs_apriori_variance=100., seed=1, robust=4)
+print("robust=4: %d of %d hit voxels have a mean weight below 0.5 (and %d of the %d others)" % (
+    r.robust.downweighted()[hits].sum(), hits.sum(), r.robust.downweighted()[~hits].sum(), (~hits).sum()))
+
+
 # ---- per-spaxel jump scales: adapt_sweeps=N ----------------------------------------------------
 # One jump amplitude for every spaxel is too wide for the bright ones and too narrow for the faint
 # ones.  adapt_sweeps=N adapts a scale per spaxel on the device during the first N sweeps and freezes

@@ -751,6 +751,56 @@ int d3d_export_updates(d3d_ctx *ctx, int n, const int *spaxels, double *out);
  * of this tile (they may lie outside it); err += f*G on the window's part inside. */
 int d3d_apply_updates(d3d_ctx *ctx, int n, const double *records);
 
+/* ---- Student-t likelihood: per-voxel noise weights ------------------------- */
+/* The reference's likelihood is Gaussian with a known variance (lib/run.py:171-192 sets it up,
+ * lib/run.py:407-426 is its chi2 over the window).  A Student-t error with nu degrees of freedom is
+ * that Gaussian with the variance of voxel v divided by a latent weight lambda_v ~ Gamma(nu/2, rate
+ * nu/2); given the residual r_v (SLOT_ERR) and the base 1/variance i0_v (what d3d_set_data left in
+ * SLOT_IVAR) the weights are independent,
+ *     lambda_v | r_v ~ Gamma(shape (nu + 1) / 2, rate (nu + r_v^2 i0_v) / 2),
+ * and given the weights the chain is the per-voxel-variance chain of lib/run.py:407-426 with
+ * SLOT_IVAR[v] = lambda_v i0_v.  These entries redraw the weights on the device between sweeps: an
+ * exact Gibbs step that leaves single voxels tens of sigma off (cosmic rays, sky-line residuals)
+ * without pull on the lines.  Off until begun: a ctx that never calls d3d_robust_begin allocates
+ * and launches nothing for them and runs the chain it always ran, bit for bit.
+ *
+ * The draw, in fp64 without contraction, m = (nu + 1) / 2 (integer division):
+ *     g      = -log(u_0 * u_1 * ... * u_{m-1})           (the product from the left)
+ *     g      = g + (-log(u_m)) * cos(6.283185307179586 * u_{m+1})^2     (nu even only)
+ *     lambda = (2 g) / (nu + (r r) i0)
+ * u_{2b}, u_{2b+1} are the two uniforms of Philox4x32-10 with the key of d3d_mh_config's seed and
+ * the counter (voxel, sweep number, b, 0x52425354), voxel = z H W + y W + x, the sweep number in
+ * the run's numbering (d3d_mh_set_sweep_origin): no rejection, nothing of the layout, the padding,
+ * the launch geometry or the options enters.  Where i0 == 0 (NaN voxels) SLOT_IVAR gets 0. */
+
+/* Arm: keep a copy of SLOT_IVAR as the base cube and a zeroed weight mean (two more cubes of
+ * device memory).  From then on d3d_mh_sweeps / d3d_mh_sweeps_batch redraw the weights after every
+ * sweep s (the run's numbering) with s >= start and (s - start) % every == 0 -- after the
+ * snapshot, the posterior sample, the adaptation step and the from-scratch residual of
+ * lib/run.py:521-534, with the pending residual updates written back first -- and a draw of a
+ * sweep s >= accumulate_from also enters the running mean of the weights.  Until the first draw
+ * SLOT_IVAR holds the base cube's bits; d3d_variance_is_uniform answers 0 while armed (the
+ * per-voxel kernels run; they are bit-identical to the uniform ones on a constant cube).
+ * d3d_chi2_map, the log ratios and d3d_window_stats are those of the conditional Gaussian
+ * under the current weights.  Calling it again starts afresh from the base cube.
+ * D3D_ERR_INVALID: nu outside 1..30, every < 1, a negative sweep.  D3D_ERR_STATE: no data.
+ * D3D_ERR_UNSUPPORTED: a tile ctx (d3d_set_tile), or D*H*W >= 2^32.  While armed d3d_set_data,
+ * d3d_set_tile and writes into SLOT_IVAR are refused. */
+int d3d_robust_begin(d3d_ctx *ctx, int nu, int every, int64_t start, int64_t accumulate_from);
+/* One draw now, as the one after sweep `sweep_number` (the run's numbering) would be, from the
+ * residual of the current parameters (lib/run.py:317-334; pending updates written back first):
+ * for tests, and for a resumed run, which re-makes the last due draw of the checkpointed run. */
+int d3d_robust_step(d3d_ctx *ctx, int64_t sweep_number);
+/* (D,H,W) arrays: the current weights SLOT_IVAR / base (1 before the first draw) and the running
+ * mean of the accumulated draws (0 before the first), NaN where the voxel carries no information
+ * (base 1/variance 0: lib/run.py:423-424's nansum skips it); *count the accumulated draws.  Any
+ * pointer may be NULL. */
+int d3d_robust_get(d3d_ctx *ctx, double *weights, double *weight_mean, int64_t *count);
+/* Disarm: the base cube goes back into SLOT_IVAR bit for bit, d3d_variance_is_uniform answers as
+ * before d3d_robust_begin, the two cubes are freed: the Gaussian chain of lib/run.py:171-192's
+ * variance again (d3d_ctx_destroy does it too). */
+int d3d_robust_end(d3d_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif
