@@ -183,7 +183,7 @@ int build_colour_lists(d3d_ctx *c) {
         }
     }
     std::vector<int4> list;
-    list.reserve(c->spx_cap);
+    list.reserve(c->spx.size());
     c->colour_real.assign(ncol, 0);
     for (d3d_ctx::Part &pt : c->parts) {
         pt.dy0 = std::max(pt.y0 - fhh, 0);
@@ -301,43 +301,21 @@ int build_colour_lists(d3d_ctx *c) {
                                                       ((col % c->fw - c->gx0) % c->fw + c->fw) % c->fw);
         }
         if (any) {
-            if (cols.size() > c->chain_cols_cap) {
-                if (c->chain_cols) (void)hipFree(c->chain_cols);
-                c->chain_cols = nullptr;
-                c->chain_cols_cap = 0;
-                HIP_TRY(hipMalloc(&c->chain_cols, cols.size() * sizeof(int2)));
-                c->chain_cols_cap = cols.size();
-            }
+            HIP_TRY(c->chain_cols.reserve(cols.size()));
             HIP_TRY(hipMemcpyAsync(c->chain_cols, cols.data(), cols.size() * sizeof(int2),
                                    hipMemcpyHostToDevice, c->stream));
-            if (need_slots > c->chain_slots_cap) {
-                if (c->chain_flags) (void)hipFree(c->chain_flags);
-                c->chain_flags = nullptr;
-                c->chain_slots_cap = 0;
-                HIP_TRY(hipMalloc(&c->chain_flags, 2 * need_slots * sizeof(unsigned)));
-                c->chain_slots_cap = need_slots;
+            if (2 * need_slots > c->chain_flags.size()) {
+                HIP_TRY(c->chain_flags.alloc(2 * need_slots));
                 HIP_TRY(hipMemsetAsync(c->chain_flags, 0, 2 * need_slots * sizeof(unsigned), c->stream));
                 c->chain_base = 0;
             }
-            if (need_G > c->chain_G_cap) {
-                if (c->chain_G) (void)hipFree(c->chain_G);
-                c->chain_G = nullptr;
-                c->chain_G_cap = 0;
-                HIP_TRY(hipMalloc(&c->chain_G, need_G * sizeof(double)));
-                c->chain_G_cap = need_G;
-            }
+            HIP_TRY(c->chain_G.reserve(need_G));
             HIP_TRY(hipStreamSynchronize(c->stream));  // `cols` goes out of scope
         }
     }
     c->mh_layers = 1;
     for (const d3d_ctx::Part &pt : c->parts) c->mh_layers = std::max(c->mh_layers, pt.layers);
-    if (list.size() > c->spx_cap) {
-        if (c->spx) (void)hipFree(c->spx);
-        c->spx = nullptr;
-        c->spx_cap = 0;
-        HIP_TRY(hipMalloc(&c->spx, list.size() * sizeof(int4)));
-        c->spx_cap = list.size();
-    }
+    HIP_TRY(c->spx.reserve(list.size()));
     // tables of the dataflow kernel (unpartitioned contexts only): active colours in
     // order, their ticket ranges, and per colour the map lattice point -> index in its list
     c->flow_K = 0;
@@ -395,55 +373,10 @@ int build_colour_lists(d3d_ctx *c) {
     return 0;
 }
 
-
-// ---- posterior moments (d3d_post_*) ------------------------------------------------------
-void hist_free(d3d_ctx *c) {
-    if (c->hist_bins) (void)hipFree(c->hist_bins);
-    if (c->hist_tails) (void)hipFree(c->hist_tails);
-    if (c->hist_range) (void)hipFree(c->hist_range);
-    c->hist_bins = c->hist_tails = nullptr;
-    c->hist_range = nullptr;
-    c->hist_on = c->hist_frozen = false;
-}
-
-void region_free(d3d_ctx *c) {
-    void *ptrs[] = {c->reg_member, c->reg_chunk, c->reg_first, c->reg_part, c->reg_fc, c->reg_series, c->reg_spart,
-                    c->reg_spec};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    c->reg_member = c->reg_first = nullptr;
-    c->reg_chunk = nullptr;
-    c->reg_part = c->reg_fc = c->reg_series = c->reg_spart = c->reg_spec = nullptr;
-    c->reg_on = false;
-    c->reg_K = c->reg_what = c->reg_nchunks = 0;
-    c->reg_cap = 0;
-    c->h_reg_labels.clear();
-    c->h_reg_sizes.clear();
-}
-
-void post_free(d3d_ctx *c) {
-    hist_free(c);
-    region_free(c);
-    for (double *&p : c->post_cube) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    if (c->post_map) (void)hipFree(c->post_map);
-    c->post_map = nullptr;
-    c->post_on = false;
-    c->post_what = 0;
-    c->post_n = 0;
-    c->post_every = 0;
-}
-
+// ---- per-spaxel jump scales (d3d_adapt_*) and the smoothness prior (d3d_prior_*) ----------
 void adapt_free(d3d_ctx *c) {
-    if (c->jscale) (void)hipFree(c->jscale);
-    if (c->jacc) (void)hipFree(c->jacc);
-    c->jscale = nullptr;
-    c->jacc = nullptr;
-    c->adapt_on = false;
-    c->adapt_n_win = c->adapt_k = 0;
-    c->props_sweep = -1;
+    c->adapt = {};
+    c->props_sweep = -1;  // (a table made with the scales)
 }
 
 // The kernels that make proposals from parameters they keep to themselves across sweeps
@@ -473,98 +406,9 @@ int prior_kernels_ok(const d3d_ctx *c) {
     return 0;
 }
 
-// count 0, accumulators zero (Welford's first sample starts from mean = M2 = 0)
-int post_reset(d3d_ctx *c) {
-    if (!c->post_on) return 0;
-    c->post_n = 0;
-    for (double *p : c->post_cube)
-        if (p) HIP_TRY(hipMemsetAsync(p, 0, c->cube_elems * sizeof(double), c->stream));
-    HIP_TRY(hipMemsetAsync(c->post_map, 0, (size_t)c->HW * 8 * sizeof(double), c->stream));
-    if (c->hist_on) {  // counters zero, ranges not frozen (all bits set: NaN)
-        const size_t nser = (size_t)c->HW * 4;
-        c->hist_frozen = false;
-        HIP_TRY(hipMemsetAsync(c->hist_bins, 0, nser * 64 * sizeof(uint32_t), c->stream));
-        HIP_TRY(hipMemsetAsync(c->hist_tails, 0, nser * 2 * sizeof(uint32_t), c->stream));
-        HIP_TRY(hipMemsetAsync(c->hist_range, 0xff, nser * 2 * sizeof(double), c->stream));
-    }
-    if (c->reg_on) {  // series and spectra zero; the count is the moments'
-        if (c->reg_series)
-            HIP_TRY(hipMemsetAsync(c->reg_series, 0, (size_t)c->reg_cap * c->reg_K * 3 * sizeof(double), c->stream));
-        if (c->reg_spec)
-            HIP_TRY(hipMemsetAsync(c->reg_spec, 0, (size_t)2 * c->reg_K * c->Dp * sizeof(double), c->stream));
-    }
-    return 0;
-}
-
-// The members of the regions under the mask in force, on the device (d3d_region_begin, and
-// d3d_set_data on a context with regions: its mask may have changed).  The tables that depend on
-// the number of chunks are allocated here; on failure the regions are freed.
-int region_members(d3d_ctx *c) {
-    std::vector<int> member, first;
-    std::vector<int4> chunk;
-    region_layout(c, member, chunk, first, c->h_reg_sizes);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    void *old[] = {c->reg_member, c->reg_chunk, c->reg_first, c->reg_part, c->reg_spart};
-    for (void *p : old)
-        if (p) (void)hipFree(p);
-    c->reg_member = c->reg_first = nullptr;
-    c->reg_chunk = nullptr;
-    c->reg_part = c->reg_spart = nullptr;
-    c->reg_nchunks = (int)chunk.size();
-    const size_t nm = std::max<size_t>(member.size(), 1), nc = std::max<size_t>(chunk.size(), 1);
-    hipError_t e = hipMalloc(&c->reg_member, nm * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&c->reg_chunk, nc * sizeof(int4));
-    if (e == hipSuccess) e = hipMalloc(&c->reg_first, first.size() * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&c->reg_part, nc * 4 * sizeof(double));
-    if (e == hipSuccess && (c->reg_what & 1)) e = hipMalloc(&c->reg_spart, nc * c->Dp * sizeof(double));
-    if (e == hipSuccess && !member.empty())
-        e = hipMemcpyAsync(c->reg_member, member.data(), member.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && !chunk.empty())
-        e = hipMemcpyAsync(c->reg_chunk, chunk.data(), chunk.size() * sizeof(int4), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(c->reg_first, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the host vectors go out of scope
-    if (e != hipSuccess) {
-        (void)hipGetLastError();  // the context stays usable for the chain and the moments
-        region_free(c);
-        return fail(D3D_ERR_HIP, "region posteriors (%zu members in %zu chunks): %s", member.size(), chunk.size(),
-                    hipGetErrorString(e));
-    }
-    return 0;
-}
-
 }  // namespace
 
 int d3dh::download_device_cube(d3d_ctx *c, const double *src, double *host) { return download_cube(c, src, host); }
-
-int d3dh::post_sample(d3d_ctx *c) {
-    NEED(c->post_on, D3D_ERR_STATE, "posterior moments not begun (d3d_post_begin)");
-    NEED(!c->tiled, D3D_ERR_UNSUPPORTED,
-         "posterior moments on a tile: the parameters of its frame belong to other ranks");
-    NEED(c->have_params, D3D_ERR_STATE, "parameters not set");
-    if (c->post_what & 2) {
-        NEED(c->have_taps, D3D_ERR_STATE, "taps not set");
-        if (int rc = forward_into(c, c->slot[D3D_SLOT_SIM], false)) return rc;
-    }
-    if (int rc = launch_post_accum(c)) return rc;
-    if (c->reg_on)  // d3d_region_begin: the same sample, the same number
-        if (int rc = launch_region_sample(c)) return rc;
-    ++c->post_n;
-    if (c->hist_on) {  // d3d_hist_begin: the pilot's last sample freezes the ranges, later ones are binned
-        if (c->post_n == c->hist_pilot) {
-            if (int rc = launch_hist_freeze(c)) return rc;
-            c->hist_frozen = true;
-        } else if (c->hist_frozen) {
-            if (int rc = launch_hist_accum(c)) return rc;
-        }
-    }
-    return 0;
-}
-
-bool d3dh::post_due(const d3d_ctx *c, int s) {
-    return c->post_on && c->post_every > 0 && s >= c->post_first &&
-           (s - c->post_first) % c->post_every == 0;
-}
 
 namespace {
 
@@ -726,38 +570,37 @@ int d3d_ctx_create(d3d_ctx **out, int device, int D, int H, int W, int fh, int f
     CTX_TRY(hipEventCreate(&c->ev0));
     CTX_TRY(hipEventCreate(&c->ev1));
     for (int s = 0; s < D3D_SLOT_COUNT; ++s) {
-        CTX_TRY(hipMalloc(&c->slot[s], c->cube_elems * sizeof(double)));
+        CTX_TRY(c->slot[s].alloc(c->cube_elems));
         CTX_TRY(hipMemsetAsync(c->slot[s], 0, c->cube_elems * sizeof(double), c->stream));
     }
-    CTX_TRY(hipMalloc(&c->stage, (size_t)D * c->HW * sizeof(double)));
-    CTX_TRY(hipMalloc(&c->stage2, (size_t)D * c->HW * sizeof(double)));
-    CTX_TRY(hipMalloc(&c->params, (size_t)c->HW * 3 * sizeof(double)));
-    CTX_TRY(hipMalloc(&c->params_alt, (size_t)c->HW * 3 * sizeof(double)));
-    CTX_TRY(hipMalloc(&c->mask, (size_t)c->HW));
-    CTX_TRY(hipMalloc(&c->fsf, (size_t)fh * fw * sizeof(double)));
-    CTX_TRY(hipMalloc(&c->sep_uv, (size_t)(fh + fw) * sizeof(double)));
-    CTX_TRY(hipMalloc(&c->fsf_quad, (size_t)fh * fw * sizeof(double)));
-    CTX_TRY(hipMalloc(&c->fsf_quad_sep, (size_t)fh * fw * sizeof(double)));
-    CTX_TRY(hipMalloc(&c->lsf_shift, (size_t)c->N * sizeof(int)));
-    CTX_TRY(hipMalloc(&c->lsf_weight, (size_t)c->N * sizeof(double)));
-    CTX_TRY(hipMalloc(&c->lsf_dense, (2 * d3d::LSF_RL + 1) * sizeof(double)));
-    CTX_TRY(hipMalloc(&c->dlog, (size_t)c->HW * sizeof(double)));
-    CTX_TRY(hipMalloc(&c->hwbuf, (size_t)c->HW * sizeof(double)));
-    CTX_TRY(hipMalloc(&c->scal, 16 * sizeof(double)));
-    CTX_TRY(hipMalloc(&c->accepted, sizeof(unsigned long long)));
-    CTX_TRY(hipMalloc(&c->acc_map, (size_t)c->HW * sizeof(unsigned)));
-    c->spx_cap = (size_t)(H + 2 * fh) * (W + 2 * fw);
-    CTX_TRY(hipMalloc(&c->spx, c->spx_cap * sizeof(int4)));
+    CTX_TRY(c->stage.alloc((size_t)D * c->HW));
+    CTX_TRY(c->stage2.alloc((size_t)D * c->HW));
+    CTX_TRY(c->params.alloc((size_t)c->HW * 3));
+    CTX_TRY(c->params_alt.alloc((size_t)c->HW * 3));
+    CTX_TRY(c->mask.alloc((size_t)c->HW));
+    CTX_TRY(c->fsf.alloc((size_t)fh * fw));
+    CTX_TRY(c->sep_uv.alloc((size_t)(fh + fw)));
+    CTX_TRY(c->fsf_quad.alloc((size_t)fh * fw));
+    CTX_TRY(c->fsf_quad_sep.alloc((size_t)fh * fw));
+    CTX_TRY(c->lsf_shift.alloc((size_t)c->N));
+    CTX_TRY(c->lsf_weight.alloc((size_t)c->N));
+    CTX_TRY(c->lsf_dense.alloc((2 * d3d::LSF_RL + 1)));
+    CTX_TRY(c->dlog.alloc((size_t)c->HW));
+    CTX_TRY(c->hwbuf.alloc((size_t)c->HW));
+    CTX_TRY(c->scal.alloc(16));
+    CTX_TRY(c->accepted.alloc(1));
+    CTX_TRY(c->acc_map.alloc((size_t)c->HW));
+    CTX_TRY(c->spx.alloc((size_t)(H + 2 * fh) * (W + 2 * fw)));
     c->slots_x = (W + fw - 1) / fw;
     c->slots = c->slots_x * ((H + fh - 1) / fh);
     c->Wg = W;
     c->oy1 = H;
     c->ox1 = W;
-    CTX_TRY(hipMalloc(&c->prev, (size_t)c->HW * 3 * sizeof(double)));
-    CTX_TRY(hipMalloc(&c->recbuf, (size_t)c->HW * 8 * sizeof(double)));
-    CTX_TRY(hipMalloc(&c->idxbuf, (size_t)c->HW * sizeof(int)));
+    CTX_TRY(c->prev.alloc((size_t)c->HW * 3));
+    CTX_TRY(c->recbuf.alloc((size_t)c->HW * 8));
+    CTX_TRY(c->idxbuf.alloc((size_t)c->HW));
     for (int b = 0; b < 4; ++b) {
-        CTX_TRY(hipMalloc(&c->gbuf[b], (size_t)c->slots * c->Dp * sizeof(double)));
+        CTX_TRY(c->gbuf[b].alloc((size_t)c->slots * c->Dp));
         CTX_TRY(hipMemsetAsync(c->gbuf[b], 0, (size_t)c->slots * c->Dp * sizeof(double), c->stream));
     }
     {
@@ -766,16 +609,16 @@ int d3d_ctx_create(d3d_ctx **out, int device, int D, int H, int W, int fh, int f
         c->flow_LY = H / fh + 3;
         c->flow_LX = W / fw + 3;
         c->flow_cap_K = ncol;
-        c->flow_cap_items = c->spx_cap;
-        CTX_TRY(hipMalloc(&c->flow_ent, c->spx_cap * sizeof(int4)));
-        CTX_TRY(hipMalloc(&c->flow_col, ncol * sizeof(int4)));
-        CTX_TRY(hipMalloc(&c->flow_lat, ncol * c->flow_LY * c->flow_LX * sizeof(int)));
-        c->flow_state_bytes = ((4 + ncol + c->spx_cap) * sizeof(unsigned) + 15) / 16 * 16;
-        CTX_TRY(hipMalloc(&c->flow_state, c->flow_state_bytes));
-        CTX_TRY(hipMalloc(&c->pair_state, (4 + c->spx_cap) * sizeof(unsigned)));
-        CTX_TRY(hipMemsetAsync(c->pair_state, 0, (4 + c->spx_cap) * sizeof(unsigned), c->stream));
+        c->flow_cap_items = c->spx.size();
+        CTX_TRY(c->flow_ent.alloc(c->spx.size()));
+        CTX_TRY(c->flow_col.alloc(ncol));
+        CTX_TRY(c->flow_lat.alloc(ncol * c->flow_LY * c->flow_LX));
+        c->flow_state_bytes = ((4 + ncol + c->spx.size()) * sizeof(unsigned) + 15) / 16 * 16;
+        CTX_TRY(c->flow_state.alloc(c->flow_state_bytes / sizeof(unsigned)));
+        CTX_TRY(c->pair_state.alloc((4 + c->spx.size())));
+        CTX_TRY(hipMemsetAsync(c->pair_state, 0, (4 + c->spx.size()) * sizeof(unsigned), c->stream));
 #endif
-        CTX_TRY(hipMalloc(&c->flow_err, 16));
+        CTX_TRY(c->flow_err.alloc(4));
         CTX_TRY(hipMemsetAsync(c->flow_err, 0, 16, c->stream));
         int cus = 0;
         CTX_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
@@ -800,40 +643,16 @@ int d3d_ctx_destroy(d3d_ctx *c) {
     if (c->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(c->comm);
     c->comm = nullptr;
     for (int b = 0; b < d3d_ctx::STREAM_NB; ++b) {
-        if (c->snap_dev[b]) (void)hipFree(c->snap_dev[b]);
         if (c->snap_host[b]) (void)hipHostFree(c->snap_host[b]);
         if (c->snap_ready[b]) (void)hipEventDestroy(c->snap_ready[b]);
         if (c->snap_done[b]) (void)hipEventDestroy(c->snap_done[b]);
     }
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    if (c->halo_send) (void)hipFree(c->halo_send);
-    if (c->halo_recv) (void)hipFree(c->halo_recv);
-    for (double *p : c->post_cube)
-        if (p) (void)hipFree(p);
-    if (c->post_map) (void)hipFree(c->post_map);
-    hist_free(c);
-    region_free(c);
-    adapt_free(c);
-    robust_free(c);
-    if (c->prior_part) (void)hipFree(c->prior_part);
     for (hipEvent_t e : c->halo_ev) (void)hipEventDestroy(e);
-    for (int s = 0; s < D3D_SLOT_COUNT; ++s)
-        if (c->slot[s]) (void)hipFree(c->slot[s]);
-    if (c->line.tab) (void)hipFree(const_cast<double *>(c->line.tab));
-    void *ptrs[] = {c->stage, c->stage2, c->params, c->params_alt, c->mask, c->fsf, c->lsf_shift, c->lsf_weight,
-                    c->dlog, c->hwbuf, c->scal, c->accepted, c->acc_map, c->spx, c->gbuf[0], c->gbuf[1], c->gbuf[2], c->gbuf[3],
-                    c->flow_ent, c->flow_col, c->flow_lat, c->flow_state, c->flow_err, c->pair_state, c->sep_uv,
-                    c->lsf_dense, c->prev, c->recbuf, c->idxbuf, c->extbuf, c->fsf_quad, c->fsf_quad_sep,
-                    c->chain_cols, c->chain_flags, c->chain_G, c->props, c->z_part, c->z_E, c->ltab, c->ptab};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-#ifdef D3D_EXPERIMENTS
-    if (c->stampbuf) (void)hipFree(c->stampbuf);
-#endif
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;  // every DevBuf of the context
     return D3D_OK;
 }
 
@@ -886,12 +705,12 @@ int d3d_ctx_set_option(d3d_ctx *c, const char *key, long value) {
     NEED(opt_value_ok(*o, value), D3D_ERR_INVALID, "option %s: value %ld out of range", key, value);
     if (c->*(o->field) == (int)value) return D3D_OK;
     HIP_TRY(hipSetDevice(c->device));
-    if (c->adapt_on && value != 0 &&
+    if (c->adapt.on && value != 0 &&
         (!strcmp(key, "mh_chain") || !strcmp(key, "mh_flow") || !strcmp(key, "mh_pair")))
         return fail(D3D_ERR_UNSUPPORTED,
                     "option %s with per-spaxel jump scales on (d3d_adapt_begin): the kernel keeps its "
                     "proposals' inputs across sweeps", key);
-    if (c->prior_on && value != 0 &&
+    if (c->prior.on && value != 0 &&
         (!strcmp(key, "mh_chain") || !strcmp(key, "mh_flow") || !strcmp(key, "mh_pair")))
         return fail(D3D_ERR_UNSUPPORTED,
                     "option %s with the smoothness prior on (d3d_prior_begin): the kernel decides more "
@@ -922,6 +741,10 @@ int d3d_ctx_get_option(d3d_ctx *c, const char *key, long *value) {
     }
     if (!strcmp(key, "prep_median_ns") || !strcmp(key, "prep_stats_ns")) {  // read-only: the last d3d_prepare etc.
         *value = key[5] == 'm' ? c->prep_median_ns : c->prep_stats_ns;
+        return D3D_OK;
+    }
+    if (!strcmp(key, "device_bytes")) {  // read-only: device memory the library holds, all contexts of the process
+        *value = (long)d3dh::dev_bytes.load();
         return D3D_OK;
     }
     // read-only, derived: what the context actually runs
@@ -1176,7 +999,7 @@ static int set_taps_impl(d3d_ctx *c, const double *fsf, const double *lsf, doubl
 int d3d_set_data(d3d_ctx *c, const double *data, const double *var, double var_scalar,
                  const uint8_t *mask) {
     NEED(c && data, D3D_ERR_INVALID, "NULL argument");
-    NEED(!c->rb_on, D3D_ERR_STATE, "robust weights are armed on the old variance: d3d_robust_end first");
+    NEED(!c->robust.on, D3D_ERR_STATE, "robust weights are armed on the old variance: d3d_robust_end first");
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)c->D * c->HW;
     // mask: user mask AND no NaN anywhere in the spectrum (lib/run.py:153-162)
@@ -1231,7 +1054,7 @@ int d3d_set_data(d3d_ctx *c, const double *data, const double *var, double var_s
     c->have_data = true;
     c->err_valid = false;
     pend_clear(c);
-    if (c->reg_on)  // the members of a region are its unmasked spaxels
+    if (c->reg.on)  // the members of a region are its unmasked spaxels
         if (int rc2 = region_members(c)) return rc2;
     return post_reset(c);  // moments over two data sets mean nothing
 }
@@ -1299,31 +1122,17 @@ int d3d_set_line_table(d3d_ctx *c, int n, double support, const double *table, d
     HIP_TRY(hipSetDevice(c->device));
     // the new table first (a failure keeps the old one), then as d3d_set_line_shape: the pending
     // updates were made with the old line
-    double *dev = nullptr;
+    DevBuf<double> dev;
     if (n != 0) {
         std::vector<double> padded((size_t)n + 2, 0.0);
         std::copy(table, table + n, padded.begin() + 1);
-        HIP_TRY(hipMalloc(&dev, padded.size() * sizeof(double)));
-        hipError_t e = hipMemcpy(dev, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(dev);
-            HIP_TRY(e);
-        }
+        HIP_TRY(dev.alloc(padded.size()));
+        HIP_TRY(hipMemcpy(dev, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    if (int rc = flush_pending(c)) {
-        if (dev) (void)hipFree(dev);
-        return rc;
-    }
-    if (c->line.tab) {
-        // (launches that read the old table may still be queued)
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) {
-            if (dev) (void)hipFree(dev);
-            HIP_TRY(e);
-        }
-        (void)hipFree(const_cast<double *>(c->line.tab));
-    }
-    c->line.tab = dev;
+    if (int rc = flush_pending(c)) return rc;
+    if (c->line_tab) HIP_TRY(hipStreamSynchronize(c->stream));  // (launches that read the old table may still be queued)
+    c->line_tab = std::move(dev);
+    c->line.tab = c->line_tab;
     c->line.n = n;
     c->line.support = n ? support : 0.0;
     c->line.inv_h = n ? (double)(n - 1) / (2.0 * support) : 0.0;
@@ -1362,7 +1171,7 @@ int d3d_convolve_slots(d3d_ctx *c, int src, int dst) {
     NEED(c->have_taps, D3D_ERR_STATE, "taps not set");
     NEED(dst != D3D_SLOT_TMP1 && src != D3D_SLOT_TMP1, D3D_ERR_INVALID,
          "SLOT_TMP1 is the convolution's intermediate");
-    NEED(dst != D3D_SLOT_IVAR || !c->rb_on, D3D_ERR_STATE,
+    NEED(dst != D3D_SLOT_IVAR || !c->robust.on, D3D_ERR_STATE,
          "SLOT_IVAR is rewritten by the robust weights: d3d_robust_end first");
     HIP_TRY(hipSetDevice(c->device));
     if (src == D3D_SLOT_ERR)
@@ -1383,7 +1192,7 @@ int d3d_convolve_slots(d3d_ctx *c, int src, int dst) {
 int d3d_upload_slot(d3d_ctx *c, int slot, const double *cube) {
     NEED(c && cube, D3D_ERR_INVALID, "NULL argument");
     NEED(slot >= 0 && slot < D3D_SLOT_COUNT, D3D_ERR_INVALID, "bad slot %d", slot);
-    NEED(slot != D3D_SLOT_IVAR || !c->rb_on, D3D_ERR_STATE,
+    NEED(slot != D3D_SLOT_IVAR || !c->robust.on, D3D_ERR_STATE,
          "SLOT_IVAR is rewritten by the robust weights: d3d_robust_end first");
     HIP_TRY(hipSetDevice(c->device));
     int rc = upload_cube(c, cube, c->slot[slot]);
@@ -1585,240 +1394,6 @@ int d3d_flush(d3d_ctx *c) {
     return flush_pending(c);
 }
 
-int d3d_post_begin(d3d_ctx *c, int what) {
-    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
-    NEED(what >= 0 && what <= 3, D3D_ERR_INVALID,
-         "what = %d: bit 0 the clean cube, bit 1 the convolved cube (0..3)", what);
-    NEED(!c->tiled, D3D_ERR_UNSUPPORTED,
-         "posterior moments on a tile: the parameters of its frame belong to other ranks");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    post_free(c);
-    hipError_t e = hipMalloc(&c->post_map, (size_t)c->HW * 8 * sizeof(double));
-    for (int k = 0; k < 4 && e == hipSuccess; ++k)
-        if (what & (1 << (k / 2))) e = hipMalloc(&c->post_cube[k], c->cube_elems * sizeof(double));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();  // the context stays usable for the chain
-        post_free(c);
-        return fail(D3D_ERR_HIP, "posterior accumulators (%d cubes of %zu bytes): %s",
-                    2 * ((what & 1) + (what >> 1)), c->cube_elems * sizeof(double), hipGetErrorString(e));
-    }
-    c->post_on = true;
-    c->post_what = what;
-    return post_reset(c);
-}
-
-int d3d_post_schedule(d3d_ctx *c, int first_sweep, int every) {
-    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
-    NEED(first_sweep >= 0, D3D_ERR_INVALID, "first_sweep = %d is negative", first_sweep);
-    NEED(every >= 1, D3D_ERR_INVALID, "every = %d: accumulate one sweep in how many (>= 1)", every);
-    NEED(c->post_on, D3D_ERR_STATE, "posterior moments not begun (d3d_post_begin)");
-    c->post_first = first_sweep;
-    c->post_every = every;
-    return D3D_OK;
-}
-
-int d3d_post_accumulate(d3d_ctx *c) {
-    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    return post_sample(c);
-}
-
-int d3d_post_count(d3d_ctx *c, int64_t *n) {
-    NEED(c && n, D3D_ERR_INVALID, "NULL argument");
-    *n = c->post_on ? c->post_n : 0;
-    return D3D_OK;
-}
-
-int d3d_post_get(d3d_ctx *c, int which, double *mean, double *m2) {
-    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
-    NEED(which >= 0 && which <= 2, D3D_ERR_INVALID,
-         "which = %d: 0 the parameter map, 1 the clean cube, 2 the convolved cube", which);
-    NEED(c->post_on, D3D_ERR_STATE, "posterior moments not begun (d3d_post_begin)");
-    NEED(which == 0 || (c->post_what & which), D3D_ERR_STATE,
-         "the %s cube's moments were not begun (d3d_post_begin what = %d)",
-         which == 1 ? "clean" : "convolved", c->post_what);
-    HIP_TRY(hipSetDevice(c->device));
-    if (which == 0) {
-        const size_t bytes = (size_t)c->HW * 4 * sizeof(double);
-        if (mean) HIP_TRY(hipMemcpyAsync(mean, c->post_map, bytes, hipMemcpyDeviceToHost, c->stream));
-        if (m2)
-            HIP_TRY(hipMemcpyAsync(m2, c->post_map + (size_t)c->HW * 4, bytes, hipMemcpyDeviceToHost,
-                                   c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return D3D_OK;
-    }
-    if (mean)
-        if (int rc = download_cube(c, c->post_cube[2 * (which - 1)], mean)) return rc;
-    if (m2)
-        if (int rc = download_cube(c, c->post_cube[2 * (which - 1) + 1], m2)) return rc;
-    return D3D_OK;
-}
-
-int d3d_post_end(d3d_ctx *c) {
-    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    post_free(c);
-    return D3D_OK;
-}
-
-int d3d_hist_begin(d3d_ctx *c, int64_t pilot, double span) {
-    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
-    NEED(pilot >= 2, D3D_ERR_INVALID, "pilot = %lld: the range needs a standard deviation (>= 2 samples)",
-         (long long)pilot);
-    NEED(std::isfinite(span) && span > 0.0, D3D_ERR_INVALID, "span = %g is not a positive number", span);
-    NEED(c->post_on, D3D_ERR_STATE, "posterior moments not begun (d3d_post_begin)");
-    NEED(c->have_cfg, D3D_ERR_STATE, "bounds not set (d3d_mh_config)");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    hist_free(c);
-    const size_t nser = (size_t)c->HW * 4;
-    hipError_t e = hipMalloc(&c->hist_bins, nser * 64 * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&c->hist_tails, nser * 2 * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&c->hist_range, nser * 2 * sizeof(double));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();  // the context stays usable for the chain and the moments
-        hist_free(c);
-        return fail(D3D_ERR_HIP, "posterior histograms (%zu bytes): %s", nser * (66 * sizeof(uint32_t) + 16),
-                    hipGetErrorString(e));
-    }
-    c->hist_on = true;
-    c->hist_pilot = pilot;
-    c->hist_span = span;
-    return post_reset(c);  // the pilot is the moments' first samples
-}
-
-int d3d_hist_count(d3d_ctx *c, int64_t *n) {
-    NEED(c && n, D3D_ERR_INVALID, "NULL argument");
-    *n = c->hist_on ? std::max<int64_t>(c->post_n - c->hist_pilot, 0) : 0;
-    return D3D_OK;
-}
-
-int d3d_hist_get(d3d_ctx *c, uint32_t *bins, uint32_t *tails, double *range) {
-    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
-    NEED(c->hist_on, D3D_ERR_STATE, "posterior histograms not begun (d3d_hist_begin)");
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t nser = (size_t)c->HW * 4;
-    if (bins)
-        HIP_TRY(hipMemcpyAsync(bins, c->hist_bins, nser * 64 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (tails)
-        HIP_TRY(hipMemcpyAsync(tails, c->hist_tails, nser * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (range)
-        HIP_TRY(hipMemcpyAsync(range, c->hist_range, nser * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return D3D_OK;
-}
-
-int d3d_hist_quantiles(d3d_ctx *c, int n_q, const double *q, double *quantiles, double *mode, double *outside) {
-    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
-    NEED(n_q >= 1 && n_q <= 8, D3D_ERR_INVALID, "n_q = %d: 1 to 8 quantiles a call", n_q);
-    NEED(q, D3D_ERR_INVALID, "q is NULL");
-    for (int j = 0; j < n_q; ++j)
-        NEED(q[j] > 0.0 && q[j] < 1.0, D3D_ERR_INVALID, "q[%d] = %g lies outside (0, 1)", j, q[j]);
-    NEED(c->hist_on, D3D_ERR_STATE, "posterior histograms not begun (d3d_hist_begin)");
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t nser = (size_t)c->HW * 4;
-    double *buf = nullptr;  // quantiles [nser][n_q] | mode [nser] | outside [nser]
-    HIP_TRY(hipMalloc(&buf, nser * (size_t)(n_q + 2) * sizeof(double)));
-    double *d_mode = buf + nser * (size_t)n_q, *d_out = d_mode + nser;
-    int rc = launch_hist_quantiles(c, n_q, q, quantiles ? buf : nullptr, mode ? d_mode : nullptr,
-                                   outside ? d_out : nullptr);
-    hipError_t e = hipSuccess;
-    if (!rc && quantiles)
-        e = hipMemcpyAsync(quantiles, buf, nser * (size_t)n_q * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (!rc && e == hipSuccess && mode)
-        e = hipMemcpyAsync(mode, d_mode, nser * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (!rc && e == hipSuccess && outside)
-        e = hipMemcpyAsync(outside, d_out, nser * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    (void)hipFree(buf);
-    if (rc) return rc;
-    HIP_TRY(e);
-    HIP_TRY(es);
-    return D3D_OK;
-}
-
-int d3d_hist_end(d3d_ctx *c) {
-    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    hist_free(c);
-    return D3D_OK;
-}
-
-int d3d_region_begin(d3d_ctx *c, const int32_t *labels, int K, int64_t capacity, int what) {
-    NEED(c && labels, D3D_ERR_INVALID, "NULL argument");
-    NEED(K >= 1, D3D_ERR_INVALID, "K = %d: at least one region", K);
-    NEED(capacity >= 0, D3D_ERR_INVALID, "capacity = %lld is negative", (long long)capacity);
-    NEED(what >= 0 && what <= 1, D3D_ERR_INVALID, "what = %d: bit 0 the spectra (0..1)", what);
-    for (long s = 0; s < c->HW; ++s)
-        NEED(labels[s] >= 0 && labels[s] <= K, D3D_ERR_INVALID, "labels[%ld] = %d lies outside 0 .. K = %d", s,
-             (int)labels[s], K);
-    NEED(!c->tiled, D3D_ERR_UNSUPPORTED,
-         "region posteriors on a tile: the parameters of its frame belong to other ranks");
-    NEED(c->post_on, D3D_ERR_STATE, "posterior moments not begun (d3d_post_begin)");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    region_free(c);
-    c->reg_K = K;
-    c->reg_what = what;
-    c->reg_cap = capacity;
-    c->h_reg_labels.assign(labels, labels + c->HW);
-    const size_t series_bytes = (size_t)capacity * K * 3 * sizeof(double);
-    const size_t spec_bytes = (what & 1) ? (size_t)2 * K * c->Dp * sizeof(double) : 0;
-    hipError_t e = hipMalloc(&c->reg_fc, (size_t)K * 2 * sizeof(double));
-    if (e == hipSuccess && series_bytes) e = hipMalloc(&c->reg_series, series_bytes);
-    if (e == hipSuccess && spec_bytes) e = hipMalloc(&c->reg_spec, spec_bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();  // the context stays usable for the chain and the moments
-        region_free(c);
-        return fail(D3D_ERR_HIP, "region posteriors (%zu bytes): %s", series_bytes + spec_bytes,
-                    hipGetErrorString(e));
-    }
-    if (int rc = region_members(c)) return rc;
-    c->reg_on = true;
-    return post_reset(c);  // the series' rows are the moments' samples
-}
-
-int d3d_region_count(d3d_ctx *c, int64_t *n, int64_t *stored) {
-    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
-    if (n) *n = c->reg_on ? c->post_n : 0;
-    if (stored) *stored = c->reg_on ? std::min<int64_t>(c->post_n, c->reg_cap) : 0;
-    return D3D_OK;
-}
-
-int d3d_region_get(d3d_ctx *c, double *series, double *spec_mean, double *spec_m2, int32_t *sizes) {
-    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
-    NEED(c->reg_on, D3D_ERR_STATE, "region posteriors not begun (d3d_region_begin)");
-    NEED(c->reg_spec || (!spec_mean && !spec_m2), D3D_ERR_STATE,
-         "the regions' spectra were not begun (d3d_region_begin what = %d)", c->reg_what);
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t stored = (size_t)std::min<int64_t>(c->post_n, c->reg_cap);
-    if (series && stored)
-        HIP_TRY(hipMemcpyAsync(series, c->reg_series, stored * c->reg_K * 3 * sizeof(double), hipMemcpyDeviceToHost,
-                               c->stream));
-    // (K, Dp) on the device, (K, D) for the caller: the pad channel of an odd depth stays behind
-    const size_t row = (size_t)c->D * sizeof(double), pitch = (size_t)c->Dp * sizeof(double);
-    if (spec_mean)
-        HIP_TRY(hipMemcpy2DAsync(spec_mean, row, c->reg_spec, pitch, row, (size_t)c->reg_K, hipMemcpyDeviceToHost,
-                                 c->stream));
-    if (spec_m2)
-        HIP_TRY(hipMemcpy2DAsync(spec_m2, row, c->reg_spec + (size_t)c->reg_K * c->Dp, pitch, row, (size_t)c->reg_K,
-                                 hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (sizes) std::copy(c->h_reg_sizes.begin(), c->h_reg_sizes.end(), sizes);
-    return D3D_OK;
-}
-
-int d3d_region_end(d3d_ctx *c) {
-    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    region_free(c);
-    return D3D_OK;
-}
-
 int d3d_line_search(d3d_ctx *c, int n_c, const double *centres, int n_w, const double *widths,
                     const double *host_bank, int32_t *best_out, double *stat_out) {
     NEED(c && centres && widths && best_out && stat_out, D3D_ERR_INVALID, "NULL argument");
@@ -1876,45 +1451,45 @@ int d3d_adapt_begin(d3d_ctx *c, double target, int window, int64_t last_sweep, d
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     adapt_free(c);
-    hipError_t e = hipMalloc(&c->jscale, (size_t)c->HW * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&c->jacc, (size_t)c->HW * sizeof(unsigned));
+    hipError_t e = c->adapt.jscale.alloc((size_t)c->HW);
+    if (e == hipSuccess) e = c->adapt.jacc.alloc((size_t)c->HW);
     if (e != hipSuccess) {
         (void)hipGetLastError();  // the context stays usable for the chain
         adapt_free(c);
         return fail(D3D_ERR_HIP, "jump scale map (%ld spaxels): %s", c->HW, hipGetErrorString(e));
     }
     std::vector<double> ones((size_t)c->HW, 1.0);
-    HIP_TRY(hipMemcpy(c->jscale, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(c->jacc, 0, (size_t)c->HW * sizeof(unsigned)));
-    c->adapt_target = target;
-    c->adapt_window = window;
-    c->adapt_last = last_sweep;
-    c->adapt_gain = gain;
-    c->adapt_min = scale_min;
-    c->adapt_max = scale_max;
-    c->adapt_n_win = c->adapt_k = 0;
-    c->adapt_on = true;
+    HIP_TRY(hipMemcpy(c->adapt.jscale, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(c->adapt.jacc, 0, (size_t)c->HW * sizeof(unsigned)));
+    c->adapt.target = target;
+    c->adapt.window = window;
+    c->adapt.last = last_sweep;
+    c->adapt.gain = gain;
+    c->adapt.min = scale_min;
+    c->adapt.max = scale_max;
+    c->adapt.n_win = c->adapt.k = 0;
+    c->adapt.on = true;
     c->props_sweep = -1;
     return D3D_OK;
 }
 
 int d3d_adapt_get(d3d_ctx *c, double *scale_hw, uint32_t *accepted_hw, int64_t *n_win, int64_t *k) {
     NEED(c, D3D_ERR_INVALID, "ctx is NULL");
-    NEED(c->adapt_on, D3D_ERR_STATE, "per-spaxel jump scales not begun (d3d_adapt_begin)");
+    NEED(c->adapt.on, D3D_ERR_STATE, "per-spaxel jump scales not begun (d3d_adapt_begin)");
     HIP_TRY(hipSetDevice(c->device));
     if (scale_hw)
-        HIP_TRY(hipMemcpyAsync(scale_hw, c->jscale, (size_t)c->HW * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(scale_hw, c->adapt.jscale, (size_t)c->HW * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (accepted_hw)
-        HIP_TRY(hipMemcpyAsync(accepted_hw, c->jacc, (size_t)c->HW * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(accepted_hw, c->adapt.jacc, (size_t)c->HW * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (n_win) *n_win = c->adapt_n_win;
-    if (k) *k = c->adapt_k;
+    if (n_win) *n_win = c->adapt.n_win;
+    if (k) *k = c->adapt.k;
     return D3D_OK;
 }
 
 int d3d_adapt_set(d3d_ctx *c, const double *scale_hw, const uint32_t *accepted_hw, int64_t n_win, int64_t k) {
     NEED(c, D3D_ERR_INVALID, "ctx is NULL");
-    NEED(c->adapt_on, D3D_ERR_STATE, "per-spaxel jump scales not begun (d3d_adapt_begin)");
+    NEED(c->adapt.on, D3D_ERR_STATE, "per-spaxel jump scales not begun (d3d_adapt_begin)");
     NEED(n_win >= 0 && k >= 0, D3D_ERR_INVALID, "n_win = %lld / k = %lld is negative", (long long)n_win, (long long)k);
     if (scale_hw)
         for (long i = 0; i < c->HW; ++i)
@@ -1922,11 +1497,11 @@ int d3d_adapt_set(d3d_ctx *c, const double *scale_hw, const uint32_t *accepted_h
                  "jump scale of spaxel (%ld, %ld) is %g: finite, positive numbers", i / c->W, i % c->W, scale_hw[i]);
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (scale_hw) HIP_TRY(hipMemcpy(c->jscale, scale_hw, (size_t)c->HW * sizeof(double), hipMemcpyHostToDevice));
+    if (scale_hw) HIP_TRY(hipMemcpy(c->adapt.jscale, scale_hw, (size_t)c->HW * sizeof(double), hipMemcpyHostToDevice));
     if (accepted_hw)
-        HIP_TRY(hipMemcpy(c->jacc, accepted_hw, (size_t)c->HW * sizeof(uint32_t), hipMemcpyHostToDevice));
-    c->adapt_n_win = n_win;
-    c->adapt_k = k;
+        HIP_TRY(hipMemcpy(c->adapt.jacc, accepted_hw, (size_t)c->HW * sizeof(uint32_t), hipMemcpyHostToDevice));
+    c->adapt.n_win = n_win;
+    c->adapt.k = k;
     c->props_sweep = -1;  // (a table made from the old scales)
     return D3D_OK;
 }
@@ -1949,16 +1524,16 @@ int d3d_prior_begin(d3d_ctx *c, const double lam[3]) {
     if (int rc = prior_kernels_ok(c)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int k = 0; k < 3; ++k) c->prior_lam[k] = lam[k];
-    c->prior_on = true;
+    for (int k = 0; k < 3; ++k) c->prior.lam[k] = lam[k];
+    c->prior.on = true;
     c->props_sweep = -1;
     return D3D_OK;
 }
 
 int d3d_prior_get(d3d_ctx *c, double lam[3], int *on) {
     NEED(c && lam && on, D3D_ERR_INVALID, "NULL argument");
-    for (int k = 0; k < 3; ++k) lam[k] = c->prior_on ? c->prior_lam[k] : 0.0;
-    *on = c->prior_on ? 1 : 0;
+    for (int k = 0; k < 3; ++k) lam[k] = c->prior.on ? c->prior.lam[k] : 0.0;
+    *on = c->prior.on ? 1 : 0;
     return D3D_OK;
 }
 
@@ -1966,8 +1541,8 @@ int d3d_prior_end(d3d_ctx *c) {
     NEED(c, D3D_ERR_INVALID, "ctx is NULL");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->prior_on = false;
-    c->prior_lam[0] = c->prior_lam[1] = c->prior_lam[2] = 0.0;
+    c->prior.on = false;
+    c->prior.lam[0] = c->prior.lam[1] = c->prior.lam[2] = 0.0;
     c->props_sweep = -1;
     return D3D_OK;
 }
@@ -1976,22 +1551,14 @@ int d3d_prior_energy(d3d_ctx *c, const double *params, double energy[3], int64_t
     NEED(c && energy && pairs, D3D_ERR_INVALID, "NULL argument");
     NEED(params || c->have_params, D3D_ERR_STATE, "parameters not set");
     HIP_TRY(hipSetDevice(c->device));
-    double *tmp = nullptr;
+    DevBuf<double> tmp;
     if (params) {
-        HIP_TRY(hipMalloc(&tmp, (size_t)c->HW * 3 * sizeof(double)));
-        hipError_t e = hipMemcpyAsync(tmp, params, (size_t)c->HW * 3 * sizeof(double), hipMemcpyHostToDevice,
-                                      c->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(tmp);
-            HIP_TRY(e);
-        }
+        HIP_TRY(tmp.alloc((size_t)c->HW * 3));
+        HIP_TRY(hipMemcpyAsync(tmp, params, (size_t)c->HW * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
     double out4[4] = {0.0, 0.0, 0.0, 0.0};
-    const int rc = d3dh::prior_energy(c, tmp ? tmp : c->params, out4);
-    if (tmp) {
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipFree(tmp);
-    }
+    const int rc = d3dh::prior_energy(c, params ? tmp.get() : c->params.get(), out4);
+    if (tmp) (void)hipStreamSynchronize(c->stream);
     if (rc) return rc;
     for (int k = 0; k < 3; ++k) energy[k] = out4[k];
     *pairs = (int64_t)out4[3];
@@ -2012,7 +1579,7 @@ int d3d_get_dlog(d3d_ctx *c, double *out_hw) {
 int d3d_x_stamps_arm(d3d_ctx *c, int launches) {
     NEED(c && launches > 0, D3D_ERR_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(c->device));
-    if (c->stampbuf) HIP_TRY(hipFree(c->stampbuf));
+    c->stampbuf.reset();
     NEED(c->have_data, D3D_ERR_STATE, "data not set");
     size_t most = 0;
     for (const d3d_ctx::Part &pt : c->parts)
@@ -2022,7 +1589,7 @@ int d3d_x_stamps_arm(d3d_ctx *c, int launches) {
     c->stamp_launches = (size_t)launches;
     c->stamp_next = 0;
     const size_t bytes = c->stamp_launches * c->stamp_stride * sizeof(unsigned long long);
-    HIP_TRY(hipMalloc((void **)&c->stampbuf, bytes));
+    HIP_TRY(c->stampbuf.alloc(c->stamp_launches * c->stamp_stride));
     HIP_TRY(hipMemset(c->stampbuf, 0, bytes));
     return D3D_OK;
 }
@@ -2076,11 +1643,11 @@ int d3d_set_tile(d3d_ctx *c, int gy0, int gx0, int Wg, int oy0, int oy1, int ox0
          c->W);
     NEED(0 <= oy0 && oy0 <= oy1 && oy1 <= c->H && 0 <= ox0 && ox0 <= ox1 && ox1 <= c->W,
          D3D_ERR_INVALID, "owned rectangle [%d,%d)x[%d,%d) outside the tile", oy0, oy1, ox0, ox1);
-    NEED(!c->adapt_on, D3D_ERR_UNSUPPORTED,
+    NEED(!c->adapt.on, D3D_ERR_UNSUPPORTED,
          "per-spaxel jump scales are on (d3d_adapt_begin): not on a tile; call d3d_adapt_end first");
-    NEED(!c->prior_on, D3D_ERR_UNSUPPORTED,
+    NEED(!c->prior.on, D3D_ERR_UNSUPPORTED,
          "the smoothness prior is on (d3d_prior_begin): not on a tile; call d3d_prior_end first");
-    NEED(!c->rb_on, D3D_ERR_UNSUPPORTED,
+    NEED(!c->robust.on, D3D_ERR_UNSUPPORTED,
          "robust weights are armed (d3d_robust_begin): not on a tile; call d3d_robust_end first");
     c->gy0 = gy0;
     c->gx0 = gx0;
@@ -2101,7 +1668,7 @@ int d3d_set_parts(d3d_ctx *c, int nparts, const int *rects, const int *phases) {
     NEED(c, D3D_ERR_INVALID, "ctx is NULL");
     NEED(nparts >= 0 && nparts <= 4096 && (nparts == 0 || (rects && phases)), D3D_ERR_INVALID,
          "bad part list");
-    NEED(!c->prior_on || nparts <= 1, D3D_ERR_UNSUPPORTED,
+    NEED(!c->prior.on || nparts <= 1, D3D_ERR_UNSUPPORTED,
          "the smoothness prior is on (d3d_prior_begin): not on a context cut into parts; call "
          "d3d_prior_end first");
     HIP_TRY(hipSetDevice(c->device));
@@ -2174,7 +1741,7 @@ int d3d_mh_colour_lines(d3d_ctx *c, int sweep, int n, const int *spaxels, const 
     NEED(n >= 0 && sweep >= 0, D3D_ERR_INVALID, "bad count / sweep");
     if (n == 0) return D3D_OK;
     NEED(spaxels && in3 && lines && out3, D3D_ERR_INVALID, "NULL argument");
-    NEED(!c->prior_on, D3D_ERR_UNSUPPORTED,
+    NEED(!c->prior.on, D3D_ERR_UNSUPPORTED,
          "the smoothness prior is on (d3d_prior_begin): a host-evaluated model's parameters are not the "
          "context's (a, c, w); call d3d_prior_end first");
     NEED(c->have_taps && c->have_data && c->have_cfg && c->err_valid, D3D_ERR_STATE,
@@ -2183,13 +1750,7 @@ int d3d_mh_colour_lines(d3d_ctx *c, int sweep, int n, const int *spaxels, const 
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = flush_pending(c)) return rc;
     const size_t per = 6 + 2 * (size_t)c->D;
-    if ((size_t)n > c->ext_cap) {
-        if (c->extbuf) (void)hipFree(c->extbuf);
-        c->extbuf = nullptr;
-        c->ext_cap = 0;
-        HIP_TRY(hipMalloc(&c->extbuf, (size_t)n * per * sizeof(double)));
-        c->ext_cap = (size_t)n;
-    }
+    HIP_TRY(c->extbuf.reserve((size_t)n * per));
     double *d_in = c->extbuf;                      // [n*3]
     double *d_out = d_in + (size_t)n * 3;          // [n*3]
     double *d_lines = d_out + (size_t)n * 3;       // [n*2*D]
@@ -2366,26 +1927,15 @@ int d3d_halo_plan(d3d_ctx *c, int plan, int n, const int *entries) {
     HIP_TRY(hipStreamSynchronize(c->stream));  // nobody may still use the old buffers
     // Grow the buffers FIRST; the plan goes live only when both exist, so that a failed
     // allocation leaves the old plan and the old buffers as they were.
-    double *ns = nullptr, *nr = nullptr;
-    if (so > c->halo_send_cap) HIP_TRY(hipMalloc(&ns, so * sizeof(double)));
-    if (ro > c->halo_recv_cap) {
-        const hipError_t e = hipMalloc(&nr, ro * sizeof(double));
-        if (e != hipSuccess) {
-            if (ns) (void)hipFree(ns);
-            return fail(D3D_ERR_HIP, "hipMalloc of the halo receive buffer failed: %s",
-                        hipGetErrorString(e));
-        }
+    DevBuf<double> ns, nr;
+    if (so > c->halo_send.size()) HIP_TRY(ns.alloc(so));
+    if (ro > c->halo_recv.size()) {
+        const hipError_t e = nr.alloc(ro);
+        if (e != hipSuccess)
+            return fail(D3D_ERR_HIP, "hipMalloc of the halo receive buffer failed: %s", hipGetErrorString(e));
     }
-    if (ns) {
-        if (c->halo_send) (void)hipFree(c->halo_send);
-        c->halo_send = ns;
-        c->halo_send_cap = so;
-    }
-    if (nr) {
-        if (c->halo_recv) (void)hipFree(c->halo_recv);
-        c->halo_recv = nr;
-        c->halo_recv_cap = ro;
-    }
+    if (ns) c->halo_send = std::move(ns);
+    if (nr) c->halo_recv = std::move(nr);
     if ((int)c->plans.size() <= plan) c->plans.resize(plan + 1);
     c->plans[plan] = v;
     return D3D_OK;
@@ -2520,18 +2070,11 @@ int d3d_rtnorm(d3d_ctx *c, long n, double lo, double hi, double mu, double sigma
     NEED(sigma > 0.0, D3D_ERR_INVALID, "sigma must be positive");
     if (n == 0) return D3D_OK;
     HIP_TRY(hipSetDevice(c->device));
-    double *buf = nullptr;
-    HIP_TRY(hipMalloc(&buf, (size_t)n * sizeof(double)));
-    if (int rc = launch_rtnorm(c, n, lo, hi, mu, sigma, seed, wave_mode, buf)) {
-        (void)hipFree(buf);
-        return rc;
-    }
-    hipError_t e = hipSuccess;
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(out, buf, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(buf);
-    HIP_TRY(e);
+    DevBuf<double> buf;
+    HIP_TRY(buf.alloc((size_t)n));
+    if (int rc = launch_rtnorm(c, n, lo, hi, mu, sigma, seed, wave_mode, buf)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, buf, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return D3D_OK;
 }
 
@@ -2543,9 +2086,9 @@ int d3d_philox(d3d_ctx *c, long n, const uint32_t *counters, const uint32_t *key
     HIP_TRY(hipSetDevice(c->device));
     // one allocation: pairs [2n] doubles | counters [4n] | keys [2n] | words [4n]
     const size_t nn = (size_t)n;
-    char *buf = nullptr;
-    HIP_TRY(hipMalloc(&buf, nn * (2 * sizeof(double) + 10 * sizeof(uint32_t))));
-    double *d_pairs = reinterpret_cast<double *>(buf);
+    DevBuf<char> buf;
+    HIP_TRY(buf.alloc(nn * (2 * sizeof(double) + 10 * sizeof(uint32_t))));
+    double *d_pairs = reinterpret_cast<double *>(buf.get());
     uint32_t *d_counters = reinterpret_cast<uint32_t *>(buf + nn * 2 * sizeof(double));
     uint32_t *d_keys = d_counters + 4 * nn;
     uint32_t *d_words = d_keys + 2 * nn;
@@ -2555,19 +2098,16 @@ int d3d_philox(d3d_ctx *c, long n, const uint32_t *counters, const uint32_t *key
         e = hipMemcpyAsync(d_keys, keys, nn * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(c->stream);
-        (void)hipFree(buf);
         HIP_TRY(e);
     }
     if (int rc = launch_philox(c, n, d_counters, d_keys, d_words, d_pairs)) {
         (void)hipStreamSynchronize(c->stream);
-        (void)hipFree(buf);
         return rc;
     }
     e = hipMemcpyAsync(out_words, d_words, nn * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess)
         e = hipMemcpyAsync(out_pairs, d_pairs, nn * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     const hipError_t es = hipStreamSynchronize(c->stream);
-    (void)hipFree(buf);
     HIP_TRY(e);
     HIP_TRY(es);
     return D3D_OK;

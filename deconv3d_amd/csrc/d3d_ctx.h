@@ -1,17 +1,21 @@
 // Internal header of libdeconv3d_hip.so: the context struct and the launch
 // functions shared by the library's translation units (d3d_api.hip: C ABI and host
 // logic; d3d_spatial.hip: line / LSF / FSF kernels; d3d_mh.hip: the MH-within-Gibbs
-// kernels; d3d_sweep.hip: the sweep driver; d3d_post.hip: posterior moments; d3d_region.hip: region
-// posteriors; d3d_search.hip: the
-// matched-filter line search; d3d_prep.hip: continuum removal and channel noise of a raw cube;
-// d3d_temper.hip: replica exchange between tempered chains; d3d_robust.hip: the per-voxel weights of
-// a Student-t likelihood).
+// kernels; d3d_sweep.hip: the sweep driver; d3d_post.hip: posterior moments and histograms;
+// d3d_region.hip: region posteriors; d3d_search.hip: the matched-filter line search; d3d_prep.hip:
+// continuum removal and channel noise of a raw cube; d3d_temper.hip: replica exchange between
+// tempered chains; d3d_robust.hip: the per-voxel weights of a Student-t likelihood).
+// Ownership: every device allocation is a DevBuf, freed by whoever holds it -- the context or group
+// it is a member of (their `delete`), or the call it is a local of.  An optional feature's state is
+// one sub-struct of the context, and its *_end is `c->feature = {}`: buffers freed, fields back at
+// their defaults.  A DevBuf never synchronises: whoever frees one has drained the stream that uses it.
 // Not installed: the public interface is include/deconv3d_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: the library is dlopen()ed by d3d_comm_init
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -19,6 +23,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/deconv3d_hip.h"
@@ -55,6 +60,50 @@ int fail(int code, const char *fmt, ...);
         if (!(cond)) return d3dh::fail(code, __VA_ARGS__); \
     } while (0)
 
+namespace d3dh {
+// bytes of device memory the DevBufs of this process hold (read-only option device_bytes)
+inline std::atomic<size_t> dev_bytes{0};
+}
+
+// One device allocation of n elements, owned (move-only).  No contents survive alloc / reserve.
+template <typename T>
+class DevBuf {
+    T *p_ = nullptr;
+    size_t n_ = 0;
+
+   public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p_(std::exchange(o.p_, nullptr)), n_(std::exchange(o.n_, 0)) {}
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        std::swap(p_, o.p_);
+        std::swap(n_, o.n_);
+        o.reset();
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    hipError_t alloc(size_t n) {  // on failure it holds nothing
+        reset();
+        const hipError_t e = hipMalloc(&p_, n * sizeof(T));
+        if (e != hipSuccess) {
+            p_ = nullptr;
+            return e;
+        }
+        n_ = n;
+        d3dh::dev_bytes += n * sizeof(T);
+        return e;
+    }
+    hipError_t reserve(size_t n) { return n <= n_ ? hipSuccess : alloc(n); }  // grow-only
+    void reset() {
+        if (p_) (void)hipFree(p_);
+        d3dh::dev_bytes -= n_ * sizeof(T);
+        p_ = nullptr;
+        n_ = 0;
+    }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+    size_t size() const { return n_; }
+};
+
 struct d3d_ctx {
     int device = 0;
     int D = 0, H = 0, W = 0, fh = 0, fw = 0;
@@ -65,24 +114,23 @@ struct d3d_ctx {
     hipStream_t own_stream = nullptr, stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 
-    double *slot[D3D_SLOT_COUNT] = {};
-    double *stage = nullptr;   // D*HW doubles, host-layout staging
-    double *stage2 = nullptr;  // second staging (variance)
-    double *params = nullptr;  // HW*3
-    double *params_alt = nullptr;  // HW*3: parameter map of d3d_simulate (not the chain state)
-    uint8_t *mask = nullptr;   // HW
-    double *fsf = nullptr;     // fh*fw
-    int *lsf_shift = nullptr;
-    double *lsf_weight = nullptr;
+    DevBuf<double> slot[D3D_SLOT_COUNT];
+    DevBuf<double> stage;   // D*HW doubles, host-layout staging
+    DevBuf<double> stage2;  // second staging (variance)
+    DevBuf<double> params;  // HW*3
+    DevBuf<double> params_alt;  // HW*3: parameter map of d3d_simulate (not the chain state)
+    DevBuf<uint8_t> mask;   // HW
+    DevBuf<double> fsf;     // fh*fw
+    DevBuf<int> lsf_shift;
+    DevBuf<double> lsf_weight;
     int ntaps = 0;
-    double *dlog = nullptr;  // HW
-    double *hwbuf = nullptr; // HW scratch (chi2 map)
-    double *scal = nullptr;  // small device scalars (8 doubles)
-    unsigned long long *accepted = nullptr;
-    unsigned *acc_map = nullptr;  // [HW] accepted moves per spaxel since the last accepted_collect (MHArgs::acc_map)
-    int4 *spx = nullptr;  // work lists per (part, colour): real spaxels first, then virtual ones
+    DevBuf<double> dlog;  // HW
+    DevBuf<double> hwbuf; // HW scratch (chi2 map)
+    DevBuf<double> scal;  // small device scalars (8 doubles)
+    DevBuf<unsigned long long> accepted;
+    DevBuf<unsigned> acc_map;  // [HW] accepted moves per spaxel since the last accepted_collect (MHArgs::acc_map)
+    DevBuf<int4> spx;  // work lists per (part, colour): real spaxels first, then virtual ones
     std::vector<int> colour_real;  // fh*fw: number of real spaxels of each colour (all parts)
-    size_t spx_cap = 0;
     // A PART is a rectangle of spaxels updated together: sweep = for every phase, for
     // every part of the phase, for every colour class, one launch (lib/run.py:553-560
     // declares the scan order overridable).  An unpartitioned context has one part,
@@ -115,8 +163,7 @@ struct d3d_ctx {
         size_t send_off = 0, send_n = 0, recv_off = 0, recv_n = 0;  // in doubles
     };
     std::vector<std::vector<HaloEntry>> plans;
-    double *halo_send = nullptr, *halo_recv = nullptr;
-    size_t halo_send_cap = 0, halo_recv_cap = 0;
+    DevBuf<double> halo_send, halo_recv;
     // asynchronous chain streaming (lib/run.py:447-451 chain[i] = parameters, :428-432):
     // at a saved sweep the compute stream snapshots parameters + log ratios device to
     // device (microseconds), a COPY stream moves the snapshot to a pinned host buffer,
@@ -124,7 +171,7 @@ struct d3d_ctx {
     // runs on -- STREAM_NB snapshots may be in flight
     static constexpr int STREAM_NB = 4;
     hipStream_t copy_stream = nullptr;
-    double *snap_dev[STREAM_NB] = {};   // [HW*4]: params (HW*3) | dlog (HW)
+    DevBuf<double> snap_dev[STREAM_NB]; // [HW*4]: params (HW*3) | dlog (HW)
     double *snap_host[STREAM_NB] = {};  // pinned
     hipEvent_t snap_ready[STREAM_NB] = {}, snap_done[STREAM_NB] = {};
     // RCCL communicator of the tiled chain (d3d_comm_init)
@@ -141,8 +188,9 @@ struct d3d_ctx {
     std::vector<uint8_t> h_user_mask;  // the caller's mask alone, without the NaN rule (d3d_line_search)
 
     d3d::LineShape line = {1, {0.0, 0.0, 0.0, 0.0}, {1.0, 0.0, 0.0, 0.0}, nullptr, 0, 0.0, 0.0};  // d3d_set_line_shape
-    // d3d_set_line_table: line.tab is the device copy (n + 2 doubles, owned), h_line_tab the n
-    // samples on the host (d3d_mh_sweeps_batch compares them), line_tab_flux the integral of phi
+    // d3d_set_line_table: line_tab owns the device copy (n + 2 doubles) that line.tab points to, h_line_tab
+    // holds the n samples on the host (d3d_mh_sweeps_batch compares them), line_tab_flux the integral of phi
+    DevBuf<double> line_tab;
     std::vector<double> h_line_tab;
     double line_tab_flux = 0.0;
     bool have_taps = false, have_data = false, have_params = false, have_cfg = false;
@@ -160,17 +208,16 @@ struct d3d_ctx {
     int mh_defer_opt = 1;         // option mh_defer
     int mh_zblocks = 1;           // option mh_zblocks = 0: cubes deeper than 512 channels keep k_mh_defer / k_mh_deep
     bool mh_zb = false;           // the z-blocked kernels run (k_mh_ws<..., ZBK> + k_mh_zdecide)
-    double *z_part = nullptr;     // [items of a launch][blocks][4 waves][8] wave sums
-    double *z_E = nullptr;        // [2][slots][Dp] lines of the updates of the last colour class
-    size_t z_part_cap = 0;        // doubles allocated
+    DevBuf<double> z_part;        // [items of a launch][blocks][4 waves][8] wave sums
+    DevBuf<double> z_E;           // [2][slots][Dp] lines of the updates of the last colour class
 #ifdef D3D_EXPERIMENTS
-    unsigned long long *stampbuf = nullptr;  // D3D_MH_STAMP=1: [launch][workgroup][8]
+    DevBuf<unsigned long long> stampbuf; // D3D_MH_STAMP=1: [launch][workgroup][8]
     size_t stamp_launches = 0, stamp_next = 0, stamp_stride = 0;
 #endif
     bool ivar_is_uniform = false; // SLOT_IVAR holds one constant (k_mh_ws<.., true> skips reading it)
     double ivar_uniform = 0.0;
     int uniform_fast_path = 1;    // option uniform_ivar = 0 turns the variant off
-    double *gbuf[4] = {nullptr, nullptr, nullptr, nullptr};  // update coefficients [slots][Dp]
+    DevBuf<double> gbuf[4];  // update coefficients [slots][Dp]
     // pending layers, oldest first: colour class and G buffer of each update that has
     // not been written into SLOT_ERR yet (k_mh_ws applies up to mh_layers of them)
     int lay_n = 0, lay_cy[3] = {-1, -1, -1}, lay_cx[3] = {-1, -1, -1}, lay_g[3] = {0, 0, 0};
@@ -192,57 +239,53 @@ struct d3d_ctx {
     int mh_chain_opt = 0;          // option mh_chain (EXPERIMENTS builds): 1 = k_mh_chain wherever a part's
                                    // slots are all resident; measured no faster than the colour launches
                                    // (profiles/r03_chain_phases.txt)
-    int2 *chain_cols = nullptr;    // [parts][fh*fw] local residues of each part's active colours
-    size_t chain_cols_cap = 0;
-    unsigned *chain_flags = nullptr;  // [2][chain_slots_cap]: flag1 | flag2 (monotonic epochs)
-    size_t chain_slots_cap = 0;
-    double *chain_G = nullptr;     // [2][K][slots][Dp] G rows | [slots][K][2][Dp] unit lines of a sweep
-    size_t chain_G_cap = 0;
+    DevBuf<int2> chain_cols;       // [parts][fh*fw] local residues of each part's active colours
+    DevBuf<unsigned> chain_flags;  // [2][size() / 2]: flag1 | flag2 (monotonic epochs)
+    DevBuf<double> chain_G;        // [2][K][slots][Dp] G rows | [slots][K][2][Dp] unit lines of a sweep
     unsigned chain_base = 0;       // the epoch every flag of a finished launch holds
     bool chain_used = false;       // a chain launch ran since the error word was last read
     int mh_props = 1;              // option mh_props: the proposals of a sweep in one launch before its colours
-    d3d::MHProposal *props = nullptr;  // [HW]
+    DevBuf<d3d::MHProposal> props; // [HW]
     long props_sweep = -1;         // the sweep (Philox number) the table holds, -1 = none
     int mh_prio = 0;               // option mh_prio: staggered completion by wave priority (MHArgs::prio)
     int mh_small = 1;              // option mh_small = 0: small colour launches keep round 3's k_mh_ws variants instead of k_mh_small
-    double *ptab = nullptr;        // [(fh fw + 1)][fh fw][4] relative position tables of k_mh_small (ensure_proposals)
+    DevBuf<double> ptab;           // [(fh fw + 1)][fh fw][4] relative position tables of k_mh_small (ensure_proposals)
     bool ptab_valid = false;       // (d3d_set_taps invalidates them)
-    double *ltab = nullptr;        // [HW][2][Dp] line table of the current sweep (k_mh_line_table), allocated on first use
+    DevBuf<double> ltab;           // [HW][2][Dp] line table of the current sweep (k_mh_line_table), allocated on first use
     int mh_wide = 1;               // option mh_wide = 0: never the wide form for the small launches of a partitioned context
     int mh_pair = 0;               // D3D_MH_PAIR=1: two colour classes per launch (k_mh_pair;
                                    // measured 43.0 vs 42.0 us per colour: opt-in)
-    unsigned *pair_state = nullptr;  // [0] ticket counter | [4 ..] done flags per item
+    DevBuf<unsigned> pair_state; // [0] ticket counter | [4 ..] done flags per item
     unsigned pair_epoch = 0, pair_tickets = 0;
     std::vector<int> flow_first;   // first item of every active colour (+ total)
     std::vector<int> flow_colour;  // colour class index of every active colour
-    int4 *flow_ent = nullptr;     // [items] {y, x, real, colour ordinal}
-    int4 *flow_col = nullptr;     // [K] {first ticket, cy, cx, -}
-    int *flow_lat = nullptr;      // [K][LY*LX]
-    unsigned *flow_state = nullptr;  // one block, zeroed per launch: ctl[4] | cnt[K] | done[items]
-    unsigned *flow_err = nullptr;    // sticky error word of k_mh_flow
+    DevBuf<int4> flow_ent;        // [items] {y, x, real, colour ordinal}
+    DevBuf<int4> flow_col;        // [K] {first ticket, cy, cx, -}
+    DevBuf<int> flow_lat;         // [K][LY*LX]
+    DevBuf<unsigned> flow_state; // one block, zeroed per launch: ctl[4] | cnt[K] | done[items]
+    DevBuf<unsigned> flow_err;   // sticky error word of k_mh_flow
     size_t flow_state_bytes = 0, flow_cap_items = 0, flow_cap_K = 0;
     int slots_x = 0, slots = 0;
     int gy0 = 0, gx0 = 0, Wg = 0;    // tile origin / global width (RNG keys)
     bool tiled = false;              // d3d_set_tile was called
     int oy0 = 0, oy1 = 0, ox0 = 0, ox1 = 0;  // owned local rectangle
-    double *prev = nullptr;          // [HW*3] parameters before each spaxel's last update
-    double *recbuf = nullptr;        // [HW*8] staging of update records
-    int *idxbuf = nullptr;           // [HW] staging of spaxel lists
-    double *extbuf = nullptr;        // external-lines staging: [cap][6 + 2D] doubles
-    size_t ext_cap = 0;              // spaxels per d3d_mh_colour_lines call it can hold
+    DevBuf<double> prev;          // [HW*3] parameters before each spaxel's last update
+    DevBuf<double> recbuf;        // [HW*8] staging of update records
+    DevBuf<int> idxbuf;           // [HW] staging of spaxel lists
+    DevBuf<double> extbuf;           // external-lines staging of d3d_mh_colour_lines: [spaxels][6 + 2D] doubles
     bool fsf_sep = false;         // fsf == u v^T to rounding (k_spatial_sep); D3D_SPATIAL_SEP=0 disables
     int sep_fuse = 1;             // LSF in the same pass (k_spatial_sep_lsf); option sep_fuse = 0 disables
     int spatial_sep = 1;          // option spatial_sep = 0: treat an outer-product FSF as a general one
-    double *sep_uv = nullptr;     // [fh + fw] on the device
+    DevBuf<double> sep_uv;        // [fh + fw] on the device
     bool fsf_symx = false;        // fsf[k][i] == fsf[k][fw-1-i] bit for bit
     bool fsf_symy = false;        // fsf[k][i] == fsf[fh-1-k][i] bit for bit
-    double *fsf_quad = nullptr;   // [(fhh+1)^2] quadrant taps of an x/y-symmetric square FSF (k_conv_rows)
-    double *fsf_quad_sep = nullptr;  // the same table for an outer-product FSF: row 0 = v, row 1 = u
+    DevBuf<double> fsf_quad;      // [(fhh+1)^2] quadrant taps of an x/y-symmetric square FSF (k_conv_rows)
+    DevBuf<double> fsf_quad_sep; // the same table for an outer-product FSF: row 0 = v, row 1 = u
     bool fsf_symt = false;        // ... and fsf[k][i] == fsf[i][k] bit for bit (radial FSFs)
     bool lsf_dense_sym = false;   // dense LSF weights mirror-symmetric bit for bit
     int conv_rows = 1;            // D3D_CONV_ROWS=0: never use the one-pass kernel k_conv_rows
     int conv_zb = 1;              // option conv_zb = 0: depths above 128 keep the march kernels (no z-blocks)
-    double *lsf_dense = nullptr;  // [2*LSF_RL+1] dense LSF weights for the fused epilogue
+    DevBuf<double> lsf_dense;     // [2*LSF_RL+1] dense LSF weights for the fused epilogue
     bool lsf_dense_ok = false;    // taps within +-LSF_RL and power-of-two depth (z-major spectral kernel)
     bool lsf_dense_any = false;   // taps within +-LSF_RL channels at ANY depth (k_spectral_blocks)
     int spectral_blocks = 1;      // option spectral_blocks = 0: never use k_spectral_blocks
@@ -273,70 +316,81 @@ struct d3d_ctx {
     int march_mode = 2;
     int sp_nt = 256;              // spectral / spatial block size
     int march_stamp = 0;          // option march_stamp (EXPERIMENTS builds): phase stamps of the march kernel
+    int post_nt = 0;               // option post_nt = 1: the moments' accumulators' loads and stores non-temporal
+    // The optional features, one sub-struct each: nothing is allocated before its d3d_*_begin, and
+    // `c->feature = {}` frees it and puts every field back (the caller has drained the stream).
     // posterior moments (d3d_post_*): running mean and M2 = sum of squared deviations of the
     // samples' clean cube, convolved cube and (a, c, w, F) map, updated on the device after the
-    // scheduled sweeps (k_post_accum).  Nothing is allocated before d3d_post_begin.
-    bool post_on = false;
-    int post_what = 0;             // bit 0 clean cube, bit 1 convolved cube
-    double *post_cube[4] = {};     // clean mean | clean M2 | convolved mean | convolved M2, device layout
-    double *post_map = nullptr;    // [2][HW*4]: mean | M2 of (a, c, w, F)
-    int64_t post_n = 0;            // samples accumulated
-    int post_first = 0, post_every = 0;  // d3d_post_schedule (every == 0: none)
-    int post_nt = 0;               // option post_nt = 1: the accumulators' loads and stores non-temporal
-    // posterior histograms (d3d_hist_*): per spaxel and per quantity of post_map 64 equal bins and
-    // two tail counters over a range frozen from the moments of the first hist_pilot samples
-    // (k_hist_freeze); every later sample is binned (k_hist_accum).  Nothing is allocated before
-    // d3d_hist_begin.
-    bool hist_on = false, hist_frozen = false;
-    int64_t hist_pilot = 0;        // samples that feed the moments only
-    double hist_span = 0.0;        // the range is mean +- span * sd of the pilot, clipped to the bounds
-    uint32_t *hist_bins = nullptr;   // [HW*4][64]
-    uint32_t *hist_tails = nullptr;  // [HW*4][2]: below | above
-    double *hist_range = nullptr;    // [HW*4][2]: lo | hi (NaN: not frozen yet, or masked)
+    // scheduled sweeps (k_post_accum)
+    struct Post {
+        bool on = false;
+        int what = 0;             // bit 0 clean cube, bit 1 convolved cube
+        DevBuf<double> cube[4];   // clean mean | clean M2 | convolved mean | convolved M2, device layout
+        DevBuf<double> map;       // [2][HW*4]: mean | M2 of (a, c, w, F)
+        int64_t n = 0;            // samples accumulated
+        int first = 0, every = 0; // d3d_post_schedule (every == 0: none)
+    } post;
+    // posterior histograms (d3d_hist_*): per spaxel and per quantity of post.map 64 equal bins and
+    // two tail counters over a range frozen from the moments of the first `pilot` samples
+    // (k_hist_freeze); every later sample is binned (k_hist_accum)
+    struct Hist {
+        bool on = false, frozen = false;
+        int64_t pilot = 0;        // samples that feed the moments only
+        double span = 0.0;        // the range is mean +- span * sd of the pilot, clipped to the bounds
+        DevBuf<uint32_t> bins;    // [HW*4][64]
+        DevBuf<uint32_t> tails;   // [HW*4][2]: below | above
+        DevBuf<double> range;     // [HW*4][2]: lo | hi (NaN: not frozen yet, or masked)
+    } hist;
     // region posteriors (d3d_region_*): per sample of the moments the (F, C, S) of every labelled set
-    // of spaxels into a series, and its summed clean spectrum into a mean and M2 (d3d_region.hip).
-    // Nothing is allocated before d3d_region_begin.
-    bool reg_on = false;
-    int reg_K = 0, reg_what = 0;   // regions 1..K; bit 0 of what: the spectra
-    int64_t reg_cap = 0;           // rows of the series
-    int reg_nchunks = 0;
-    std::vector<int32_t> h_reg_labels;  // the caller's (H,W) map: d3d_set_data lays the members out again
-    std::vector<int32_t> h_reg_sizes;   // [K] members of every region
-    int *reg_member = nullptr;     // [members] spaxels, region after region
-    int4 *reg_chunk = nullptr;     // [chunks] {first member, members, region, -}
-    int *reg_first = nullptr;      // [K + 1] first chunk of every region
-    double *reg_part = nullptr;    // [chunks][4] scalar partials
-    double *reg_fc = nullptr;      // [K][2] F and C between the passes
-    double *reg_series = nullptr;  // [reg_cap][K][3]
-    double *reg_spart = nullptr;   // [chunks][Dp] spectrum partials (spectra on)
-    double *reg_spec = nullptr;    // [2][K][Dp] mean | M2 (spectra on)
-    // per-spaxel jump scales (d3d_adapt_*): every `adapt_window` sweeps of d3d_mh_sweeps each
-    // spaxel's scale moves towards the target acceptance rate (k_mh_adapt), up to sweep
-    // adapt_last; the counters then go on counting.  Nothing is allocated before d3d_adapt_begin.
-    bool adapt_on = false;
-    double *jscale = nullptr;      // [HW] multiplicative jump scale of every spaxel
-    unsigned *jacc = nullptr;      // [HW] accepted proposals since the counters were last cleared
-    double adapt_target = 0.0, adapt_gain = 0.0, adapt_min = 0.0, adapt_max = 0.0;
-    int adapt_window = 0;          // sweeps per adaptation step (0: a fixed map that never adapts)
-    int64_t adapt_last = 0;        // no step after this sweep (the run's numbering: s + sweep_origin)
-    int64_t adapt_n_win = 0;       // sweeps counted since the counters were last cleared
-    int64_t adapt_k = 0;           // adaptation steps taken
+    // of spaxels into a series, and its summed clean spectrum into a mean and M2 (d3d_region.hip)
+    struct Regions {
+        bool on = false;
+        int K = 0, what = 0;      // regions 1..K; bit 0 of what: the spectra
+        int64_t rows = 0;         // rows of the series (the caller's capacity)
+        int nchunks = 0;
+        std::vector<int32_t> h_labels;  // the caller's (H,W) map: d3d_set_data lays the members out again
+        std::vector<int32_t> h_sizes;   // [K] members of every region
+        DevBuf<int> member;       // [members] spaxels, region after region
+        DevBuf<int4> chunk;       // [chunks] {first member, members, region, -}
+        DevBuf<int> first;        // [K + 1] first chunk of every region
+        DevBuf<double> part;      // [chunks][4] scalar partials
+        DevBuf<double> fc;        // [K][2] F and C between the passes
+        DevBuf<double> series;    // [rows][K][3]
+        DevBuf<double> spart;     // [chunks][Dp] spectrum partials (spectra on)
+        DevBuf<double> spec;      // [2][K][Dp] mean | M2 (spectra on)
+    } reg;
+    // per-spaxel jump scales (d3d_adapt_*): every `window` sweeps of d3d_mh_sweeps each spaxel's
+    // scale moves towards the target acceptance rate (k_mh_adapt), up to sweep `last`; the counters
+    // then go on counting
+    struct Adapt {
+        bool on = false;
+        DevBuf<double> jscale;    // [HW] multiplicative jump scale of every spaxel
+        DevBuf<unsigned> jacc;    // [HW] accepted proposals since the counters were last cleared
+        double target = 0.0, gain = 0.0, min = 0.0, max = 0.0;
+        int window = 0;           // sweeps per adaptation step (0: a fixed map that never adapts)
+        int64_t last = 0;         // no step after this sweep (the run's numbering: s + sweep_origin)
+        int64_t n_win = 0;        // sweeps counted since the counters were last cleared
+        int64_t k = 0;            // adaptation steps taken
+    } adapt;
     // smoothness prior between 4-neighbours (d3d_prior_*): lam[k] = 1 / sigma_k^2 of (a, c, w), read by
-    // every MH decision (MHArgs::lam).  Nothing is allocated before the first d3d_prior_energy.
-    bool prior_on = false;
-    double prior_lam[3] = {0.0, 0.0, 0.0};
-    double *prior_part = nullptr;  // [PRIOR_BLOCKS + 1][4] block partials | totals of k_prior_energy
+    // every MH decision (MHArgs::lam).  `part` is allocated by the first d3d_prior_energy and kept.
+    struct Prior {
+        bool on = false;
+        double lam[3] = {0.0, 0.0, 0.0};
+        DevBuf<double> part;      // [PRIOR_BLOCKS + 1][4] block partials | totals of k_prior_energy
+    } prior;
     // Student-t likelihood (d3d_robust_*): after the due sweeps k_robust_step redraws one weight per
-    // voxel from the residual and writes SLOT_IVAR = weight * base 1/variance.  Nothing is allocated
-    // before d3d_robust_begin.
-    bool rb_on = false;
-    bool rb_was_uniform = false;   // ivar_is_uniform before arming (false while armed)
-    int rb_nu = 0, rb_every = 1;
-    int64_t rb_start = 0;          // due: s >= start and (s - start) % every == 0, the run's numbering
-    int64_t rb_accum_from = 0;     // draws of the sweeps from this one on enter the weight mean
-    int64_t rb_count = 0;          // draws in the weight mean
-    double *rb_i0 = nullptr;       // the base 1/variance d3d_set_data left in SLOT_IVAR, device layout
-    double *rb_mean = nullptr;     // running mean of the weights, device layout (0 where rb_i0 == 0)
+    // voxel from the residual and writes SLOT_IVAR = weight * base 1/variance
+    struct Robust {
+        bool on = false;
+        bool was_uniform = false; // ivar_is_uniform before arming (false while armed)
+        int nu = 0, every = 1;
+        int64_t start = 0;        // due: s >= start and (s - start) % every == 0, the run's numbering
+        int64_t accum_from = 0;   // draws of the sweeps from this one on enter the weight mean
+        int64_t count = 0;        // draws in the weight mean
+        DevBuf<double> i0;        // the base 1/variance d3d_set_data left in SLOT_IVAR, device layout
+        DevBuf<double> mean;      // running mean of the weights, device layout (0 where i0 == 0)
+    } robust;
     // d3d_line_search: device time of the last call's bank build (lines + transpose, or the transpose
     // of a host bank) and of its search kernel, by HIP events (read-only options search_bank_ns /
     // search_kernel_ns)
@@ -366,9 +420,9 @@ int launch_spatial(d3d_ctx *c, const double *in, double *out, const double *data
 // params -> SLOT_TMP0 (LSF lines) -> dst (sim, or residual when resid)
 int forward_into(d3d_ctx *c, double *dst, bool resid);
 // d3d_post.hip: one sample (the chain state; SLOT_SIM holds its convolved cube when that moment
-// is on) into the running moments, as sample number c->post_n + 1
+// is on) into the running moments, as sample number c->post.n + 1
 int launch_post_accum(d3d_ctx *c);
-// d3d_post.hip, posterior histograms: the ranges from the moments as they are (c->post_n samples);
+// d3d_post.hip, posterior histograms: the ranges from the moments as they are (c->post.n samples);
 // the chain state into its bins; quantiles, mode and outside share of every histogram into device
 // buffers [HW*4][n_q], [HW*4], [HW*4] (any may be NULL)
 int launch_hist_freeze(d3d_ctx *c);
@@ -376,7 +430,7 @@ int launch_hist_accum(d3d_ctx *c);
 int launch_hist_quantiles(d3d_ctx *c, int n_q, const double *q, double *quantiles, double *mode, double *outside);
 // d3d_post.hip: F = a w flux_factor(c)
 double flux_factor(const d3d_ctx *c);
-// d3d_region.hip: the members, chunks and chunk offsets of c->h_reg_labels under c->h_mask; one
+// d3d_region.hip: the members, chunks and chunk offsets of c->reg.h_labels under c->h_mask; one
 // sample (the chain state) into the series and the spectra, as sample number c->post_n + 1
 void region_layout(const d3d_ctx *c, std::vector<int> &member, std::vector<int4> &chunk, std::vector<int> &first,
                    std::vector<int32_t> &sizes);
@@ -406,9 +460,14 @@ bool zmajor_ok(const d3d_ctx *c);
 // LSF (x) FSF of c->stage in the reference layout (D,H,W), in place (zmajor_ok())
 int launch_zmajor_convolve(d3d_ctx *c);
 
-// ---- d3d_api.hip: what the sweep driver runs between and after the sweeps -----------------
+// ---- d3d_post.hip: what the sweep driver runs between and after the sweeps; what the setters call
 int post_sample(d3d_ctx *c);               // the chain state as one more sample of the posterior moments
 bool post_due(const d3d_ctx *c, int s);    // sweep s (the caller's numbering) is one d3d_post_schedule asked for
+int post_reset(d3d_ctx *c);                // count 0, every accumulator of moments, histograms and regions zero
+// d3d_region.hip: the members of the regions under the mask in force, on the device (d3d_set_data:
+// the mask may have changed); on failure the regions are freed
+int region_members(d3d_ctx *c);
+// ---- d3d_api.hip ---------------------------------------------------------------------------
 bool plan_has_entries(const d3d_ctx *c, int plan);
 int halo_exchange(d3d_ctx *c, int plan);
 // a cube in the device layout into a host array (D,H,W), synchronously (through c->stage)
@@ -417,7 +476,6 @@ int download_device_cube(d3d_ctx *c, const double *src, double *host);
 // ---- d3d_robust.hip: the weights of a Student-t likelihood --------------------------------
 bool robust_due(const d3d_ctx *c, int s);   // sweep s (the caller's numbering) is followed by a draw
 int robust_after_sweep(d3d_ctx *c, int s);  // the pending layers written back, then the draw, where due
-void robust_free(d3d_ctx *c);               // the base cube back into SLOT_IVAR, the buffers freed
 
 // ---- d3d_sweep.hip: local colour residues of colour class `col` (a tile's origin shifts them)
 void colour_residue(const d3d_ctx *c, int col, int *cy, int *cx);

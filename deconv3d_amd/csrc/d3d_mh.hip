@@ -44,13 +44,13 @@ static void fill_chain_fields(const d3d_ctx *c, A &a) {
         a.min_b[k] = c->min_b[k];
         a.max_b[k] = c->max_b[k];
         a.amp[k] = c->amp[k];
-        a.lam[k] = c->prior_on ? c->prior_lam[k] : 0.0;
+        a.lam[k] = c->prior.on ? c->prior.lam[k] : 0.0;
     }
     a.ra = c->ra;
     a.seed = c->seed;
-    a.jscale = c->adapt_on ? c->jscale : nullptr;
-    a.jacc = c->adapt_on ? c->jacc : nullptr;
-    a.prior = c->prior_on ? 1 : 0;
+    a.jscale = c->adapt.on ? c->adapt.jscale : nullptr;
+    a.jacc = c->adapt.on ? c->adapt.jacc : nullptr;
+    a.prior = c->prior.on ? 1 : 0;
 }
 
 void fill_chain_args(const d3d_ctx *c, d3d::MHChainArgs &B, bool tables) {
@@ -141,13 +141,13 @@ void fill_mh_args(d3d_ctx *c, d3d::MHArgs &P) {
 
 int prior_energy(d3d_ctx *c, const double *params_dev, double out4[4]) {
     const int nb = (int)std::min<long>((c->HW + 255) / 256, d3d::PRIOR_BLOCKS);
-    if (!c->prior_part) HIP_TRY(hipMalloc(&c->prior_part, (size_t)(d3d::PRIOR_BLOCKS + 1) * 4 * sizeof(double)));
-    double *total = c->prior_part + (size_t)d3d::PRIOR_BLOCKS * 4;
+    if (!c->prior.part) HIP_TRY(c->prior.part.alloc((size_t)(d3d::PRIOR_BLOCKS + 1) * 4));
+    double *total = c->prior.part + (size_t)d3d::PRIOR_BLOCKS * 4;
     hipLaunchKernelGGL(d3d::k_prior_energy, dim3((unsigned)nb), dim3(256), 0, c->stream, params_dev,
-                       (const uint8_t *)c->mask, c->H, c->W, c->prior_part);
+                       (const uint8_t *)c->mask, c->H, c->W, c->prior.part);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(d3d::k_prior_energy_total, dim3(1), dim3(256), 0, c->stream,
-                       (const double *)c->prior_part, nb, total);
+                       (const double *)c->prior.part, nb, total);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out4, total, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -162,20 +162,20 @@ int accepted_collect(d3d_ctx *c) {
 }
 
 int adapt_after_sweep(d3d_ctx *c, int s) {
-    if (!c->adapt_on) return 0;
-    ++c->adapt_n_win;
+    if (!c->adapt.on) return 0;
+    ++c->adapt.n_win;
     const int64_t at = (int64_t)s + (int64_t)c->sweep_origin;
-    if (c->adapt_window <= 0 || c->adapt_n_win != c->adapt_window || at > c->adapt_last) return 0;
-    ++c->adapt_k;
+    if (c->adapt.window <= 0 || c->adapt.n_win != c->adapt.window || at > c->adapt.last) return 0;
+    ++c->adapt.k;
     const int n = (c->oy1 - c->oy0) * (c->ox1 - c->ox0);
     if (n > 0) {
         hipLaunchKernelGGL(d3d::k_mh_adapt, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                           c->jscale, c->jacc, c->mask, c->W, c->oy0, c->oy1, c->ox0, c->ox1,
-                           (int)c->adapt_n_win, c->adapt_gain / sqrt((double)c->adapt_k), c->adapt_target,
-                           c->adapt_min, c->adapt_max);
+                           c->adapt.jscale, c->adapt.jacc, c->mask, c->W, c->oy0, c->oy1, c->ox0, c->ox1,
+                           (int)c->adapt.n_win, c->adapt.gain / sqrt((double)c->adapt.k), c->adapt.target,
+                           c->adapt.min, c->adapt.max);
         HIP_TRY(hipGetLastError());
     }
-    c->adapt_n_win = 0;
+    c->adapt.n_win = 0;
     c->props_sweep = -1;  // (a table made from the old scales)
     return 0;
 }
@@ -373,7 +373,7 @@ int ensure_ptab(d3d_ctx *c) {
             e[2] = first;
         }
     }
-    if (!c->ptab) HIP_TRY(hipMalloc(&c->ptab, tab.size() * sizeof(double)));
+    if (!c->ptab) HIP_TRY(c->ptab.alloc(tab.size()));
     HIP_TRY(hipMemcpyAsync(c->ptab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));  // `tab` goes out of scope
     c->ptab_valid = true;
@@ -686,12 +686,8 @@ int launch_mh_zb(d3d_ctx *c, d3d::MHArgs &P, unsigned n_items, uint32_t sweep, i
     // allocated once, for the largest launch there can be
     const size_t max_items = (size_t)(c->H / c->fh + 2) * (c->W / c->fw + 2);
     NEED((size_t)n_items <= max_items, D3D_ERR_STATE, "internal: %u windows in one colour launch", n_items);
-    if (!c->z_part) {
-        const size_t need = max_items * P.z_nb * 32;
-        HIP_TRY(hipMalloc(&c->z_part, need * sizeof(double)));
-        c->z_part_cap = need;
-    }
-    if (!c->z_E) HIP_TRY(hipMalloc(&c->z_E, (size_t)2 * c->slots * c->Dp * sizeof(double)));
+    if (!c->z_part) HIP_TRY(c->z_part.alloc(max_items * P.z_nb * 32));
+    if (!c->z_E) HIP_TRY(c->z_E.alloc((size_t)2 * c->slots * c->Dp));
     P.z_part = c->z_part;
     P.z_E = c->z_E;
     if (c->ivar_is_uniform && c->uniform_fast_path) return launch_mh_zb_t<true>(c, P, n_items, sweep, layers);
@@ -764,8 +760,8 @@ int launch_mh_defer(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sw
 }
 
 int ensure_tables(d3d_ctx *c, bool lines) {
-    if (!c->props) HIP_TRY(hipMalloc(&c->props, (size_t)c->HW * sizeof(d3d::MHProposal)));
-    if (lines && !c->ltab) HIP_TRY(hipMalloc(&c->ltab, (size_t)c->HW * 2 * c->Dp * sizeof(double)));
+    if (!c->props) HIP_TRY(c->props.alloc((size_t)c->HW));
+    if (lines && !c->ltab) HIP_TRY(c->ltab.alloc((size_t)c->HW * 2 * c->Dp));
     return 0;
 }
 
@@ -869,7 +865,7 @@ int launch_mh_chain(d3d_ctx *c, int pi, uint32_t sweep0, int n_sweeps) {
     // epochs are 32-bit and monotonic over launches: start over long before they wrap
     const unsigned span = (unsigned)n_sweeps * (unsigned)pt.K;
     if (c->chain_base > (1u << 30) || c->chain_base + span < c->chain_base) {
-        HIP_TRY(hipMemsetAsync(c->chain_flags, 0, 2 * c->chain_slots_cap * sizeof(unsigned), c->stream));
+        HIP_TRY(hipMemsetAsync(c->chain_flags, 0, c->chain_flags.size() * sizeof(unsigned), c->stream));
         c->chain_base = 0;
     }
     c->pend_part = pi;  // fill_mh_args takes the domain from it
@@ -879,7 +875,7 @@ int launch_mh_chain(d3d_ctx *c, int pi, uint32_t sweep0, int n_sweeps) {
     d3d::MHChain F;
     F.cols = c->chain_cols + (size_t)pi * c->fh * c->fw;
     F.flag1 = c->chain_flags;
-    F.flag2 = c->chain_flags + c->chain_slots_cap;
+    F.flag2 = c->chain_flags + c->chain_flags.size() / 2;
     F.err = c->flow_err;
     F.G = c->chain_G;
     F.Gout = c->gbuf[g_out];

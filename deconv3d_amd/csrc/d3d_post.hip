@@ -2,7 +2,8 @@
 // the chain's samples -- clean cube, LSF (x) FSF convolved cube, (a, c, w, F) map -- updated
 // between sweeps without a host round trip.  Posterior histograms (d3d_hist_*): per spaxel and per
 // quantity of the map 64 equal bins over a range frozen from a pilot, filled between sweeps, and
-// their quantile / mode / outside maps.  gfx950 only.
+// their quantile / mode / outside maps.  The lifecycle and the C entry points of both follow the
+// kernels.  gfx950 only.
 #include "d3d_ctx.h"
 
 namespace d3d {
@@ -256,17 +257,17 @@ int launch_post_accum(d3d_ctx *c) {
     A.Dp = c->Dp;
     A.HL = c->HL;
     A.nspax = c->HW;
-    A.n = (double)(c->post_n + 1);
+    A.n = (double)(c->post.n + 1);
     A.flux_k = flux_factor(c);
     A.params = c->params;
     A.mask = c->mask;
     A.sim = c->slot[D3D_SLOT_SIM];
-    A.clean_mean = c->post_cube[0];
-    A.clean_m2 = c->post_cube[1];
-    A.conv_mean = c->post_cube[2];
-    A.conv_m2 = c->post_cube[3];
-    A.map_mean = c->post_map;
-    A.map_m2 = c->post_map + (size_t)c->HW * 4;
+    A.clean_mean = c->post.cube[0];
+    A.clean_m2 = c->post.cube[1];
+    A.conv_mean = c->post.cube[2];
+    A.conv_m2 = c->post.cube[3];
+    A.map_mean = c->post.map;
+    A.map_m2 = c->post.map + (size_t)c->HW * 4;
     A.line = c->line;
     // MULTI only for K > 1 or a table, as every other line kernel
     if (d3d::line_multi(c->line))
@@ -277,8 +278,8 @@ int launch_post_accum(d3d_ctx *c) {
 static d3d::HistArgs hist_args(const d3d_ctx *c) {
     d3d::HistArgs A;
     A.nser = c->HW * 4;
-    A.pilot_m1 = (double)(c->hist_pilot - 1);
-    A.span = c->hist_span;
+    A.pilot_m1 = (double)(c->hist.pilot - 1);
+    A.span = c->hist.span;
     A.flux_k = flux_factor(c);
     for (int k = 0; k < 3; ++k) {
         A.L[k] = c->min_b[k];
@@ -288,11 +289,11 @@ static d3d::HistArgs hist_args(const d3d_ctx *c) {
     A.U[3] = c->max_b[0] * c->max_b[2] * A.flux_k;
     A.params = c->params;
     A.mask = c->mask;
-    A.map_mean = c->post_map;
-    A.map_m2 = c->post_map + (size_t)c->HW * 4;
-    A.range = c->hist_range;
-    A.bins = c->hist_bins;
-    A.tails = c->hist_tails;
+    A.map_mean = c->post.map;
+    A.map_m2 = c->post.map + (size_t)c->HW * 4;
+    A.range = c->hist.range;
+    A.bins = c->hist.bins;
+    A.tails = c->hist.tails;
     return A;
 }
 
@@ -315,9 +316,9 @@ int launch_hist_quantiles(d3d_ctx *c, int n_q, const double *q, double *quantile
     A.nser = c->HW * 4;
     A.n_q = n_q;
     for (int j = 0; j < 8; ++j) A.q[j] = j < n_q ? q[j] : 0.5;
-    A.range = c->hist_range;
-    A.bins = c->hist_bins;
-    A.tails = c->hist_tails;
+    A.range = c->hist.range;
+    A.bins = c->hist.bins;
+    A.tails = c->hist.tails;
     A.quantiles = quantiles;
     A.mode = mode;
     A.outside = outside;
@@ -326,4 +327,231 @@ int launch_hist_quantiles(d3d_ctx *c, int n_q, const double *q, double *quantile
     return 0;
 }
 
+// ---- lifecycle: moments, with the histograms and regions that hang on them ---------------
+// (the caller has drained the stream)
+static void post_free(d3d_ctx *c) {
+    c->hist = {};
+    c->reg = {};
+    c->post = {};
+}
+
+// count 0, accumulators zero (Welford's first sample starts from mean = M2 = 0)
+int post_reset(d3d_ctx *c) {
+    if (!c->post.on) return 0;
+    c->post.n = 0;
+    for (double *p : c->post.cube)
+        if (p) HIP_TRY(hipMemsetAsync(p, 0, c->cube_elems * sizeof(double), c->stream));
+    HIP_TRY(hipMemsetAsync(c->post.map, 0, (size_t)c->HW * 8 * sizeof(double), c->stream));
+    if (c->hist.on) {  // counters zero, ranges not frozen (all bits set: NaN)
+        const size_t nser = (size_t)c->HW * 4;
+        c->hist.frozen = false;
+        HIP_TRY(hipMemsetAsync(c->hist.bins, 0, nser * 64 * sizeof(uint32_t), c->stream));
+        HIP_TRY(hipMemsetAsync(c->hist.tails, 0, nser * 2 * sizeof(uint32_t), c->stream));
+        HIP_TRY(hipMemsetAsync(c->hist.range, 0xff, nser * 2 * sizeof(double), c->stream));
+    }
+    if (c->reg.on) {  // series and spectra zero; the count is the moments'
+        if (c->reg.series)
+            HIP_TRY(hipMemsetAsync(c->reg.series, 0, (size_t)c->reg.rows * c->reg.K * 3 * sizeof(double), c->stream));
+        if (c->reg.spec)
+            HIP_TRY(hipMemsetAsync(c->reg.spec, 0, (size_t)2 * c->reg.K * c->Dp * sizeof(double), c->stream));
+    }
+    return 0;
+}
+
+int post_sample(d3d_ctx *c) {
+    NEED(c->post.on, D3D_ERR_STATE, "posterior moments not begun (d3d_post_begin)");
+    NEED(!c->tiled, D3D_ERR_UNSUPPORTED,
+         "posterior moments on a tile: the parameters of its frame belong to other ranks");
+    NEED(c->have_params, D3D_ERR_STATE, "parameters not set");
+    if (c->post.what & 2) {
+        NEED(c->have_taps, D3D_ERR_STATE, "taps not set");
+        if (int rc = forward_into(c, c->slot[D3D_SLOT_SIM], false)) return rc;
+    }
+    if (int rc = launch_post_accum(c)) return rc;
+    if (c->reg.on)  // d3d_region_begin: the same sample, the same number
+        if (int rc = launch_region_sample(c)) return rc;
+    ++c->post.n;
+    if (c->hist.on) {  // d3d_hist_begin: the pilot's last sample freezes the ranges, later ones are binned
+        if (c->post.n == c->hist.pilot) {
+            if (int rc = launch_hist_freeze(c)) return rc;
+            c->hist.frozen = true;
+        } else if (c->hist.frozen) {
+            if (int rc = launch_hist_accum(c)) return rc;
+        }
+    }
+    return 0;
+}
+
+bool post_due(const d3d_ctx *c, int s) {
+    return c->post.on && c->post.every > 0 && s >= c->post.first &&
+           (s - c->post.first) % c->post.every == 0;
+}
+
 }  // namespace d3dh
+
+using namespace d3dh;
+
+extern "C" {
+
+int d3d_post_begin(d3d_ctx *c, int what) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    NEED(what >= 0 && what <= 3, D3D_ERR_INVALID,
+         "what = %d: bit 0 the clean cube, bit 1 the convolved cube (0..3)", what);
+    NEED(!c->tiled, D3D_ERR_UNSUPPORTED,
+         "posterior moments on a tile: the parameters of its frame belong to other ranks");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    post_free(c);
+    hipError_t e = c->post.map.alloc((size_t)c->HW * 8);
+    for (int k = 0; k < 4 && e == hipSuccess; ++k)
+        if (what & (1 << (k / 2))) e = c->post.cube[k].alloc(c->cube_elems);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // the context stays usable for the chain
+        post_free(c);
+        return fail(D3D_ERR_HIP, "posterior accumulators (%d cubes of %zu bytes): %s",
+                    2 * ((what & 1) + (what >> 1)), c->cube_elems * sizeof(double), hipGetErrorString(e));
+    }
+    c->post.on = true;
+    c->post.what = what;
+    return post_reset(c);
+}
+
+int d3d_post_schedule(d3d_ctx *c, int first_sweep, int every) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    NEED(first_sweep >= 0, D3D_ERR_INVALID, "first_sweep = %d is negative", first_sweep);
+    NEED(every >= 1, D3D_ERR_INVALID, "every = %d: accumulate one sweep in how many (>= 1)", every);
+    NEED(c->post.on, D3D_ERR_STATE, "posterior moments not begun (d3d_post_begin)");
+    c->post.first = first_sweep;
+    c->post.every = every;
+    return D3D_OK;
+}
+
+int d3d_post_accumulate(d3d_ctx *c) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    return post_sample(c);
+}
+
+int d3d_post_count(d3d_ctx *c, int64_t *n) {
+    NEED(c && n, D3D_ERR_INVALID, "NULL argument");
+    *n = c->post.on ? c->post.n : 0;
+    return D3D_OK;
+}
+
+int d3d_post_get(d3d_ctx *c, int which, double *mean, double *m2) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    NEED(which >= 0 && which <= 2, D3D_ERR_INVALID,
+         "which = %d: 0 the parameter map, 1 the clean cube, 2 the convolved cube", which);
+    NEED(c->post.on, D3D_ERR_STATE, "posterior moments not begun (d3d_post_begin)");
+    NEED(which == 0 || (c->post.what & which), D3D_ERR_STATE,
+         "the %s cube's moments were not begun (d3d_post_begin what = %d)",
+         which == 1 ? "clean" : "convolved", c->post.what);
+    HIP_TRY(hipSetDevice(c->device));
+    if (which == 0) {
+        const size_t bytes = (size_t)c->HW * 4 * sizeof(double);
+        if (mean) HIP_TRY(hipMemcpyAsync(mean, c->post.map, bytes, hipMemcpyDeviceToHost, c->stream));
+        if (m2)
+            HIP_TRY(hipMemcpyAsync(m2, c->post.map + (size_t)c->HW * 4, bytes, hipMemcpyDeviceToHost,
+                                   c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return D3D_OK;
+    }
+    if (mean)
+        if (int rc = download_device_cube(c, c->post.cube[2 * (which - 1)], mean)) return rc;
+    if (m2)
+        if (int rc = download_device_cube(c, c->post.cube[2 * (which - 1) + 1], m2)) return rc;
+    return D3D_OK;
+}
+
+int d3d_post_end(d3d_ctx *c) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    post_free(c);
+    return D3D_OK;
+}
+
+int d3d_hist_begin(d3d_ctx *c, int64_t pilot, double span) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    NEED(pilot >= 2, D3D_ERR_INVALID, "pilot = %lld: the range needs a standard deviation (>= 2 samples)",
+         (long long)pilot);
+    NEED(std::isfinite(span) && span > 0.0, D3D_ERR_INVALID, "span = %g is not a positive number", span);
+    NEED(c->post.on, D3D_ERR_STATE, "posterior moments not begun (d3d_post_begin)");
+    NEED(c->have_cfg, D3D_ERR_STATE, "bounds not set (d3d_mh_config)");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->hist = {};
+    const size_t nser = (size_t)c->HW * 4;
+    hipError_t e = c->hist.bins.alloc(nser * 64);
+    if (e == hipSuccess) e = c->hist.tails.alloc(nser * 2);
+    if (e == hipSuccess) e = c->hist.range.alloc(nser * 2);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // the context stays usable for the chain and the moments
+        c->hist = {};
+        return fail(D3D_ERR_HIP, "posterior histograms (%zu bytes): %s", nser * (66 * sizeof(uint32_t) + 16),
+                    hipGetErrorString(e));
+    }
+    c->hist.on = true;
+    c->hist.pilot = pilot;
+    c->hist.span = span;
+    return post_reset(c);  // the pilot is the moments' first samples
+}
+
+int d3d_hist_count(d3d_ctx *c, int64_t *n) {
+    NEED(c && n, D3D_ERR_INVALID, "NULL argument");
+    *n = c->hist.on ? std::max<int64_t>(c->post.n - c->hist.pilot, 0) : 0;
+    return D3D_OK;
+}
+
+int d3d_hist_get(d3d_ctx *c, uint32_t *bins, uint32_t *tails, double *range) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    NEED(c->hist.on, D3D_ERR_STATE, "posterior histograms not begun (d3d_hist_begin)");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t nser = (size_t)c->HW * 4;
+    if (bins)
+        HIP_TRY(hipMemcpyAsync(bins, c->hist.bins, nser * 64 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (tails)
+        HIP_TRY(hipMemcpyAsync(tails, c->hist.tails, nser * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (range)
+        HIP_TRY(hipMemcpyAsync(range, c->hist.range, nser * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return D3D_OK;
+}
+
+int d3d_hist_quantiles(d3d_ctx *c, int n_q, const double *q, double *quantiles, double *mode, double *outside) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    NEED(n_q >= 1 && n_q <= 8, D3D_ERR_INVALID, "n_q = %d: 1 to 8 quantiles a call", n_q);
+    NEED(q, D3D_ERR_INVALID, "q is NULL");
+    for (int j = 0; j < n_q; ++j)
+        NEED(q[j] > 0.0 && q[j] < 1.0, D3D_ERR_INVALID, "q[%d] = %g lies outside (0, 1)", j, q[j]);
+    NEED(c->hist.on, D3D_ERR_STATE, "posterior histograms not begun (d3d_hist_begin)");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t nser = (size_t)c->HW * 4;
+    DevBuf<double> buf;  // quantiles [nser][n_q] | mode [nser] | outside [nser]
+    HIP_TRY(buf.alloc(nser * (size_t)(n_q + 2)));
+    double *d_mode = buf + nser * (size_t)n_q, *d_out = d_mode + nser;
+    int rc = launch_hist_quantiles(c, n_q, q, quantiles ? buf.get() : nullptr, mode ? d_mode : nullptr,
+                                   outside ? d_out : nullptr);
+    hipError_t e = hipSuccess;
+    if (!rc && quantiles)
+        e = hipMemcpyAsync(quantiles, buf, nser * (size_t)n_q * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (!rc && e == hipSuccess && mode)
+        e = hipMemcpyAsync(mode, d_mode, nser * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (!rc && e == hipSuccess && outside)
+        e = hipMemcpyAsync(outside, d_out, nser * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);  // (before buf goes)
+    if (rc) return rc;
+    HIP_TRY(e);
+    HIP_TRY(es);
+    return D3D_OK;
+}
+
+int d3d_hist_end(d3d_ctx *c) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->hist = {};
+    return D3D_OK;
+}
+
+}  // extern "C"

@@ -278,21 +278,18 @@ namespace {
 
 // everything a call allocates, freed on every return path
 struct PrepBuffers {
-    double *cube = nullptr;      // (D,HW) the caller's cube
-    double *vals = nullptr;      // (HW,Dp) valid voxels, NaN elsewhere
-    double *vals2 = nullptr;     // ... after the rejection pass
-    double *cont_d = nullptr;    // (HW,Dp) running median
-    double *cont = nullptr;      // (D,HW)
-    double *res = nullptr;       // (D,HW)
-    double *stats = nullptr;     // [D][3]
-    double *sigma = nullptr;     // [D]
-    uint8_t *valid = nullptr;    // (D,HW)
-    uint8_t *select = nullptr;   // [HW]
+    DevBuf<double> cube;         // (D,HW) the caller's cube
+    DevBuf<double> vals;         // (HW,Dp) valid voxels, NaN elsewhere
+    DevBuf<double> vals2;        // ... after the rejection pass
+    DevBuf<double> cont_d;       // (HW,Dp) running median
+    DevBuf<double> cont;         // (D,HW)
+    DevBuf<double> res;          // (D,HW)
+    DevBuf<double> stats;        // [D][3]
+    DevBuf<double> sigma;        // [D]
+    DevBuf<uint8_t> valid;       // (D,HW)
+    DevBuf<uint8_t> select;      // [HW]
     hipEvent_t ev[4] = {};       // around the running-median kernel, around the statistics kernel
     ~PrepBuffers() {
-        void *p[] = {cube, vals, vals2, cont_d, cont, res, stats, sigma, valid, select};
-        for (void *q : p)
-            if (q) (void)hipFree(q);
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
     }
@@ -371,13 +368,13 @@ int prep_running_median(d3d_ctx *c, const double *cube, const uint8_t *valid, in
     HIP_TRY(hipSetDevice(c->device));
     PrepBuffers B;
     if (int rc = make_events(B)) return rc;
-    HIP_TRY(hipMalloc(&B.cube, n_host * sizeof(double)));
-    HIP_TRY(hipMalloc(&B.vals, n_dev * sizeof(double)));
-    HIP_TRY(hipMalloc(&B.cont_d, n_dev * sizeof(double)));
-    HIP_TRY(hipMalloc(&B.cont, n_host * sizeof(double)));
+    HIP_TRY(B.cube.alloc(n_host));
+    HIP_TRY(B.vals.alloc(n_dev));
+    HIP_TRY(B.cont_d.alloc(n_dev));
+    HIP_TRY(B.cont.alloc(n_host));
     HIP_TRY(hipMemcpyAsync(B.cube, cube, n_host * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (valid) {
-        HIP_TRY(hipMalloc(&B.valid, n_host));
+        HIP_TRY(B.valid.alloc(n_host));
         HIP_TRY(hipMemcpyAsync(B.valid, valid, n_host, hipMemcpyHostToDevice, c->stream));
     }
     if (int rc = launch_to_device(c, B.cube, B.valid, B.vals)) return rc;
@@ -394,11 +391,11 @@ int prep_channel_stats(d3d_ctx *c, const double *cube, const uint8_t *select, do
     HIP_TRY(hipSetDevice(c->device));
     PrepBuffers B;
     if (int rc = make_events(B)) return rc;
-    HIP_TRY(hipMalloc(&B.cube, n_host * sizeof(double)));
-    HIP_TRY(hipMalloc(&B.stats, (size_t)c->D * 3 * sizeof(double)));
+    HIP_TRY(B.cube.alloc(n_host));
+    HIP_TRY(B.stats.alloc((size_t)c->D * 3));
     HIP_TRY(hipMemcpyAsync(B.cube, cube, n_host * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (select) {
-        HIP_TRY(hipMalloc(&B.select, (size_t)c->HW));
+        HIP_TRY(B.select.alloc((size_t)c->HW));
         HIP_TRY(hipMemcpyAsync(B.select, select, (size_t)c->HW, hipMemcpyHostToDevice, c->stream));
     }
     if (int rc = launch_channel_stats(c, B, B.cube, B.select, B.stats)) return rc;
@@ -420,19 +417,19 @@ int prep_prepare(d3d_ctx *c, const double *cube, const uint8_t *select, int half
     HIP_TRY(hipSetDevice(c->device));
     PrepBuffers B;
     if (int rc = make_events(B)) return rc;
-    HIP_TRY(hipMalloc(&B.cube, n_host * sizeof(double)));
-    HIP_TRY(hipMalloc(&B.vals, n_dev * sizeof(double)));
-    HIP_TRY(hipMalloc(&B.cont_d, n_dev * sizeof(double)));
-    HIP_TRY(hipMalloc(&B.cont, n_host * sizeof(double)));
-    HIP_TRY(hipMalloc(&B.res, n_host * sizeof(double)));
-    HIP_TRY(hipMalloc(&B.stats, (size_t)c->D * 3 * sizeof(double)));
+    HIP_TRY(B.cube.alloc(n_host));
+    HIP_TRY(B.vals.alloc(n_dev));
+    HIP_TRY(B.cont_d.alloc(n_dev));
+    HIP_TRY(B.cont.alloc(n_host));
+    HIP_TRY(B.res.alloc(n_host));
+    HIP_TRY(B.stats.alloc((size_t)c->D * 3));
     if (rejecting) {
-        HIP_TRY(hipMalloc(&B.vals2, n_dev * sizeof(double)));
-        HIP_TRY(hipMalloc(&B.sigma, (size_t)c->D * sizeof(double)));
+        HIP_TRY(B.vals2.alloc(n_dev));
+        HIP_TRY(B.sigma.alloc((size_t)c->D));
     }
     HIP_TRY(hipMemcpyAsync(B.cube, cube, n_host * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (select) {
-        HIP_TRY(hipMalloc(&B.select, (size_t)c->HW));
+        HIP_TRY(B.select.alloc((size_t)c->HW));
         HIP_TRY(hipMemcpyAsync(B.select, select, (size_t)c->HW, hipMemcpyHostToDevice, c->stream));
     }
     std::vector<double> st((size_t)c->D * 3), sigma((size_t)c->D);

@@ -178,10 +178,10 @@ namespace d3dh {
 // unmasked spaxels in row-major order, cut into chunks of 64 (the last of a region may be short).
 void region_layout(const d3d_ctx *c, std::vector<int> &member, std::vector<int4> &chunk, std::vector<int> &first,
                    std::vector<int32_t> &sizes) {
-    const int K = c->reg_K;
+    const int K = c->reg.K;
     sizes.assign((size_t)K, 0);
     for (long s = 0; s < c->HW; ++s) {
-        const int l = c->h_reg_labels[(size_t)s];
+        const int l = c->reg.h_labels[(size_t)s];
         if (l > 0 && c->h_mask[(size_t)s]) ++sizes[(size_t)l - 1];
     }
     std::vector<size_t> at((size_t)K + 1, 0);
@@ -189,7 +189,7 @@ void region_layout(const d3d_ctx *c, std::vector<int> &member, std::vector<int4>
     member.assign(at[(size_t)K], 0);
     std::vector<size_t> next(at.begin(), at.end() - 1);
     for (long s = 0; s < c->HW; ++s) {
-        const int l = c->h_reg_labels[(size_t)s];
+        const int l = c->reg.h_labels[(size_t)s];
         if (l > 0 && c->h_mask[(size_t)s]) member[next[(size_t)l - 1]++] = (int)s;
     }
     chunk.clear();
@@ -210,23 +210,23 @@ static void launch_region_spectra_t(d3d_ctx *c, const d3d::RegionArgs &A) {
 
 int launch_region_sample(d3d_ctx *c) {
     d3d::RegionArgs A;
-    A.K = c->reg_K;
+    A.K = c->reg.K;
     A.D = c->D;
     A.Dp = c->Dp;
     A.steps = (c->Dp + 63) / 64;
-    A.n_chunks = c->reg_nchunks;
-    A.n = (double)(c->post_n + 1);
+    A.n_chunks = c->reg.nchunks;
+    A.n = (double)(c->post.n + 1);
     A.flux_k = flux_factor(c);
     A.params = c->params;
-    A.member = c->reg_member;
-    A.chunk = c->reg_chunk;
-    A.first = c->reg_first;
-    A.part = c->reg_part;
-    A.fc = c->reg_fc;
-    A.row = c->post_n < c->reg_cap ? c->reg_series + (size_t)c->post_n * (size_t)c->reg_K * 3 : nullptr;
-    A.spart = c->reg_spart;
-    A.spec_mean = c->reg_spec;
-    A.spec_m2 = c->reg_spec ? c->reg_spec + (size_t)c->reg_K * c->Dp : nullptr;
+    A.member = c->reg.member;
+    A.chunk = c->reg.chunk;
+    A.first = c->reg.first;
+    A.part = c->reg.part;
+    A.fc = c->reg.fc;
+    A.row = c->post.n < c->reg.rows ? c->reg.series + (size_t)c->post.n * (size_t)c->reg.K * 3 : nullptr;
+    A.spart = c->reg.spart;
+    A.spec_mean = c->reg.spec;
+    A.spec_m2 = c->reg.spec ? c->reg.spec + (size_t)c->reg.K * c->Dp : nullptr;
     A.line = c->line;
     const unsigned chunk_grid = (unsigned)((A.n_chunks + 3) / 4), region_grid = (unsigned)((A.K + 3) / 4);
     if (A.row) {  // (past the capacity the series stops, the spectra go on)
@@ -253,4 +253,114 @@ int launch_region_sample(d3d_ctx *c) {
     return 0;
 }
 
+// The members of the regions under the mask in force, on the device (d3d_region_begin, and
+// d3d_set_data on a context with regions: its mask may have changed).  The tables that depend on
+// the number of chunks are allocated here; on failure the regions are freed.
+int region_members(d3d_ctx *c) {
+    std::vector<int> member, first;
+    std::vector<int4> chunk;
+    region_layout(c, member, chunk, first, c->reg.h_sizes);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->reg.spart.reset();
+    c->reg.nchunks = (int)chunk.size();
+    const size_t nm = std::max<size_t>(member.size(), 1), nc = std::max<size_t>(chunk.size(), 1);
+    hipError_t e = c->reg.member.alloc(nm);
+    if (e == hipSuccess) e = c->reg.chunk.alloc(nc);
+    if (e == hipSuccess) e = c->reg.first.alloc(first.size());
+    if (e == hipSuccess) e = c->reg.part.alloc(nc * 4);
+    if (e == hipSuccess && (c->reg.what & 1)) e = c->reg.spart.alloc(nc * c->Dp);
+    if (e == hipSuccess && !member.empty())
+        e = hipMemcpyAsync(c->reg.member, member.data(), member.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && !chunk.empty())
+        e = hipMemcpyAsync(c->reg.chunk, chunk.data(), chunk.size() * sizeof(int4), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(c->reg.first, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the host vectors go out of scope
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // the context stays usable for the chain and the moments
+        c->reg = {};
+        return fail(D3D_ERR_HIP, "region posteriors (%zu members in %zu chunks): %s", member.size(), chunk.size(),
+                    hipGetErrorString(e));
+    }
+    return 0;
+}
+
 }  // namespace d3dh
+
+using namespace d3dh;
+
+extern "C" {
+
+int d3d_region_begin(d3d_ctx *c, const int32_t *labels, int K, int64_t capacity, int what) {
+    NEED(c && labels, D3D_ERR_INVALID, "NULL argument");
+    NEED(K >= 1, D3D_ERR_INVALID, "K = %d: at least one region", K);
+    NEED(capacity >= 0, D3D_ERR_INVALID, "capacity = %lld is negative", (long long)capacity);
+    NEED(what >= 0 && what <= 1, D3D_ERR_INVALID, "what = %d: bit 0 the spectra (0..1)", what);
+    for (long s = 0; s < c->HW; ++s)
+        NEED(labels[s] >= 0 && labels[s] <= K, D3D_ERR_INVALID, "labels[%ld] = %d lies outside 0 .. K = %d", s,
+             (int)labels[s], K);
+    NEED(!c->tiled, D3D_ERR_UNSUPPORTED,
+         "region posteriors on a tile: the parameters of its frame belong to other ranks");
+    NEED(c->post.on, D3D_ERR_STATE, "posterior moments not begun (d3d_post_begin)");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->reg = {};
+    c->reg.K = K;
+    c->reg.what = what;
+    c->reg.rows = capacity;
+    c->reg.h_labels.assign(labels, labels + c->HW);
+    const size_t series_elems = (size_t)capacity * K * 3;
+    const size_t spec_elems = (what & 1) ? (size_t)2 * K * c->Dp : 0;
+    hipError_t e = c->reg.fc.alloc((size_t)K * 2);
+    if (e == hipSuccess && series_elems) e = c->reg.series.alloc(series_elems);
+    if (e == hipSuccess && spec_elems) e = c->reg.spec.alloc(spec_elems);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // the context stays usable for the chain and the moments
+        c->reg = {};
+        return fail(D3D_ERR_HIP, "region posteriors (%zu bytes): %s", (series_elems + spec_elems) * sizeof(double),
+                    hipGetErrorString(e));
+    }
+    if (int rc = region_members(c)) return rc;
+    c->reg.on = true;
+    return post_reset(c);  // the series' rows are the moments' samples
+}
+
+int d3d_region_count(d3d_ctx *c, int64_t *n, int64_t *stored) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    if (n) *n = c->reg.on ? c->post.n : 0;
+    if (stored) *stored = c->reg.on ? std::min<int64_t>(c->post.n, c->reg.rows) : 0;
+    return D3D_OK;
+}
+
+int d3d_region_get(d3d_ctx *c, double *series, double *spec_mean, double *spec_m2, int32_t *sizes) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    NEED(c->reg.on, D3D_ERR_STATE, "region posteriors not begun (d3d_region_begin)");
+    NEED(c->reg.spec || (!spec_mean && !spec_m2), D3D_ERR_STATE,
+         "the regions' spectra were not begun (d3d_region_begin what = %d)", c->reg.what);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t stored = (size_t)std::min<int64_t>(c->post.n, c->reg.rows);
+    if (series && stored)
+        HIP_TRY(hipMemcpyAsync(series, c->reg.series, stored * c->reg.K * 3 * sizeof(double), hipMemcpyDeviceToHost,
+                               c->stream));
+    // (K, Dp) on the device, (K, D) for the caller: the pad channel of an odd depth stays behind
+    const size_t row = (size_t)c->D * sizeof(double), pitch = (size_t)c->Dp * sizeof(double);
+    if (spec_mean)
+        HIP_TRY(hipMemcpy2DAsync(spec_mean, row, c->reg.spec, pitch, row, (size_t)c->reg.K, hipMemcpyDeviceToHost,
+                                 c->stream));
+    if (spec_m2)
+        HIP_TRY(hipMemcpy2DAsync(spec_m2, row, c->reg.spec + (size_t)c->reg.K * c->Dp, pitch, row, (size_t)c->reg.K,
+                                 hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (sizes) std::copy(c->reg.h_sizes.begin(), c->reg.h_sizes.end(), sizes);
+    return D3D_OK;
+}
+
+int d3d_region_end(d3d_ctx *c) {
+    NEED(c, D3D_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->reg = {};
+    return D3D_OK;
+}
+
+}  // extern "C"

@@ -109,9 +109,9 @@ static __global__ __launch_bounds__(256) void k_robust_view(long n, const double
 namespace d3dh {
 
 bool robust_due(const d3d_ctx *c, int s) {
-    if (!c->rb_on) return false;
+    if (!c->robust.on) return false;
     const int64_t rs = (int64_t)s + (int64_t)c->sweep_origin;
-    return rs >= c->rb_start && (rs - c->rb_start) % c->rb_every == 0;
+    return rs >= c->robust.start && (rs - c->robust.start) % c->robust.every == 0;
 }
 
 // the draw of sweep `rs` (the run's numbering) from the residual as it is
@@ -120,26 +120,26 @@ static int robust_draw(d3d_ctx *c, int64_t rs) {
     d3d::RobustArgs A;
     A.HW = c->HW;
     A.HL = c->HL;
-    A.nu = c->rb_nu;
-    A.m = (c->rb_nu + 1) / 2;
-    A.even = (c->rb_nu & 1) ? 0 : 1;
+    A.nu = c->robust.nu;
+    A.m = (c->robust.nu + 1) / 2;
+    A.even = (c->robust.nu & 1) ? 0 : 1;
     A.nblk = (A.m + (A.even ? 2 : 0) + 1) / 2;
     A.sweep = (uint32_t)rs;
     A.k0 = (uint32_t)c->seed;
     A.k1 = (uint32_t)(c->seed >> 32);
-    const bool acc = rs >= c->rb_accum_from;
-    A.n = acc ? (double)(c->rb_count + 1) : 0.0;
+    const bool acc = rs >= c->robust.accum_from;
+    A.n = acc ? (double)(c->robust.count + 1) : 0.0;
     A.err = c->slot[D3D_SLOT_ERR];
-    A.i0 = c->rb_i0;
+    A.i0 = c->robust.i0;
     A.ivar = c->slot[D3D_SLOT_IVAR];
-    A.mean = c->rb_mean;
+    A.mean = c->robust.mean;
     const dim3 grid((unsigned)((c->HW + 3) / 4));
     if (acc)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_robust_step<true>), grid, dim3(256), 0, c->stream, A);
     else
         hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_robust_step<false>), grid, dim3(256), 0, c->stream, A);
     HIP_TRY(hipGetLastError());
-    if (acc) ++c->rb_count;
+    if (acc) ++c->robust.count;
     return 0;
 }
 
@@ -149,18 +149,14 @@ int robust_after_sweep(d3d_ctx *c, int s) {
 }
 
 // the base cube back into the slot (on the context's stream, waited for), the buffers freed
-void robust_free(d3d_ctx *c) {
-    if (c->rb_on) {
-        (void)hipMemcpyAsync(c->slot[D3D_SLOT_IVAR], c->rb_i0, c->cube_elems * sizeof(double),
+static void robust_free(d3d_ctx *c) {
+    if (c->robust.on) {
+        (void)hipMemcpyAsync(c->slot[D3D_SLOT_IVAR], c->robust.i0, c->cube_elems * sizeof(double),
                              hipMemcpyDeviceToDevice, c->stream);
         (void)hipStreamSynchronize(c->stream);
-        c->ivar_is_uniform = c->rb_was_uniform;
+        c->ivar_is_uniform = c->robust.was_uniform;
     }
-    if (c->rb_i0) (void)hipFree(c->rb_i0);
-    if (c->rb_mean) (void)hipFree(c->rb_mean);
-    c->rb_i0 = c->rb_mean = nullptr;
-    c->rb_on = false;
-    c->rb_count = 0;
+    c->robust = {};
 }
 
 }  // namespace d3dh
@@ -185,31 +181,31 @@ int d3d_robust_begin(d3d_ctx *c, int nu, int every, int64_t start, int64_t accum
     HIP_TRY(hipStreamSynchronize(c->stream));
     robust_free(c);  // (armed already: the base cube first goes back)
     const size_t bytes = c->cube_elems * sizeof(double);
-    hipError_t e = hipMalloc(&c->rb_i0, bytes);
-    if (e == hipSuccess) e = hipMalloc(&c->rb_mean, bytes);
+    hipError_t e = c->robust.i0.alloc(c->cube_elems);
+    if (e == hipSuccess) e = c->robust.mean.alloc(c->cube_elems);
     if (e == hipSuccess)
-        e = hipMemcpyAsync(c->rb_i0, c->slot[D3D_SLOT_IVAR], bytes, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->rb_mean, 0, bytes, c->stream);
+        e = hipMemcpyAsync(c->robust.i0, c->slot[D3D_SLOT_IVAR], bytes, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->robust.mean, 0, bytes, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         (void)hipGetLastError();  // the context stays usable for the Gaussian chain
         robust_free(c);
         return fail(D3D_ERR_HIP, "robust weights (2 cubes of %zu bytes): %s", bytes, hipGetErrorString(e));
     }
-    c->rb_on = true;
-    c->rb_nu = nu;
-    c->rb_every = every;
-    c->rb_start = start;
-    c->rb_accum_from = accumulate_from;
-    c->rb_count = 0;
-    c->rb_was_uniform = c->ivar_is_uniform;
+    c->robust.on = true;
+    c->robust.nu = nu;
+    c->robust.every = every;
+    c->robust.start = start;
+    c->robust.accum_from = accumulate_from;
+    c->robust.count = 0;
+    c->robust.was_uniform = c->ivar_is_uniform;
     c->ivar_is_uniform = false;  // the slot is read from now on (bit-identical while it holds the base cube)
     return D3D_OK;
 }
 
 int d3d_robust_step(d3d_ctx *c, int64_t sweep_number) {
     NEED(c, D3D_ERR_INVALID, "ctx is NULL");
-    NEED(c->rb_on, D3D_ERR_STATE, "robust weights not begun (d3d_robust_begin)");
+    NEED(c->robust.on, D3D_ERR_STATE, "robust weights not begun (d3d_robust_begin)");
     NEED(sweep_number >= 0, D3D_ERR_INVALID, "sweep_number = %lld is negative", (long long)sweep_number);
     NEED(c->have_taps && c->have_params && c->have_cfg, D3D_ERR_STATE,
          "taps/parameters/mh_config not set: the draw needs the residual and the seed");
@@ -223,16 +219,16 @@ int d3d_robust_step(d3d_ctx *c, int64_t sweep_number) {
 
 int d3d_robust_get(d3d_ctx *c, double *weights, double *weight_mean, int64_t *count) {
     NEED(c, D3D_ERR_INVALID, "ctx is NULL");
-    NEED(c->rb_on, D3D_ERR_STATE, "robust weights not begun (d3d_robust_begin)");
+    NEED(c->robust.on, D3D_ERR_STATE, "robust weights not begun (d3d_robust_begin)");
     HIP_TRY(hipSetDevice(c->device));
-    if (count) *count = c->rb_count;
+    if (count) *count = c->robust.count;
     const unsigned grid = (unsigned)((c->cube_elems + 255) / 256);
     double *const scratch = c->slot[D3D_SLOT_TMP0];
     for (int k = 0; k < 2; ++k) {
         double *const out = k == 0 ? weights : weight_mean;
         if (!out) continue;
         hipLaunchKernelGGL(d3d::k_robust_view, dim3(grid), dim3(256), 0, c->stream, (long)c->cube_elems,
-                           (const double *)(k == 0 ? c->slot[D3D_SLOT_IVAR] : c->rb_mean), (const double *)c->rb_i0,
+                           (const double *)(k == 0 ? c->slot[D3D_SLOT_IVAR] : c->robust.mean), (const double *)c->robust.i0,
                            k == 0 ? 1 : 0, scratch);
         HIP_TRY(hipGetLastError());
         if (int rc = download_device_cube(c, scratch, out)) return rc;

@@ -217,14 +217,11 @@ namespace {
 
 // everything the call allocates, freed on every return path
 struct SearchBuffers {
-    double *bank = nullptr, *bt = nullptr, *pmap = nullptr, *stat = nullptr;
-    uint8_t *ones = nullptr, *umask = nullptr;
-    int *best = nullptr;
+    DevBuf<double> bank, bt, pmap, stat;
+    DevBuf<uint8_t> ones, umask;
+    DevBuf<int> best;
     hipEvent_t ev[4] = {};  // around the bank build, around the search kernel
     ~SearchBuffers() {
-        void *p[] = {bank, bt, pmap, stat, ones, umask, best};
-        for (void *q : p)
-            if (q) (void)hipFree(q);
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
     }
@@ -256,11 +253,11 @@ int line_search(d3d_ctx *c, int n_c, const double *centres, int n_w, const doubl
     const int ncp = (int)((n_cand + 1) & ~1L);
     HIP_TRY(hipSetDevice(c->device));
     SearchBuffers B;
-    HIP_TRY(hipMalloc(&B.bank, bank_bytes));
-    HIP_TRY(hipMalloc(&B.bt, (size_t)c->D * ncp * sizeof(double)));
-    HIP_TRY(hipMalloc(&B.umask, (size_t)c->HW));
-    HIP_TRY(hipMalloc(&B.best, (size_t)c->HW * sizeof(int)));
-    HIP_TRY(hipMalloc(&B.stat, (size_t)c->HW * 4 * sizeof(double)));
+    HIP_TRY(B.bank.alloc((size_t)n_cand * c->Dp));
+    HIP_TRY(B.bt.alloc((size_t)c->D * ncp));
+    HIP_TRY(B.umask.alloc((size_t)c->HW));
+    HIP_TRY(B.best.alloc((size_t)c->HW));
+    HIP_TRY(B.stat.alloc((size_t)c->HW * 4));
     for (hipEvent_t &e : B.ev) HIP_TRY(hipEventCreate(&e));
     if (host_bank) {
         HIP_TRY(hipEventRecord(B.ev[0], c->stream));
@@ -279,8 +276,8 @@ int line_search(d3d_ctx *c, int n_c, const double *centres, int n_w, const doubl
                 r[1] = centres[ic];
                 r[2] = widths[iw];
             }
-        HIP_TRY(hipMalloc(&B.pmap, rows.size() * sizeof(double)));
-        HIP_TRY(hipMalloc(&B.ones, (size_t)n_cand));
+        HIP_TRY(B.pmap.alloc(rows.size()));
+        HIP_TRY(B.ones.alloc((size_t)n_cand));
         HIP_TRY(hipMemcpyAsync(B.pmap, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice,
                                c->stream));
         HIP_TRY(hipMemsetAsync(B.ones, 1, (size_t)n_cand, c->stream));
@@ -288,12 +285,11 @@ int line_search(d3d_ctx *c, int n_c, const double *centres, int n_w, const doubl
         HIP_TRY(hipEventRecord(B.ev[0], c->stream));
         // the line launchers take their spectrum count and mask from the context
         const long HW = c->HW;
-        uint8_t *mask = c->mask;
         c->HW = n_cand;
-        c->mask = B.ones;
+        std::swap(c->mask, B.ones);
         const int rc = launch_lines(c, B.bank, 1, B.pmap);
         c->HW = HW;
-        c->mask = mask;
+        std::swap(c->mask, B.ones);
         if (rc) return rc;
     }
     {

@@ -209,8 +209,8 @@ int launch_march_stamped(d3d_ctx *c, d3d::SpatialArgs A, const double *in, doubl
     const long items = (long)((c->W + TX - 1) / TX) * ((c->H + HY - 1) / HY);
     const unsigned grid = (unsigned)((items + S - 1) / S);
     const size_t nw = (size_t)grid * (NT / 64);
-    unsigned long long *dbg = nullptr;
-    HIP_TRY(hipMalloc(&dbg, nw * 8 * sizeof(unsigned long long)));
+    DevBuf<unsigned long long> dbg;
+    HIP_TRY(dbg.alloc(nw * 8));
     HIP_TRY(hipMemsetAsync(dbg, 0, nw * 8 * sizeof(unsigned long long), c->stream));
     c->spatial_path = D3D_SPATIAL_MARCH_EXPERIMENT;
     A.dbg = dbg;
@@ -221,7 +221,6 @@ int launch_march_stamped(d3d_ctx *c, d3d::SpatialArgs A, const double *in, doubl
     HIP_TRY(hipMemcpyAsync(h.data(), dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                            c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    (void)hipFree(dbg);
     double sum[5] = {0, 0, 0, 0, 0}, steps = 0;
     unsigned long long tmin = ~0ULL, tmax = 0;
     size_t live = 0;

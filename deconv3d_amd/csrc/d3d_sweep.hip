@@ -24,7 +24,7 @@ int snap_setup(d3d_ctx *c) {
     HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     const size_t bytes = (size_t)c->HW * 4 * sizeof(double);
     for (int b = 0; b < d3d_ctx::STREAM_NB; ++b) {
-        HIP_TRY(hipMalloc(&c->snap_dev[b], bytes));
+        HIP_TRY(c->snap_dev[b].alloc((size_t)c->HW * 4));
         HIP_TRY(hipHostMalloc((void **)&c->snap_host[b], bytes, hipHostMallocDefault));
         HIP_TRY(hipEventCreateWithFlags(&c->snap_ready[b], hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&c->snap_done[b], hipEventDisableTiming));
@@ -261,15 +261,13 @@ int halo_drain_one(d3d_ctx *c) {
 }
 
 // For the duration of a d3d_mh_sweeps_batch call every chain runs on the leader's stream.  On
-// every way out: that stream drained, the chains' device arguments freed, each context back on
-// its own stream.
+// every way out: that stream drained (the chains' device arguments, declared before the scope, go
+// after it), each context back on its own stream.
 struct BatchScope {
     d3d_ctx **cs;
     std::vector<hipStream_t> own;  // of the contexts switched so far
-    d3d::MHChainArgs *dev = nullptr;
     ~BatchScope() {
         (void)hipStreamSynchronize(cs[0]->stream);
-        if (dev) (void)hipFree(dev);
         for (size_t r = 0; r < own.size(); ++r) cs[r]->stream = own[r];
     }
 };
@@ -421,14 +419,14 @@ int d3d_mh_sweeps_batch(d3d_ctx **ctxs, int n_ctx, int n_sweeps, int first_sweep
              "ctx %d: another line shape than ctx 0 (the chains share the launch's arguments)", r);
         // (the chains share the leader's pending-layer state, and a from-scratch residual
         // clears a chain's own: they must all be rebuilt at the same sweeps)
-        NEED(c->prior_on == L->prior_on, D3D_ERR_INVALID,
+        NEED(c->prior.on == L->prior.on, D3D_ERR_INVALID,
              "ctx %d: the smoothness prior (d3d_prior_begin) is %s, on ctx 0 it is %s (the chains share the "
-             "launch's kernel; their weights may differ)", r, c->prior_on ? "on" : "off", L->prior_on ? "on" : "off");
+             "launch's kernel; their weights may differ)", r, c->prior.on ? "on" : "off", L->prior.on ? "on" : "off");
         NEED(c->refresh_every == L->refresh_every, D3D_ERR_INVALID,
              "ctx %d: refresh_every %d differs from ctx 0's %d (batched chains rebuild their residuals together)",
              r, c->refresh_every, L->refresh_every);
         // (and written back at the same sweeps: d3d_robust_begin's draws flush the pending layers)
-        NEED(c->rb_on == L->rb_on && (!c->rb_on || (c->rb_every == L->rb_every && c->rb_start == L->rb_start)),
+        NEED(c->robust.on == L->robust.on && (!c->robust.on || (c->robust.every == L->robust.every && c->robust.start == L->robust.start)),
              D3D_ERR_INVALID,
              "ctx %d: robust weights (d3d_robust_begin) armed, every or start differ from ctx 0's (batched chains "
              "write their pending residual updates back together)", r);
@@ -452,6 +450,7 @@ int d3d_mh_sweeps_batch(d3d_ctx **ctxs, int n_ctx, int n_sweeps, int first_sweep
         ctxs[r]->batch_layers = b.layers;  // (read-only option batch_layers)
         b.small = b.small && mh_small_usable(ctxs[r]);
     }
+    DevBuf<d3d::MHChainArgs> dev;
     BatchScope scope = {ctxs};
     for (int r = 0; r < n_ctx; ++r) {
         HIP_TRY(hipStreamSynchronize(ctxs[r]->stream));
@@ -469,9 +468,9 @@ int d3d_mh_sweeps_batch(d3d_ctx **ctxs, int n_ctx, int n_sweeps, int first_sweep
     }
     if (b.small)
         if (int rc = ensure_ptab(L)) return rc;
-    HIP_TRY(hipMalloc(&scope.dev, n_ctx * sizeof(d3d::MHChainArgs)));
-    HIP_TRY(hipMemcpy(scope.dev, host.data(), n_ctx * sizeof(d3d::MHChainArgs), hipMemcpyHostToDevice));
-    b.dev = scope.dev;
+    HIP_TRY(dev.alloc((size_t)n_ctx));
+    HIP_TRY(hipMemcpy(dev, host.data(), n_ctx * sizeof(d3d::MHChainArgs), hipMemcpyHostToDevice));
+    b.dev = dev;
     for (int s = first_sweep; s < first_sweep + n_sweeps; ++s) {
         const uint32_t rs = (uint32_t)s + L->sweep_origin;
         if (b.small) {  // every chain's proposals and lines of this sweep, one launch

@@ -447,14 +447,13 @@ struct d3d_temper {
     size_t cube_elems = 0, par_elems = 0;
     int nblk = 0;     // workgroups per chain of k_temper_energy
     int xblk = 0;     // workgroups per pair of k_temper_exchange
-    void *dev = nullptr;  // the group's one device block
+    DevBuf<char> dev;     // the group's one device block
     d3d::TemperBlock T = {};
     hipEvent_t done = nullptr;  // end of the last round on the leader's stream
     // exchange of patches (d3d_temper_set_patch): nothing allocated before the first such round
     int patch = 0;               // 0: whole cubes
-    void *pcount = nullptr;      // [2][n-1] patch attempts | accepts
-    void *prec = nullptr;        // the per-tile record of the last round, prec_cap records per pair
-    size_t prec_cap = 0;
+    DevBuf<unsigned long long> pcount;  // [2][n-1] patch attempts | accepts
+    DevBuf<char> prec;           // the per-tile record of the last round, 7 * 8 + 4 bytes per pair and tile
     d3d::PatchBlock P = {};
     int pgeom[6] = {0, 0, 0, 0, 0, 0};  // oy, ox, nty, ntx, my, mx of the last patch round
     bool plast = false;          // the last round was a patch round
@@ -506,23 +505,16 @@ void philox_host(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0
 int ensure_patch_block(d3d_temper *t, size_t nrec) {
     const size_t np = (size_t)t->n - 1;
     if (!t->pcount) {
-        HIP_TRY(hipMalloc(&t->pcount, 2 * np * 8));
+        HIP_TRY(t->pcount.alloc(2 * np));
         HIP_TRY(hipMemsetAsync(t->pcount, 0, 2 * np * 8, t->ctxs[0]->stream));
-        t->P.attempts = static_cast<unsigned long long *>(t->pcount);
+        t->P.attempts = t->pcount;
         t->P.accepts = t->P.attempts + np;
     }
-    if (nrec > t->prec_cap) {
-        if (t->prec) {
-            HIP_TRY(hipStreamSynchronize(t->ctxs[0]->stream));
-            HIP_TRY(hipFree(t->prec));
-            t->prec = nullptr;
-            t->prec_cap = 0;
-        }
-        HIP_TRY(hipMalloc(&t->prec, np * nrec * (7 * 8 + 4)));
-        t->prec_cap = nrec;
-    }
+    const size_t bytes = np * nrec * (7 * 8 + 4);
+    if (bytes > t->prec.size() && t->prec) HIP_TRY(hipStreamSynchronize(t->ctxs[0]->stream));
+    HIP_TRY(t->prec.reserve(bytes));
     // (laid out for this round's record count: d3d_temper_last_patches reads it the same way)
-    double *d = static_cast<double *>(t->prec);
+    double *d = reinterpret_cast<double *>(t->prec.get());
     t->P.terms = d;
     d += np * nrec * 5;
     t->P.u = d;
@@ -585,8 +577,8 @@ int patch_round(d3d_temper *t, int64_t round) {
     A.my = my;
     A.mx = mx;
     A.parity = parity;
-    A.prior = L->prior_on && (L->prior_lam[0] != 0.0 || L->prior_lam[1] != 0.0 || L->prior_lam[2] != 0.0);
-    for (int k = 0; k < 3; ++k) A.lam[k] = L->prior_on ? L->prior_lam[k] : 0.0;
+    A.prior = L->prior.on && (L->prior.lam[0] != 0.0 || L->prior.lam[1] != 0.0 || L->prior.lam[2] != 0.0);
+    for (int k = 0; k < 3; ++k) A.lam[k] = L->prior.on ? L->prior.lam[k] : 0.0;
     A.round = (long long)round;
     A.seed = t->seed;
     A.fsf = L->fsf;
@@ -658,7 +650,7 @@ int d3d_temper_create(d3d_temper **out, d3d_ctx **ctxs, int n, const double *bet
         NEED(c->have_taps && c->have_data, D3D_ERR_STATE, "ctx %d: taps/data not set", r);
         NEED(!c->tiled && c->parts.size() == 1 && !c->comm, D3D_ERR_UNSUPPORTED,
              "ctx %d is tiled or partitioned: tempered chains are whole cubes", r);
-        NEED(c->ext_cap == 0, D3D_ERR_UNSUPPORTED,
+        NEED(!c->extbuf, D3D_ERR_UNSUPPORTED,
              "ctx %d is driven by d3d_mh_colour_lines: its lines live on the host, tempering swaps device state", r);
         NEED(c->device == L->device && c->D == L->D && c->H == L->H && c->W == L->W && c->fh == L->fh &&
                  c->fw == L->fw,
@@ -692,10 +684,10 @@ int d3d_temper_create(d3d_temper **out, d3d_ctx **ctxs, int n, const double *bet
     const size_t nl = 2 * (size_t)(n - 1) + n;
     const size_t ni = (size_t)(n - 1) + n;
     const size_t bytes = (nd + nl) * 8 + ni * 4;
-    hipError_t e = hipMalloc(&t->dev, bytes);
+    hipError_t e = t->dev.alloc(bytes);
     if (e == hipSuccess) e = hipMemset(t->dev, 0, bytes);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&t->done, hipEventDisableTiming);
-    double *d = static_cast<double *>(t->dev);
+    double *d = reinterpret_cast<double *>(t->dev.get());
     t->T.partials = d;
     d += (size_t)n * t->nblk;
     t->T.energy = d;
@@ -726,7 +718,6 @@ int d3d_temper_create(d3d_temper **out, d3d_ctx **ctxs, int n, const double *bet
     }
     if (e != hipSuccess) {
         if (t->done) (void)hipEventDestroy(t->done);
-        if (t->dev) (void)hipFree(t->dev);
         delete t;
         HIP_TRY(e);
     }
@@ -759,8 +750,8 @@ int d3d_temper_swap(d3d_temper *t, int64_t round) {
     if (t->patch > 0) {
         for (int r = 1; r < t->n; ++r) {
             const d3d_ctx *c = t->ctxs[r];
-            bool same = c->prior_on == L->prior_on;
-            for (int k = 0; k < 3; ++k) same = same && (!c->prior_on || c->prior_lam[k] == L->prior_lam[k]);
+            bool same = c->prior.on == L->prior.on;
+            for (int k = 0; k < 3; ++k) same = same && (!c->prior.on || c->prior.lam[k] == L->prior.lam[k]);
             NEED(same, D3D_ERR_INVALID,
                  "ctx %d: another smoothness prior than ctx 0 (the prior's term of a patch exchange cancels "
                  "only between rungs of one prior)", r);
@@ -857,11 +848,8 @@ int d3d_temper_destroy(d3d_temper *t) {
     if (!t) return D3D_OK;
     (void)hipSetDevice(t->device);
     (void)hipEventSynchronize(t->done);  // (a round may still be running)
-    if (t->pcount) (void)hipFree(t->pcount);
-    if (t->prec) (void)hipFree(t->prec);
     if (t->done) (void)hipEventDestroy(t->done);
-    if (t->dev) (void)hipFree(t->dev);
-    delete t;
+    delete t;  // every DevBuf of the group
     return D3D_OK;
 }
 

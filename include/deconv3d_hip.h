@@ -110,7 +110,9 @@ int d3d_timer_stop(d3d_ctx *ctx, double *elapsed_ms);
  * "spatial_path" (the last FSF pass -- d3d_convolve_slots, d3d_forward, d3d_residual, d3d_simulate,
  * a residual rebuilt by the sweeps), "spectral_path" (the last stand-alone LSF pass of
  * d3d_convolve_slots) and "stage_path" (the last d3d_stage_convolve / d3d_convolve): the
- * D3D_SPATIAL_*, D3D_SPECTRAL_* and D3D_STAGE_* codes below. */
+ * D3D_SPATIAL_*, D3D_SPECTRAL_* and D3D_STAGE_* codes below.
+ * "device_bytes" (read-only): the bytes of device memory the library holds, over all contexts and
+ * tempering groups of the process (the pinned snapshot ring is host memory and not counted). */
 enum {
     D3D_SPATIAL_CONV_ROWS = 1,     /* k_conv_rows, FSF only, one block of <= 128 channels */
     D3D_SPATIAL_CONV_ROWS_ZB = 2,  /* k_conv_rows in z-blocks of 128 channels (FSF only) */
