@@ -13,6 +13,8 @@ from .math_utils import median_clip  # noqa: F401
 from . import adapt  # noqa: F401
 from . import posterior  # noqa: F401
 from .posterior import PosteriorHistograms, PosteriorMoments  # noqa: F401
+from . import predictive  # noqa: F401
+from .predictive import PredictiveAccuracy  # noqa: F401
 from . import prepare  # noqa: F401
 from .prepare import Prepared, prepare_cube  # noqa: F401
 from . import regions  # noqa: F401

@@ -47,6 +47,7 @@ SYMBOLS = [
     "d3d_temper_create", "d3d_temper_swap", "d3d_temper_get", "d3d_temper_last", "d3d_temper_destroy",
     "d3d_temper_set_patch", "d3d_temper_last_patches", "d3d_temper_get_patches",
     "d3d_robust_begin", "d3d_robust_step", "d3d_robust_get", "d3d_robust_end",
+    "d3d_pred_begin", "d3d_pred_count", "d3d_pred_get", "d3d_pred_maps", "d3d_pred_cubes", "d3d_pred_end",
 ]
 
 # posterior moments (a table, so that tools/posterior_time.py can load the PARENT commit's library,
@@ -125,7 +126,16 @@ ROBUST_PROTOTYPES = {
     "d3d_robust_get": [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)],
     "d3d_robust_end": [],
 }
-POST_CLEAN, POST_CONVOLVED = 1, 2                     # d3d_post_begin: bits of `what`
+# pointwise predictive accuracy (a table for the same reason: tools/predictive_time.py)
+PRED_PROTOTYPES = {
+    "d3d_pred_begin": [],
+    "d3d_pred_count": [C.POINTER(C.c_int64)],
+    "d3d_pred_get": [C.POINTER(C.c_double)] * 4,
+    "d3d_pred_maps": [C.POINTER(C.c_double)],
+    "d3d_pred_cubes": [C.POINTER(C.c_double)] * 2,
+    "d3d_pred_end": [],
+}
+POST_CLEAN, POST_CONVOLVED = 1, 2                   # d3d_post_begin: bits of `what`
 POST_PARAMETERS, POST_CLEAN_CUBE, POST_CONVOLVED_CUBE = 0, 1, 2   # d3d_post_get: `which`
 REGION_SPECTRA = 1                                    # d3d_region_begin: bit of `what`
 
@@ -251,7 +261,8 @@ def load():
     for name, argtypes in (list(POST_PROTOTYPES.items()) + list(ADAPT_PROTOTYPES.items())
                            + list(SEARCH_PROTOTYPES.items()) + list(PREP_PROTOTYPES.items())
                            + list(PRIOR_PROTOTYPES.items()) + list(HIST_PROTOTYPES.items())
-                           + list(REGION_PROTOTYPES.items()) + list(ROBUST_PROTOTYPES.items())):
+                           + list(REGION_PROTOTYPES.items()) + list(ROBUST_PROTOTYPES.items())
+                           + list(PRED_PROTOTYPES.items())):
         getattr(lib, name).argtypes = [ctx_p] + argtypes
     for name, argtypes in TEMPER_PROTOTYPES.items():
         getattr(lib, name).argtypes = argtypes
@@ -1011,6 +1022,40 @@ class Engine(object):
     def robust_end(self):
         """Disarm: the base 1/variance back, bit for bit."""
         _check(self._lib.d3d_robust_end(self._ctx))
+
+    # -- pointwise predictive accuracy --------------------------------------------------
+    def pred_begin(self):
+        """Allocate and zero the four accumulators of the pointwise log density (include/
+        deconv3d_hip.h: d3d_pred_begin) and start the moments afresh: every sample of theirs is
+        from now on one of these too.  Needs post_begin; after robust_begin when both are wanted."""
+        _check(self._lib.d3d_pred_begin(self._ctx))
+
+    def pred_count(self):
+        n = C.c_int64(0)
+        _check(self._lib.d3d_pred_count(self._ctx, C.byref(n)))
+        return n.value
+
+    def pred_get(self):
+        """The raw accumulators (M, S, mean, M2) of q, each (D,H,W), 0 where the voxel is not counted."""
+        out = [np.empty(self.shape, dtype=np.float64) for _ in range(4)]
+        _check(self._lib.d3d_pred_get(self._ctx, *[_dp(a) for a in out]))
+        return tuple(out)
+
+    def pred_maps(self):
+        """(H,W,4): sum of lppd_v, sum of p_v, counted voxels, sum of (lppd_v - p_v)^2 per spaxel."""
+        out = np.empty(self.shape[1:] + (4,), dtype=np.float64)
+        _check(self._lib.d3d_pred_maps(self._ctx, _dp(out)))
+        return out
+
+    def pred_cubes(self, lppd=True, p_waic=True):
+        """(lppd_v, p_v), each (D,H,W) with NaN where the voxel is not counted; None for one not asked for."""
+        a = np.empty(self.shape, dtype=np.float64) if lppd else None
+        b = np.empty(self.shape, dtype=np.float64) if p_waic else None
+        _check(self._lib.d3d_pred_cubes(self._ctx, _dp(a) if lppd else None, _dp(b) if p_waic else None))
+        return a, b
+
+    def pred_end(self):
+        _check(self._lib.d3d_pred_end(self._ctx))
 
     # -- smoothness prior between neighbouring spaxels ----------------------------------
     def prior_begin(self, lam):

@@ -4,7 +4,8 @@
 // kernels; d3d_sweep.hip: the sweep driver; d3d_post.hip: posterior moments and histograms;
 // d3d_region.hip: region posteriors; d3d_search.hip: the matched-filter line search; d3d_prep.hip:
 // continuum removal and channel noise of a raw cube; d3d_temper.hip: replica exchange between
-// tempered chains; d3d_robust.hip: the per-voxel weights of a Student-t likelihood).
+// tempered chains; d3d_robust.hip: the per-voxel weights of a Student-t likelihood; d3d_pred.hip:
+// lppd and WAIC per voxel).
 // Ownership: every device allocation is a DevBuf, freed by whoever holds it -- the context or group
 // it is a member of (their `delete`), or the call it is a local of.  An optional feature's state is
 // one sub-struct of the context, and its *_end is `c->feature = {}`: buffers freed, fields back at
@@ -391,6 +392,14 @@ struct d3d_ctx {
         DevBuf<double> i0;        // the base 1/variance d3d_set_data left in SLOT_IVAR, device layout
         DevBuf<double> mean;      // running mean of the weights, device layout (0 where i0 == 0)
     } robust;
+    // pointwise predictive accuracy (d3d_pred_*): per voxel and per sample of the moments the
+    // chain-varying part q of the log density of the residual -- its running maximum M, S = sum
+    // exp(q - M), and Welford's mean and M2 (k_pred_accum); lppd and the WAIC penalty at extraction
+    struct Pred {
+        bool on = false;
+        int nu = 0;               // the likelihood of every sample: 0 Gaussian, else the armed robust.nu
+        DevBuf<double> cube[4];   // M | S | mean | M2, device layout (0 where the voxel is not counted)
+    } pred;
     // d3d_line_search: device time of the last call's bank build (lines + transpose, or the transpose
     // of a host bank) and of its search kernel, by HIP events (read-only options search_bank_ns /
     // search_kernel_ns)
@@ -476,6 +485,11 @@ int download_device_cube(d3d_ctx *c, const double *src, double *host);
 // ---- d3d_robust.hip: the weights of a Student-t likelihood --------------------------------
 bool robust_due(const d3d_ctx *c, int s);   // sweep s (the caller's numbering) is followed by a draw
 int robust_after_sweep(d3d_ctx *c, int s);  // the pending layers written back, then the draw, where due
+
+// ---- d3d_pred.hip: pointwise predictive accuracy ------------------------------------------
+// the chain state's residual (made valid, pending layers written back) as sample number
+// c->post.n + 1 of the four accumulators
+int pred_sample(d3d_ctx *c);
 
 // ---- d3d_sweep.hip: local colour residues of colour class `col` (a tile's origin shifts them)
 void colour_residue(const d3d_ctx *c, int col, int *cy, int *cx);

@@ -173,6 +173,32 @@ __device__ __forceinline__ void welford(double &mean, double &m2, double m, doub
     m2 += delta * (m - mean);
 }
 
+// A double2 cell of a streaming accumulator cube (k_post_accum, k_pred_accum), NTV: past the caches
+// (option post_nt)
+typedef double post_v2d __attribute__((ext_vector_type(2)));
+
+template <bool NTV>
+__device__ __forceinline__ double2 post_load(const double *p) {
+    if constexpr (NTV) {
+        const post_v2d t = __builtin_nontemporal_load(reinterpret_cast<const post_v2d *>(p));
+        return make_double2(t.x, t.y);
+    } else {
+        return *reinterpret_cast<const double2 *>(p);
+    }
+}
+
+template <bool NTV>
+__device__ __forceinline__ void post_store(double *p, double2 v) {
+    if constexpr (NTV) {
+        post_v2d t;
+        t.x = v.x;
+        t.y = v.y;
+        __builtin_nontemporal_store(t, reinterpret_cast<post_v2d *>(p));
+    } else {
+        *reinterpret_cast<double2 *>(p) = v;
+    }
+}
+
 struct SpectralArgs {
     int D, Dp, HL, N, ntaps;
     long nspax;

@@ -22,30 +22,6 @@ struct PostArgs {
     LineShape line;
 };
 
-typedef double post_v2d __attribute__((ext_vector_type(2)));
-
-template <bool NTV>
-__device__ __forceinline__ double2 post_load(const double *p) {
-    if constexpr (NTV) {
-        const post_v2d t = __builtin_nontemporal_load(reinterpret_cast<const post_v2d *>(p));
-        return make_double2(t.x, t.y);
-    } else {
-        return *reinterpret_cast<const double2 *>(p);
-    }
-}
-
-template <bool NTV>
-__device__ __forceinline__ void post_store(double *p, double2 v) {
-    if constexpr (NTV) {
-        post_v2d t;
-        t.x = v.x;
-        t.y = v.y;
-        __builtin_nontemporal_store(t, reinterpret_cast<post_v2d *>(p));
-    } else {
-        *reinterpret_cast<double2 *>(p) = v;
-    }
-}
-
 template <bool NTV>
 __device__ __forceinline__ void welford_pair(double *mean, double *m2, double2 m, double n) {
     double2 mu = post_load<NTV>(mean), s = post_load<NTV>(m2);
@@ -332,6 +308,7 @@ int launch_hist_quantiles(d3d_ctx *c, int n_q, const double *q, double *quantile
 static void post_free(d3d_ctx *c) {
     c->hist = {};
     c->reg = {};
+    c->pred = {};
     c->post = {};
 }
 
@@ -355,6 +332,8 @@ int post_reset(d3d_ctx *c) {
         if (c->reg.spec)
             HIP_TRY(hipMemsetAsync(c->reg.spec, 0, (size_t)2 * c->reg.K * c->Dp * sizeof(double), c->stream));
     }
+    if (c->pred.on)  // the first sample overwrites M and S; Welford's starts from zero
+        for (double *p : c->pred.cube) HIP_TRY(hipMemsetAsync(p, 0, c->cube_elems * sizeof(double), c->stream));
     return 0;
 }
 
@@ -368,6 +347,8 @@ int post_sample(d3d_ctx *c) {
         if (int rc = forward_into(c, c->slot[D3D_SLOT_SIM], false)) return rc;
     }
     if (int rc = launch_post_accum(c)) return rc;
+    if (c->pred.on)  // d3d_pred_begin: the same sample, the same number
+        if (int rc = pred_sample(c)) return rc;
     if (c->reg.on)  // d3d_region_begin: the same sample, the same number
         if (int rc = launch_region_sample(c)) return rc;
     ++c->post.n;

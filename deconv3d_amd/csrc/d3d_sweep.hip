@@ -479,6 +479,14 @@ int d3d_mh_sweeps_batch(d3d_ctx **ctxs, int n_ctx, int n_sweeps, int first_sweep
             if (int rc = launch_line_table(L, T, rs, b.dev, n_ctx)) return rc;
         }
         if (int rc = run_part(L, 0, rs, &b)) return rc;
+        // d3d_pred_begin: a predictive sample writes its chain's pending layers back, and the chains
+        // share the leader's pending-layer state: where one chain samples (tempering: rung 0), all
+        // write theirs back
+        bool pred_flush = false;
+        for (int r = 0; r < n_ctx; ++r) pred_flush = pred_flush || (ctxs[r]->pred.on && post_due(ctxs[r], s));
+        if (pred_flush)
+            for (int r = 0; r < n_ctx; ++r)
+                if (int rc = flush_pending(ctxs[r])) return rc;
         // chain after chain, where d3d_mh_sweeps' loop runs one: the chains share a stream and
         // touch disjoint buffers, so the order across chains does not change any of them
         for (int r = 0; r < n_ctx; ++r)

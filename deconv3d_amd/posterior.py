@@ -91,6 +91,7 @@ class PosteriorMoments(object):
         self._cache = {}
         self.histograms = histograms    # a PosteriorHistograms, or None
         self.regions = None             # a regions.RegionPosterior (Run(regions=...)), or None
+        self.predictive = None          # a predictive.PredictiveAccuracy (Run(predictive=...)), or None
 
     @classmethod
     def from_engine(cls, engine, template=None, histograms=False):
@@ -164,7 +165,8 @@ class PosteriorMoments(object):
         """``<prefix>_posterior_{clean,convolved}_{mean,std}.fits`` and
         ``<prefix>_posterior_parameters.npz`` (count, parameters_mean, parameters_std,
         flux_mean, flux_std), beside the files of ``Run.save(prefix)``; with regions their
-        ``<prefix>_posterior_regions.npz``."""
+        ``<prefix>_posterior_regions.npz``, with the predictive accuracy its
+        ``<prefix>_posterior_predictive.npz``."""
         for name in ("clean", "convolved"):
             for kind in ("mean", "std"):
                 self._cube(getattr(self, "%s_%s" % (name, kind))).to_fits(
@@ -174,6 +176,8 @@ class PosteriorMoments(object):
                  flux_mean=self.flux_mean, flux_std=self.flux_std)
         if self.regions is not None:
             self.regions.save(prefix)
+        if self.predictive is not None:
+            self.predictive.save(prefix)
 
 
 class PosteriorHistograms(object):

@@ -10,7 +10,8 @@ of freedom is that Gaussian with each voxel's variance divided by a latent weigh
 on ``variance_v / lambda_v`` (include/deconv3d_hip.h: d3d_robust_*).
 
 ``run.likelihoods``, the chi2 map and the window probe of a robust run are those of the conditional
-Gaussian under the current weights, not Student-t log densities.
+Gaussian under the current weights, not Student-t log densities; ``Run(predictive=True)`` scores the
+run by the Student-t marginal instead (deconv3d_amd/predictive.py).
 """
 from __future__ import annotations
 

@@ -39,7 +39,7 @@ import numpy as np
 
 from . import _lib, adapt as _adapt, ensemble, posterior as _posterior, prepare as _prepare, \
     regions as _regions, \
-    prior as _prior, robust as _robust, search as _search, tempering as _tempering
+    predictive as _predictive, prior as _prior, robust as _robust, search as _search, tempering as _tempering
 from .cube import Cube, read_fits
 from .host_model import HostModelChain
 from .instruments import Instrument
@@ -296,6 +296,21 @@ class Run:
     ``resume_state=`` refuses a state written with others and re-makes the last due draw at or
     before the checkpointed sweep from the restored state; the weight mean starts afresh.  Costs
     two more cubes of device memory per chain.
+
+    ``predictive=True`` (or ``dict()``, for future keys; default ``None``: off, nothing allocated or
+    launched; needs ``posterior_burn_in``) keeps, on the device, the pointwise predictive density of
+    every voxel over the samples of the posterior moments: ``lppd_v = log mean_s p(y_v | theta_s)``
+    and the WAIC penalty ``p_v = var_s log p(y_v | theta_s)`` (d3d_pred_*), under the run's own
+    likelihood -- Gaussian, or with ``robust=`` the Student-t marginal on the given variance.
+    ``run.posterior.predictive`` is a :class:`deconv3d_amd.predictive.PredictiveAccuracy`
+    (``count``; ``lppd_map``, ``p_waic_map``, ``elpd_map``, ``voxels``; ``lppd``, ``p_waic``,
+    ``elpd``, ``waic``, ``se``; ``lppd_cube``, ``p_waic_cube``; ``compare(other)`` -> ``(delta_elpd,
+    se_delta)``; ``save(prefix)``), ``None`` without the keyword.  The chain is bit for bit the chain
+    without the keyword.  With ``chains=R`` every chain keeps its own,
+    ``run.posteriors[r].predictive``, and the pooled one merges their accumulators exactly;
+    ``tempering=`` follows rung 0.  Not part of a checkpoint: a resumed run starts afresh.  A
+    host-evaluated line model raises ``NotImplementedError``.  Costs four more cubes of device
+    memory per chain.
     """
 
     def __init__(
@@ -334,12 +349,13 @@ class Run:
         tempering=None,
         regions=None,
         robust=None,
+        predictive=None,
     ):
         prepare_cfg, search_cfg, posterior_burn_in, posterior_every, hist_cfg = self._check_keywords(
             prepare, initial_search, initial_parameters, resume_state, posterior_burn_in,
             posterior_every, posterior_histograms, adapt_sweeps, adapt_window, adapt_target,
             adapt_gain, adapt_scale_range, smoothness, tempering, keep_one_in, write_every,
-            max_iterations, chains, regions, robust)
+            max_iterations, chains, regions, robust, predictive)
         self._read_inputs(cube, prepare_cfg, mask, variance, device)
         self._read_instrument(instrument)
         self._read_model(model, jump_amplitude, gibbs_apriori_variance, seed, posterior_burn_in)
@@ -362,7 +378,8 @@ class Run:
     def _check_keywords(self, prepare, initial_search, initial_parameters, resume_state,
                         posterior_burn_in, posterior_every, posterior_histograms, adapt_sweeps,
                         adapt_window, adapt_target, adapt_gain, adapt_scale_range, smoothness,
-                        tempering, keep_one_in, write_every, max_iterations, chains, regions, robust=None):
+                        tempering, keep_one_in, write_every, max_iterations, chains, regions, robust=None,
+                        predictive=None):
         """The keywords' own checks.  Returns the checked ``prepare=`` and ``initial_search=``,
         the posterior schedule and the checked ``posterior_histograms=``."""
         # (before anything else: no device work yet)
@@ -374,6 +391,7 @@ class Run:
         hist_cfg = _posterior.check_histograms(posterior_histograms, posterior_burn_in)
         # (the map's shape is checked against the cube's in _read_inputs)
         self._regions_cfg = _regions.check_regions(regions, None, posterior_burn_in)
+        self._predictive_cfg = _predictive.check_keyword(predictive, posterior_burn_in)
         adapt_cfg = None
         if adapt_sweeps is not None:
             adapt_cfg = _AdaptKeywords(*_adapt.check_keywords(adapt_sweeps, adapt_window, adapt_target,
@@ -516,6 +534,9 @@ class Run:
         if self._regions_cfg is not None and self._host_model:
             self._refuse_host_model("regions=", "the device follows regions only for the models it "
                                     "evaluates itself")
+        if self._predictive_cfg is not None and self._host_model:
+            self._refuse_host_model("predictive=", "the device accumulates the predictive density only "
+                                    "between the sweeps it runs itself")
         if posterior_burn_in is not None and self._host_model:
             self._refuse_host_model("posterior_burn_in=", "the device accumulates posterior moments "
                                     "only for the models it evaluates itself")
@@ -705,6 +726,9 @@ class Run:
                     first = cfg["start"] if posterior_burn_in is None else posterior_burn_in + self.sweep_origin
                     eng.robust_begin(cfg["nu"], cfg["every"], cfg["start"],
                                      max(first, self.sweep_origin + 1) if resumed else first)
+                # (after robust=: the predictive density is the likelihood's in force; rung 0 only)
+                if self._predictive_cfg is not None and (temper_cfg is None or r == 0):
+                    eng.pred_begin()
         if resumed:
             for chain in self._host_chains if self._host_model else self.engines:
                 chain.set_sweep_origin(self.sweep_origin)
@@ -863,6 +887,14 @@ class Run:
                     pm.regions = _regions.RegionPosterior.from_engine(eng, self._regions_cfg["ids"])
                 if len(self.posteriors) > 1:
                     self.posterior.regions = _regions.pooled([pm.regions for pm in self.posteriors])
+            if self._predictive_cfg is not None:   # every chain its own; the pooled one merges them exactly
+                nu = 0 if self._robust_cfg is None else self._robust_cfg["nu"]
+                for pm, eng in zip(self.posteriors, self.engines):
+                    pm.predictive = _predictive.PredictiveAccuracy.from_engine(eng, nu)
+                if len(self.posteriors) > 1:
+                    self.posterior.predictive = _predictive.pooled(
+                        [pm.predictive for pm in self.posteriors],
+                        _predictive.base_ivar(self.cube.data, self.variance_cube))
             if self.posterior.count == 0:
                 self.logger.warning("posterior_burn_in=%d: the run stopped at iteration %d, before "
                                     "the first accumulated sweep; run.posterior holds no sample"

@@ -803,6 +803,57 @@ int d3d_robust_get(d3d_ctx *ctx, double *weights, double *weight_mean, int64_t *
  * variance again (d3d_ctx_destroy does it too). */
 int d3d_robust_end(d3d_ctx *ctx);
 
+/* ---- pointwise predictive accuracy: lppd and WAIC per voxel ---------------- */
+/* The reference scores one state of the chain (lib/run.py:407-426 is its chi2 over a window,
+ * lib/run.py:423 the sum d3d_chi2_map maps): that neither scores the posterior nor penalises
+ * flexibility, and under d3d_robust_begin it is the conditional Gaussian's, not the Student-t's.
+ * These entries keep, over the samples of the posterior moments (d3d_post_*), what the widely
+ * applicable information criterion needs of every voxel v:
+ *     lppd_v = log mean_s p(y_v | theta_s)        p_v = var_s log p(y_v | theta_s)
+ * elpd = sum_v (lppd_v - p_v), WAIC = -2 elpd.  With r the residual (SLOT_ERR) and i0 the base
+ * 1/variance (d3d_set_data's SLOT_IVAR; under d3d_robust_begin the copy the weights keep, never the
+ * reweighted slot) log p = k_v + q_sv, k_v constant over the chain:
+ *     Gaussian      q = -1/2 (r r) i0                      k = 1/2 log(i0) - 1/2 log(2 pi)
+ *     Student-t     q = -((nu + 1)/2) log1p((r r) i0 / nu)
+ *                   k = lgamma((nu + 1)/2) - lgamma(nu/2) - 1/2 log(nu pi) + 1/2 log(i0)
+ * (the Student-t marginal: the weight integrated out).  Only q is accumulated, into four cubes:
+ * M = max_s q, S = sum_s exp(q - M), and Welford's mean and M2 of q; with n samples
+ *     lppd_v = (k_v + M_v) + log(S_v / n)         p_v = M2_v / (n - 1)   (NaN for n < 2).
+ * The update of sample number n, in fp64 without contraction (the first sample sets M = q, S = 1):
+ *     d = q - M;  e = exp(-fabs(d));
+ *     S = (d <= 0) ? S + e : S * e + 1;   M = (d <= 0) ? M : q;   then Welford's step of (mean, M2).
+ * No term of S exceeds 1, whatever the order of good and bad samples.  A voxel counts iff i0 != 0,
+ * at masked spaxels too (the set d3d_chi2_map sums); NaN voxels and the pad channel never do.  Off
+ * until begun: a ctx that never calls d3d_pred_begin allocates and launches nothing for it. */
+
+/* Arm (lib/run.py:407-426's likelihood, per voxel): four zeroed cubes of device memory; the moments
+ * start afresh (as d3d_hist_begin) and from then on every sample of theirs -- d3d_post_accumulate, the
+ * sweeps of d3d_post_schedule -- is also one of these, made from the residual of the sample's state
+ * (rebuilt when not valid, pending updates written back first).  The likelihood is the one in force
+ * now: Student-t with d3d_robust_begin's nu when the weights are armed (arm them first), else
+ * Gaussian; a sample after the weights were armed, disarmed or given another nu is D3D_ERR_STATE.
+ * D3D_ERR_STATE: d3d_post_begin not called.  D3D_ERR_UNSUPPORTED: a tile ctx (d3d_set_tile).
+ * D3D_ERR_HIP: the four cubes do not fit; the ctx stays usable.  d3d_post_begin / d3d_post_end free
+ * them, d3d_set_data zeroes them with the moments. */
+int d3d_pred_begin(d3d_ctx *ctx);
+/* Samples accumulated (lib/run.py:407-426 evaluated that many times per voxel): d3d_post_count's
+ * number, 0 when not begun. */
+int d3d_pred_count(d3d_ctx *ctx, int64_t *n);
+/* The raw accumulators of q (lib/run.py:407-426 without its constants) as (D,H,W) arrays, 0 where
+ * the voxel is not counted; chains are pooled from these (M = max M_r, S = sum S_r exp(M_r - M),
+ * Chan's merge of mean and M2).  Any pointer may be NULL. */
+int d3d_pred_get(d3d_ctx *ctx, double *M, double *S, double *mean, double *m2);
+/* maps (H,W,4) = {sum_z lppd_v, sum_z p_v, counted voxels, sum_z (lppd_v - p_v)^2} of every spaxel
+ * (per spectrum, as lib/run.py:407-426 sums its chi2), folded on the device in a fixed order: lane l of
+ * 64 takes the channel pairs l, l + 64, ..., then the lanes fold by halves -- the same bits on every
+ * call.  The standard error of elpd is sqrt(N var_v(lppd_v - p_v)) from the first, second and last. */
+int d3d_pred_maps(d3d_ctx *ctx, double *maps);
+/* lppd_v and p_v as (D,H,W) arrays, NaN where the voxel is not counted (the nansum of
+ * lib/run.py:407-426 skips it); through SLOT_TMP0.  Either pointer may be NULL. */
+int d3d_pred_cubes(d3d_ctx *ctx, double *lppd, double *p);
+/* Free the four cubes; the moments go on (lib/run.py:407-426's chain is untouched throughout). */
+int d3d_pred_end(d3d_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif
