@@ -15,6 +15,8 @@ from . import posterior  # noqa: F401
 from .posterior import PosteriorHistograms, PosteriorMoments  # noqa: F401
 from . import predictive  # noqa: F401
 from .predictive import PredictiveAccuracy  # noqa: F401
+from . import noise  # noqa: F401
+from .noise import NoiseReport  # noqa: F401
 from . import prepare  # noqa: F401
 from .prepare import Prepared, prepare_cube  # noqa: F401
 from . import regions  # noqa: F401

@@ -48,6 +48,7 @@ SYMBOLS = [
     "d3d_temper_set_patch", "d3d_temper_last_patches", "d3d_temper_get_patches",
     "d3d_robust_begin", "d3d_robust_step", "d3d_robust_get", "d3d_robust_end",
     "d3d_pred_begin", "d3d_pred_count", "d3d_pred_get", "d3d_pred_maps", "d3d_pred_cubes", "d3d_pred_end",
+    "d3d_noise_begin", "d3d_noise_step", "d3d_noise_count", "d3d_noise_get", "d3d_noise_end",
 ]
 
 # posterior moments (a table, so that tools/posterior_time.py can load the PARENT commit's library,
@@ -134,6 +135,15 @@ PRED_PROTOTYPES = {
     "d3d_pred_maps": [C.POINTER(C.c_double)],
     "d3d_pred_cubes": [C.POINTER(C.c_double)] * 2,
     "d3d_pred_end": [],
+}
+# variance factors of channel groups (a table for the same reason: tools/noise_time.py)
+NOISE_PROTOTYPES = {
+    "d3d_noise_begin": [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_uint8), C.c_double, C.c_double, C.c_int,
+                        C.c_int64, C.c_int64],
+    "d3d_noise_step": [C.c_int64],
+    "d3d_noise_count": [C.POINTER(C.c_int64)],
+    "d3d_noise_get": [C.POINTER(C.c_double), C.POINTER(C.c_int64)] + [C.POINTER(C.c_double)] * 3,
+    "d3d_noise_end": [],
 }
 POST_CLEAN, POST_CONVOLVED = 1, 2                   # d3d_post_begin: bits of `what`
 POST_PARAMETERS, POST_CLEAN_CUBE, POST_CONVOLVED_CUBE = 0, 1, 2   # d3d_post_get: `which`
@@ -262,7 +272,7 @@ def load():
                            + list(SEARCH_PROTOTYPES.items()) + list(PREP_PROTOTYPES.items())
                            + list(PRIOR_PROTOTYPES.items()) + list(HIST_PROTOTYPES.items())
                            + list(REGION_PROTOTYPES.items()) + list(ROBUST_PROTOTYPES.items())
-                           + list(PRED_PROTOTYPES.items())):
+                           + list(PRED_PROTOTYPES.items()) + list(NOISE_PROTOTYPES.items())):
         getattr(lib, name).argtypes = [ctx_p] + argtypes
     for name, argtypes in TEMPER_PROTOTYPES.items():
         getattr(lib, name).argtypes = argtypes
@@ -1022,6 +1032,57 @@ class Engine(object):
     def robust_end(self):
         """Disarm: the base 1/variance back, bit for bit."""
         _check(self._lib.d3d_robust_end(self._ctx))
+
+    # -- variance factors of channel groups ----------------------------------------------
+    def noise_begin(self, group, n_groups=None, spaxels=None, shape=0., rate=0., every=1, start=0, capacity=1):
+        """Arm the variance factors of the channel groups (include/deconv3d_hip.h: d3d_noise_begin):
+        ``group`` (D,) maps every channel to 0 .. n_groups-1 or -1 (never rescaled), ``spaxels`` (H,W)
+        0/1 the counted spaxels (None: all); after every sweep s >= ``start`` with ``(s - start) %
+        every == 0`` (the run's numbering) the device redraws the factors from the residual and rewrites
+        1/variance; ``capacity`` draws fit the series.  Needs set_data."""
+        group = np.ascontiguousarray(group, dtype=np.int32)
+        if group.shape != (self.shape[0],):
+            raise ValueError("group must have shape (%d,), got %s" % (self.shape[0], group.shape))
+        if n_groups is None:
+            n_groups = int(group.max()) + 1
+        sp = None
+        if spaxels is not None:
+            sp = np.ascontiguousarray(np.asarray(spaxels) != 0, dtype=np.uint8)
+            if sp.shape != tuple(self.shape[1:]):
+                raise ValueError("spaxels must have shape %s, got %s" % (tuple(self.shape[1:]), sp.shape))
+        _check(self._lib.d3d_noise_begin(
+            self._ctx, group.ctypes.data_as(C.POINTER(C.c_int32)), int(n_groups),
+            None if sp is None else sp.ctypes.data_as(C.POINTER(C.c_uint8)), float(shape), float(rate),
+            int(every), int(start), int(capacity)))
+        self._noise_groups = int(n_groups)
+
+    def noise_step(self, sweep_number):
+        """One draw now, as the one after sweep ``sweep_number`` (the run's numbering)."""
+        _check(self._lib.d3d_noise_step(self._ctx, int(sweep_number)))
+
+    def noise_count(self):
+        """Draws in the series."""
+        n = C.c_int64(0)
+        _check(self._lib.d3d_noise_count(self._ctx, C.byref(n)))
+        return n.value
+
+    def noise_get(self):
+        """``(scale (n, G), sweeps (n,), voxels (G,), last_sum (G,), tau (D,))``: the series of scales
+        (NaN: a group of fewer than 2 counted voxels) and the sweep of every row, N_g and Q_g of the last
+        draw, and the factor 1/variance carries in every channel now."""
+        n = self.noise_count()
+        G = self._noise_groups
+        series = np.empty((n, G), dtype=np.float64)
+        sweeps = np.empty((n,), dtype=np.int64)
+        voxels, last = np.empty((G,), dtype=np.float64), np.empty((G,), dtype=np.float64)
+        tau = np.empty((self.shape[0],), dtype=np.float64)
+        _check(self._lib.d3d_noise_get(self._ctx, _dp(series), sweeps.ctypes.data_as(C.POINTER(C.c_int64)),
+                                       _dp(voxels), _dp(last), _dp(tau)))
+        return series, sweeps, voxels, last, tau
+
+    def noise_end(self):
+        """Disarm: the base 1/variance back, bit for bit."""
+        _check(self._lib.d3d_noise_end(self._ctx))
 
     # -- pointwise predictive accuracy --------------------------------------------------
     def pred_begin(self):

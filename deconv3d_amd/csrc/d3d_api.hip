@@ -454,6 +454,7 @@ const OptDesc g_opts[] = {
     {"alt_dir", "D3D_ALT_DIR", &d3d_ctx::alt_dir, OPT_LAUNCH, 0, 1},
     {"stagger", "D3D_STAGGER", &d3d_ctx::stagger, OPT_LAUNCH, 0, 1 << 20},
     {"post_nt", "D3D_POST_NT", &d3d_ctx::post_nt, OPT_LAUNCH, 0, 1},
+    {"noise_timing", "D3D_NOISE_TIMING", &d3d_ctx::noise_timing, OPT_LAUNCH, 0, 1},
 #ifdef D3D_EXPERIMENTS
     // measured-but-not-faster variants of DESIGN.md section 3 (make EXPERIMENTS=1)
     {"mh_chain", "D3D_MH_CHAIN", &d3d_ctx::mh_chain_opt, OPT_MH, 0, 1},
@@ -743,6 +744,10 @@ int d3d_ctx_get_option(d3d_ctx *c, const char *key, long *value) {
         *value = key[5] == 'm' ? c->prep_median_ns : c->prep_stats_ns;
         return D3D_OK;
     }
+    if (!strcmp(key, "noise_sums_ns") || !strcmp(key, "noise_draw_ns") || !strcmp(key, "noise_apply_ns")) {
+        *value = c->noise_ns[key[6] == 's' ? 0 : key[6] == 'd' ? 1 : 2];  // read-only: the last timed d3d_noise_step
+        return D3D_OK;
+    }
     if (!strcmp(key, "device_bytes")) {  // read-only: device memory the library holds, all contexts of the process
         *value = (long)d3dh::dev_bytes.load();
         return D3D_OK;
@@ -1000,6 +1005,7 @@ int d3d_set_data(d3d_ctx *c, const double *data, const double *var, double var_s
                  const uint8_t *mask) {
     NEED(c && data, D3D_ERR_INVALID, "NULL argument");
     NEED(!c->robust.on, D3D_ERR_STATE, "robust weights are armed on the old variance: d3d_robust_end first");
+    NEED(!c->noise.on, D3D_ERR_STATE, "noise scales are armed on the old variance: d3d_noise_end first");
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)c->D * c->HW;
     // mask: user mask AND no NaN anywhere in the spectrum (lib/run.py:153-162)
@@ -1173,6 +1179,8 @@ int d3d_convolve_slots(d3d_ctx *c, int src, int dst) {
          "SLOT_TMP1 is the convolution's intermediate");
     NEED(dst != D3D_SLOT_IVAR || !c->robust.on, D3D_ERR_STATE,
          "SLOT_IVAR is rewritten by the robust weights: d3d_robust_end first");
+    NEED(dst != D3D_SLOT_IVAR || !c->noise.on, D3D_ERR_STATE,
+         "SLOT_IVAR is rewritten by the noise scales: d3d_noise_end first");
     HIP_TRY(hipSetDevice(c->device));
     if (src == D3D_SLOT_ERR)
         if (int rc = flush_pending(c)) return rc;
@@ -1194,6 +1202,8 @@ int d3d_upload_slot(d3d_ctx *c, int slot, const double *cube) {
     NEED(slot >= 0 && slot < D3D_SLOT_COUNT, D3D_ERR_INVALID, "bad slot %d", slot);
     NEED(slot != D3D_SLOT_IVAR || !c->robust.on, D3D_ERR_STATE,
          "SLOT_IVAR is rewritten by the robust weights: d3d_robust_end first");
+    NEED(slot != D3D_SLOT_IVAR || !c->noise.on, D3D_ERR_STATE,
+         "SLOT_IVAR is rewritten by the noise scales: d3d_noise_end first");
     HIP_TRY(hipSetDevice(c->device));
     int rc = upload_cube(c, cube, c->slot[slot]);
     if (rc) return rc;
@@ -1649,6 +1659,8 @@ int d3d_set_tile(d3d_ctx *c, int gy0, int gx0, int Wg, int oy0, int oy1, int ox0
          "the smoothness prior is on (d3d_prior_begin): not on a tile; call d3d_prior_end first");
     NEED(!c->robust.on, D3D_ERR_UNSUPPORTED,
          "robust weights are armed (d3d_robust_begin): not on a tile; call d3d_robust_end first");
+    NEED(!c->noise.on, D3D_ERR_UNSUPPORTED,
+         "noise scales are armed (d3d_noise_begin): not on a tile; call d3d_noise_end first");
     c->gy0 = gy0;
     c->gx0 = gx0;
     c->Wg = Wg;

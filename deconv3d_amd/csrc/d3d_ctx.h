@@ -5,7 +5,7 @@
 // d3d_region.hip: region posteriors; d3d_search.hip: the matched-filter line search; d3d_prep.hip:
 // continuum removal and channel noise of a raw cube; d3d_temper.hip: replica exchange between
 // tempered chains; d3d_robust.hip: the per-voxel weights of a Student-t likelihood; d3d_pred.hip:
-// lppd and WAIC per voxel).
+// lppd and WAIC per voxel; d3d_noise.hip: the variance factors of channel groups).
 // Ownership: every device allocation is a DevBuf, freed by whoever holds it -- the context or group
 // it is a member of (their `delete`), or the call it is a local of.  An optional feature's state is
 // one sub-struct of the context, and its *_end is `c->feature = {}`: buffers freed, fields back at
@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <new>
 #include <string>
 #include <utility>
@@ -400,6 +401,32 @@ struct d3d_ctx {
         int nu = 0;               // the likelihood of every sample: 0 Gaussian, else the armed robust.nu
         DevBuf<double> cube[4];   // M | S | mean | M2, device layout (0 where the voxel is not counted)
     } pred;
+    // noise-scale inference (d3d_noise_*): every group of channels has a variance factor s_g with an
+    // inverse-gamma prior; after the due sweeps k_noise_sums / k_noise_draw redraw tau_g = 1 / s_g from
+    // the residual and k_noise_apply writes SLOT_IVAR = base 1/variance * tau of the channel's group
+    struct Noise {
+        bool on = false;
+        bool was_uniform = false; // ivar_is_uniform before arming (false while armed)
+        bool has_spaxels = false; // a map of counted spaxels was given (else every spaxel)
+        int G = 0, every = 1;
+        int64_t start = 0;        // due: s >= start and (s - start) % every == 0, the run's numbering
+        double shape = 0.0, rate = 0.0;  // the prior InvGamma(shape, rate) of every s_g
+        int64_t capacity = 0, draws = 0; // rows of the series, rows written
+        std::vector<int64_t> sweeps;     // the sweep (the run's numbering) of every row
+        DevBuf<double> i0;        // the base 1/variance d3d_set_data left in SLOT_IVAR, device layout
+        DevBuf<int> group;        // [D] group of every channel, -1: never rescaled
+        DevBuf<uint8_t> spaxels;  // [HW] 0/1 counted spaxels (has_spaxels)
+        DevBuf<double> part_q;    // [NOISE_STREAMS][Dp] partial sums of r^2 i0
+        DevBuf<unsigned> part_n;  // [NOISE_STREAMS][Dp] partial counts
+        DevBuf<double> chan;      // [2][Dp] sum | count of every channel
+        DevBuf<double> tau;       // [Dp] precision factor of every channel (1: not rescaled; the pad channel)
+        DevBuf<double> tau_g;     // [3][G] tau | counted voxels | last sum of every group
+        DevBuf<double> series;    // [capacity][G] the scales s_g = 1 / tau_g (NaN: a group of fewer than 2 voxels)
+    } noise;
+    // option noise_timing = 1: d3d_noise_step records HIP events around its three kernels; their device
+    // time in the last such call (read-only options noise_sums_ns / noise_draw_ns / noise_apply_ns)
+    int noise_timing = 0;
+    long noise_ns[3] = {0, 0, 0};
     // d3d_line_search: device time of the last call's bank build (lines + transpose, or the transpose
     // of a host bank) and of its search kernel, by HIP events (read-only options search_bank_ns /
     // search_kernel_ns)
@@ -486,6 +513,12 @@ int download_device_cube(d3d_ctx *c, const double *src, double *host);
 bool robust_due(const d3d_ctx *c, int s);   // sweep s (the caller's numbering) is followed by a draw
 int robust_after_sweep(d3d_ctx *c, int s);  // the pending layers written back, then the draw, where due
 
+// ---- d3d_noise.hip: the variance factors of channel groups --------------------------------
+// streams of the reduction of k_noise_sums: stream j adds the spaxels j, j + NOISE_STREAMS, ... in turn
+constexpr int NOISE_STREAMS = 1024;
+bool noise_due(const d3d_ctx *c, int s);   // sweep s (the caller's numbering) is followed by a draw
+int noise_after_sweep(d3d_ctx *c, int s);  // the pending layers written back, then the draw, where due
+
 // ---- d3d_pred.hip: pointwise predictive accuracy ------------------------------------------
 // the chain state's residual (made valid, pending layers written back) as sample number
 // c->post.n + 1 of the four accumulators
@@ -541,5 +574,7 @@ int launch_mh_pair(d3d_ctx *c, int ka, uint32_t sweep);
 // the round's parity, the exchange of the accepted pairs' residuals and parameters (three launches,
 // nothing but device memory between them).  The caller has written the pending layers back.
 int temper_round(d3d_temper *t, int64_t round);
+// the context is a member of a live group (d3d_temper_create .. d3d_temper_destroy)
+bool ctx_is_tempered(const d3d_ctx *c);
 
 }  // namespace d3dh

@@ -201,6 +201,8 @@ int d3d_pred_begin(d3d_ctx *c) {
     NEED(!c->tiled, D3D_ERR_UNSUPPORTED,
          "predictive accuracy on a tile: the voxels of its frame belong to other ranks");
     NEED(c->post.on, D3D_ERR_STATE, "posterior moments not begun (d3d_post_begin)");
+    NEED(!c->noise.on, D3D_ERR_UNSUPPORTED,
+         "noise scales are armed (d3d_noise_begin): the density's normaliser 1/2 log i0 would change with every sample");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->pred = {};

@@ -173,6 +173,8 @@ int d3d_robust_begin(d3d_ctx *c, int nu, int every, int64_t start, int64_t accum
     NEED(start >= 0 && accumulate_from >= 0, D3D_ERR_INVALID, "start = %lld / accumulate_from = %lld is negative",
          (long long)start, (long long)accumulate_from);
     NEED(c->have_data, D3D_ERR_STATE, "data not set: the base 1/variance is d3d_set_data's");
+    NEED(!c->noise.on, D3D_ERR_UNSUPPORTED,
+         "noise scales are armed (d3d_noise_begin): both rewrite SLOT_IVAR from the base cube; d3d_noise_end first");
     NEED(!c->tiled, D3D_ERR_UNSUPPORTED,
          "robust weights on a tile: the voxels of its frame belong to other ranks");
     NEED((double)c->D * (double)c->HW < 4294967296.0, D3D_ERR_UNSUPPORTED,

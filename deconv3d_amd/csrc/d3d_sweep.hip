@@ -244,7 +244,9 @@ int end_sweep(d3d_ctx *c, int s, int keep_one_in, SnapQueue &snaps, double *chai
         if (int rc = forward_into(c, c->slot[D3D_SLOT_ERR], true)) return rc;
     }
     // d3d_robust_begin: the weights of a Student-t likelihood, redrawn from the refreshed residual
-    return robust_after_sweep(c, s);
+    if (int rc = robust_after_sweep(c, s)) return rc;
+    // d3d_noise_begin: the variance factors of the channel groups, likewise (the two exclude each other)
+    return noise_after_sweep(c, s);
 }
 
 // option halo_timing: the oldest event pair in flight, reduced into halo_ms / halo_count
@@ -317,7 +319,7 @@ int d3d_mh_sweeps(d3d_ctx *c, int n_sweeps, int first_sweep, int keep_one_in, do
             for (int t = s; t <= last; ++t) {
                 const bool saved = t % keep_one_in == 0 && (chain_out || dlog_out);
                 const bool refresh = c->refresh_every > 0 && t % c->refresh_every == 0;
-                if (saved || refresh || post_due(c, t) || robust_due(c, t)) {
+                if (saved || refresh || post_due(c, t) || robust_due(c, t) || noise_due(c, t)) {
                     last = t;
                     break;
                 }
@@ -429,6 +431,10 @@ int d3d_mh_sweeps_batch(d3d_ctx **ctxs, int n_ctx, int n_sweeps, int first_sweep
         NEED(c->robust.on == L->robust.on && (!c->robust.on || (c->robust.every == L->robust.every && c->robust.start == L->robust.start)),
              D3D_ERR_INVALID,
              "ctx %d: robust weights (d3d_robust_begin) armed, every or start differ from ctx 0's (batched chains "
+             "write their pending residual updates back together)", r);
+        NEED(c->noise.on == L->noise.on && (!c->noise.on || (c->noise.every == L->noise.every && c->noise.start == L->noise.start)),
+             D3D_ERR_INVALID,
+             "ctx %d: noise scales (d3d_noise_begin) armed, every or start differ from ctx 0's (batched chains "
              "write their pending residual updates back together)", r);
     }
     HIP_TRY(hipSetDevice(L->device));

@@ -460,6 +460,21 @@ struct d3d_temper {
 };
 
 namespace {
+// the live groups (d3d_temper_create .. d3d_temper_destroy): ctx_is_tempered looks a context up
+std::mutex live_mutex;
+std::vector<const d3d_temper *> live_groups;
+}  // namespace
+
+namespace d3dh {
+bool ctx_is_tempered(const d3d_ctx *c) {
+    std::lock_guard<std::mutex> lock(live_mutex);
+    for (const d3d_temper *t : live_groups)
+        if (std::find(t->ctxs.begin(), t->ctxs.end(), c) != t->ctxs.end()) return true;
+    return false;
+}
+}  // namespace d3dh
+
+namespace {
 
 // For the duration of a round every context runs on the leader's stream (flush_pending launches
 // on c->stream); on every way out each is back on its own.
@@ -650,6 +665,8 @@ int d3d_temper_create(d3d_temper **out, d3d_ctx **ctxs, int n, const double *bet
         NEED(c->have_taps && c->have_data, D3D_ERR_STATE, "ctx %d: taps/data not set", r);
         NEED(!c->tiled && c->parts.size() == 1 && !c->comm, D3D_ERR_UNSUPPORTED,
              "ctx %d is tiled or partitioned: tempered chains are whole cubes", r);
+        NEED(!c->noise.on, D3D_ERR_UNSUPPORTED,
+             "ctx %d: noise scales are armed (d3d_noise_begin): a rung's variance / beta is not rescaled with them", r);
         NEED(!c->extbuf, D3D_ERR_UNSUPPORTED,
              "ctx %d is driven by d3d_mh_colour_lines: its lines live on the host, tempering swaps device state", r);
         NEED(c->device == L->device && c->D == L->D && c->H == L->H && c->W == L->W && c->fh == L->fh &&
@@ -720,6 +737,10 @@ int d3d_temper_create(d3d_temper **out, d3d_ctx **ctxs, int n, const double *bet
         if (t->done) (void)hipEventDestroy(t->done);
         delete t;
         HIP_TRY(e);
+    }
+    {
+        std::lock_guard<std::mutex> lock(live_mutex);
+        live_groups.push_back(t);
     }
     *out = t;
     return D3D_OK;
@@ -849,6 +870,10 @@ int d3d_temper_destroy(d3d_temper *t) {
     (void)hipSetDevice(t->device);
     (void)hipEventSynchronize(t->done);  // (a round may still be running)
     if (t->done) (void)hipEventDestroy(t->done);
+    {
+        std::lock_guard<std::mutex> lock(live_mutex);
+        live_groups.erase(std::remove(live_groups.begin(), live_groups.end(), t), live_groups.end());
+    }
     delete t;  // every DevBuf of the group
     return D3D_OK;
 }

@@ -37,7 +37,7 @@ from os.path import splitext
 
 import numpy as np
 
-from . import _lib, adapt as _adapt, ensemble, posterior as _posterior, prepare as _prepare, \
+from . import _lib, adapt as _adapt, ensemble, noise as _noise, posterior as _posterior, prepare as _prepare, \
     regions as _regions, \
     predictive as _predictive, prior as _prior, robust as _robust, search as _search, tempering as _tempering
 from .cube import Cube, read_fits
@@ -297,6 +297,26 @@ class Run:
     before the checkpointed sweep from the restored state; the weight mean starts afresh.  Costs
     two more cubes of device memory per chain.
 
+    ``noise=True`` (or ``dict(per='channel'|'cube'|<D integer labels>, every=1, start=0, shape=0.,
+    rate=0., spaxels='all'|'unmasked'|<(H, W) 0/1 map>)``; default ``None``: off, nothing allocated or
+    launched, the chain is bit for bit what it is without the keyword) stops taking the variance as
+    known (lib/run.py:171-200, 407-426): the variance of every voxel of a group ``g`` of channels is
+    ``s_g`` times the given one, ``s_g ~ InvGamma(shape, rate)`` (0, 0: Jeffreys' ``1/s``), and after
+    every sweep ``s >= start`` with ``(s - start) % every == 0`` (the whole run's numbering) the device
+    redraws ``1/s_g ~ Gamma(shape + N_g/2, rate rate + Q_g/2)`` from the residual -- an exact Gibbs
+    step (d3d_noise_*) -- and the sweeps run on the rescaled variance.  ``per`` names the groups
+    (label -1: the channel is never rescaled), ``spaxels`` the spaxels whose voxels are counted.
+    ``run.noise`` is a :class:`deconv3d_amd.noise.NoiseReport` (``scale`` (n, G), ``sweeps``,
+    ``groups``, ``voxels``, ``count``; ``scale_mean``, ``scale_std``, ``quantiles(q)`` over the draws
+    from ``posterior_burn_in`` on, or all; ``channel_scale`` (D,); ``variance(given)``;
+    ``save(prefix)``).  With ``chains=R`` every chain draws its own, ``run.noises[r]``, and
+    ``run.noise`` concatenates the series.  ``run.likelihoods`` and the chi2 map of such a run are those
+    of the conditional Gaussian under the current scales.  ``initial_search=`` and ``prepare=`` run
+    before arming, on the given variance.  A checkpoint records the keywords, ``resume_state=`` refuses
+    a state written with others, and a resumed run re-makes the last due draw and starts a fresh
+    series.  Refused: ``robust=`` and ``predictive=`` (their device code reads the base variance),
+    ``tempering=``, host-evaluated line models.
+
     ``predictive=True`` (or ``dict()``, for future keys; default ``None``: off, nothing allocated or
     launched; needs ``posterior_burn_in``) keeps, on the device, the pointwise predictive density of
     every voxel over the samples of the posterior moments: ``lppd_v = log mean_s p(y_v | theta_s)``
@@ -350,12 +370,13 @@ class Run:
         regions=None,
         robust=None,
         predictive=None,
+        noise=None,
     ):
         prepare_cfg, search_cfg, posterior_burn_in, posterior_every, hist_cfg = self._check_keywords(
             prepare, initial_search, initial_parameters, resume_state, posterior_burn_in,
             posterior_every, posterior_histograms, adapt_sweeps, adapt_window, adapt_target,
             adapt_gain, adapt_scale_range, smoothness, tempering, keep_one_in, write_every,
-            max_iterations, chains, regions, robust, predictive)
+            max_iterations, chains, regions, robust, predictive, noise)
         self._read_inputs(cube, prepare_cfg, mask, variance, device)
         self._read_instrument(instrument)
         self._read_model(model, jump_amplitude, gibbs_apriori_variance, seed, posterior_burn_in)
@@ -379,7 +400,7 @@ class Run:
                         posterior_burn_in, posterior_every, posterior_histograms, adapt_sweeps,
                         adapt_window, adapt_target, adapt_gain, adapt_scale_range, smoothness,
                         tempering, keep_one_in, write_every, max_iterations, chains, regions, robust=None,
-                        predictive=None):
+                        predictive=None, noise=None):
         """The keywords' own checks.  Returns the checked ``prepare=`` and ``initial_search=``,
         the posterior schedule and the checked ``posterior_histograms=``."""
         # (before anything else: no device work yet)
@@ -405,6 +426,9 @@ class Run:
         temper_cfg = self.tempering_cfg = _tempering.check_keywords(tempering)
         self._robust_cfg = _robust.check_keywords(robust)
         _robust.check_run(self._robust_cfg, temper_cfg)
+        # (shapes are checked against the cube's in _read_inputs)
+        self._noise_cfg = _noise.check_keywords(noise)
+        _noise.check_run(self._noise_cfg, temper_cfg, self._robust_cfg, self._predictive_cfg)
         # lib/run.py:112-114
         assert keep_one_in > 0, "keep_one_in= MUST be a positive integer"
         assert write_every > 0, "write_every= MUST be a positive integer"
@@ -469,6 +493,8 @@ class Run:
                              % (cube_height, cube_width, str(mask.shape)))
         mask[np.isnan(np.sum(self.cube.data, 0))] = 0
         self.mask = mask
+        if self._noise_cfg is not None:      # noise=: the groups and the counted spaxels of this cube
+            self._noise_cfg = _noise.resolve(self._noise_cfg, cube_depth, mask)
 
         # ---- variance (lib/run.py:170-200) ---------------------------------
         if variance is not None:
@@ -545,6 +571,9 @@ class Run:
             self._refuse_host_model("smoothness=", "the device knows the prior only for the "
                                     "(a, c, w) of the models it evaluates itself")
         _tempering.check_run(self.tempering_cfg, 1, self._host_model, type(self.model).__name__)
+        if self._noise_cfg is not None and self._host_model:
+            self._refuse_host_model("noise=", "the device redraws the scales only between the sweeps "
+                                    "it runs itself")
         if self._robust_cfg is not None and self._host_model:
             self._refuse_host_model("robust=", "the device redraws the weights only between the sweeps "
                                     "it runs itself")
@@ -726,6 +755,11 @@ class Run:
                     first = cfg["start"] if posterior_burn_in is None else posterior_burn_in + self.sweep_origin
                     eng.robust_begin(cfg["nu"], cfg["every"], cfg["start"],
                                      max(first, self.sweep_origin + 1) if resumed else first)
+                if self._noise_cfg is not None:
+                    # (after initial_search= and prepare= have seen the given variance; the run's numbering)
+                    cfg = self._noise_cfg
+                    eng.noise_begin(cfg["group"], cfg["G"], cfg["map"], cfg["shape"], cfg["rate"], cfg["every"],
+                                    cfg["start"], _noise.capacity(cfg, self.max_iterations, self.sweep_origin))
                 # (after robust=: the predictive density is the likelihood's in force; rung 0 only)
                 if self._predictive_cfg is not None and (temper_cfg is None or r == 0):
                     eng.pred_begin()
@@ -752,6 +786,12 @@ class Run:
             if last is not None:
                 for eng in self.engines:
                     eng.robust_step(last)
+            # noise=, resumed: likewise the scales
+            last = _noise.last_due(self._noise_cfg, self.sweep_origin) \
+                if resumed and self._noise_cfg is not None else None
+            if last is not None:
+                for eng in self.engines:
+                    eng.noise_step(last)
         # tempering=: the group that exchanges the rungs' states on the device.  The round of the
         # exchange after sweep s is (s + sweep_origin) // swap_every: a resumed run continues the
         # numbering, so no uniform is drawn twice.
@@ -906,6 +946,13 @@ class Run:
                             for eng in self.engines]
             self.robust = self.robusts[0] if len(self.robusts) == 1 else \
                 _robust.pooled(self.robusts, self.cube)
+        # noise=: the series of scales (still on the device: fetched on access)
+        self.noises, self.noise = None, None
+        if self._noise_cfg is not None:
+            burn_in = None if posterior_burn_in is None else posterior_burn_in + self.sweep_origin
+            self.noises = [_noise.NoiseReport.from_engine(eng, self._noise_cfg, burn_in, self.sweep_origin + 1)
+                           for eng in self.engines]
+            self.noise = self.noises[0] if len(self.noises) == 1 else _noise.pooled(self.noises)
 
     # ------------------------------------------------------------------------
 
@@ -987,6 +1034,7 @@ class Run:
         _prior.check_resume(state, files, self.smoothness)
         _tempering.check_resume(state, files, self.tempering_cfg)
         _robust.check_resume(state, files, self._robust_cfg)
+        _noise.check_resume(state, files, self._noise_cfg)
         _prepare.check_resume(state, files,
                               None if self.prepared is None else self.prepared.settings)
         # (a checkpoint without a line shape was written by a single-Gaussian run)
@@ -1039,6 +1087,8 @@ class Run:
             state["smoothness_sigmas"] = _prior.keyword_record(self.smoothness)
         if self._robust_cfg is not None:    # (resume_state= checks them; the weights are redrawn)
             state["robust_keywords"] = _robust.keyword_record(self._robust_cfg)
+        if self._noise_cfg is not None:     # (resume_state= checks them; the series starts afresh)
+            state.update(_noise.keyword_record(self._noise_cfg))
         if self.tempering_cfg is not None:  # (resume_state= checks them; counters and labels start afresh)
             state.update(_tempering.state_record(self.tempering_cfg))
         if self._adapt_cfg is not None:     # (resume_state= checks the keywords, restores the rest)
@@ -1141,7 +1191,8 @@ class Run:
     def save(self, name, clobber=False):
         """Write ``<name>_parameters.npy``, ``_chain.npy``, ``_matlab.mat``,
         ``_images.png``, ``_chain.png``, ``_convolved_cube.fits``,
-        ``_clean_cube.fits``, ``_result.npz`` (lib/run.py:742-788)."""
+        ``_clean_cube.fits``, ``_result.npz`` (lib/run.py:742-788); with ``noise=`` also
+        ``_noise.npz``."""
         self.save_parameters_npy("%s_parameters.npy" % name)
         self.save_chain_npy("%s_chain.npy" % name)
         try:
@@ -1157,6 +1208,8 @@ class Run:
             maps = dict(jump_scale=self.jump_scale, acceptance_map=self.acceptance_map)
         np.savez("%s_result.npz" % name, chain=self.chain, likelihoods=self.likelihoods,
                  fsf=self.fsf, lsf=self.lsf if self.lsf is not None else np.zeros(0), **maps)
+        if self.noise is not None:
+            self.noise.save(name)
 
     def save_parameters_npy(self, filepath):
         """lib/run.py:790-797; reusable as ``initial_parameters``."""

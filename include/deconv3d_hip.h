@@ -97,7 +97,7 @@ int d3d_timer_stop(d3d_ctx *ctx, double *elapsed_ms);
  * mh_wide, mh_props, halo_timing, mh_zigzag, mh_nt_ivar -1(auto)|0|1, mh_nt, uniform_ivar, conv_rows,
  * conv_zb, conv_hy, spatial_sep, sep_fuse, spatial_mode, march_hy, zmajor, zmajor_hy,
  * spectral_dense, spectral_blocks, lines_dense, lines_rounds, spatial_nt, xcd_remap, alt_dir, stagger,
- * post_nt; a build with
+ * post_nt, noise_timing; a build with
  * `make EXPERIMENTS=1` adds mh_chain, mh_prio, mh_maxit, mh_flow, mh_pair, spectral_shfl, fuse_lsf, march_pf,
  * march_one, march_stamp.  Unknown key or value out of range: D3D_ERR_INVALID.
  * d3d_ctx_get_option also answers the read-only key "chain_parts": how many of the
@@ -111,6 +111,9 @@ int d3d_timer_stop(d3d_ctx *ctx, double *elapsed_ms);
  * a residual rebuilt by the sweeps), "spectral_path" (the last stand-alone LSF pass of
  * d3d_convolve_slots) and "stage_path" (the last d3d_stage_convolve / d3d_convolve): the
  * D3D_SPATIAL_*, D3D_SPECTRAL_* and D3D_STAGE_* codes below.
+ * "noise_sums_ns" / "noise_draw_ns" / "noise_apply_ns" (read-only): device time of the three kernels of
+ * the last d3d_noise_step made with the option noise_timing = 1 (HIP events between its launches; the
+ * draws of the sweeps are never timed).
  * "device_bytes" (read-only): the bytes of device memory the library holds, over all contexts and
  * tempering groups of the process (the pinned snapshot ring is host memory and not counted). */
 enum {
@@ -853,6 +856,67 @@ int d3d_pred_maps(d3d_ctx *ctx, double *maps);
 int d3d_pred_cubes(d3d_ctx *ctx, double *lppd, double *p);
 /* Free the four cubes; the moments go on (lib/run.py:407-426's chain is untouched throughout). */
 int d3d_pred_end(d3d_ctx *ctx);
+
+/* ---- noise-scale inference: variance factors of channel groups ------------- */
+/* The reference takes the variance as known (lib/run.py:171-200: the given cube, or one constant
+ * from a corner of the data) and sums r^2 / variance over every window (lib/run.py:407-426).  Here
+ * every channel z belongs to a group group[z] in 0 .. G-1 (-1: never rescaled) and the variance of
+ * its voxels is s_g variance_v, s_g ~ InvGamma(shape a0, rate b0) (a0 = b0 = 0: Jeffreys' 1/s).
+ * With i0_v the base 1/variance (what d3d_set_data left in SLOT_IVAR), a voxel counts iff i0_v != 0,
+ * group[z] >= 0 and its spaxel is in the 0/1 map `spaxels` (NULL: every spaxel, masked ones too: the
+ * set d3d_pred_begin counts).  N_g the counted voxels and Q_g = sum (r_v r_v) i0_v over them,
+ *     tau_g = 1 / s_g | r ~ Gamma(shape a0 + N_g / 2, rate b0 + Q_g / 2),
+ * an exact Gibbs step, after which SLOT_IVAR[v] = i0_v tau_group[z] -- always from the base cube,
+ * never in place -- and the sweep kernels run unchanged.  Channels of group -1 and groups with
+ * N_g < 2 keep tau = 1 (the latter are reported as NaN); a rate of exactly 0 keeps the previous tau.
+ *
+ * The sums, in fp64 without contraction, in one fixed order whatever the chip, the launch geometry,
+ * the options and the padding: stream j of 1024 adds, per channel, the counted terms of the spaxels
+ * j, j + 1024, ... (spaxel = y W + x) one after the other from 0; the 1024 partials of a channel are
+ * added in index order from 0; the channels of a group in increasing z from 0.
+ * The draw (Marsaglia and Tsang), alpha = a0 + 0.5 N_g, d = alpha - 1/3, c = 1 / sqrt(9 d): attempt
+ * t = 0 .. 15 takes (u1, u2) = the two uniforms of Philox4x32-10 block 2t and u3 = the first of block
+ * 2t + 1, key d3d_mh_config's seed, counter (g, sweep number, block, 0x4E4F4953), the sweep number in
+ * the run's numbering (d3d_mh_set_sweep_origin);
+ *     x = sqrt(-2 log(u1)) * cos(6.283185307179586 * u2);  v = 1 + c x;  rejected when v <= 0;
+ *     v = v v v;  accepted iff log(u3) < 0.5 x x + d - d v + d log(v);  then gamma = d v,
+ * and gamma = d when no attempt of the 16 is accepted (probability below 1e-20 for alpha >= 1);
+ *     tau_g = gamma / (b0 + 0.5 Q_g).
+ * Off until begun: a ctx that never calls d3d_noise_begin allocates and launches nothing for it. */
+
+/* Arm (lib/run.py:171-200's variance becomes the base of a scaled one; lib/run.py:407-426's sums
+ * run on the scaled one): a copy of SLOT_IVAR as the base cube, 1024 x Dp partials and a series of
+ * `capacity` rows of G scales on the device.  From then on d3d_mh_sweeps / d3d_mh_sweeps_batch redraw
+ * after every sweep s (the run's numbering) with s >= start and (s - start) % every == 0 -- last,
+ * after the snapshot, the posterior sample, the adaptation step and the from-scratch residual, with
+ * the pending residual updates written back first -- on the context's stream, no host round trip.
+ * d3d_variance_is_uniform answers 0 while armed.  d3d_chi2_map and the log ratios are those of the
+ * conditional Gaussian under the current scales.  Calling it again starts afresh from the base cube.
+ * Refused before any allocation -- D3D_ERR_UNSUPPORTED: a tile ctx, d3d_robust_begin or
+ * d3d_pred_begin armed, a member of a tempering group; D3D_ERR_INVALID: G < 1, a label outside
+ * -1 .. G-1, a negative shape, rate or start, every < 1, capacity < 1; D3D_ERR_STATE: no data.
+ * A due draw with the series full fails with D3D_ERR_STATE.  While armed d3d_set_data, d3d_set_tile,
+ * d3d_robust_begin, d3d_pred_begin, d3d_temper_create and writes into SLOT_IVAR are refused. */
+int d3d_noise_begin(d3d_ctx *ctx, const int32_t *group /*D*/, int G, const uint8_t *spaxels /*H*W or NULL*/,
+                    double shape, double rate, int every, int64_t start, int64_t capacity);
+/* One draw now, as the one after sweep `sweep_number` (the run's numbering) would be, from the
+ * residual as it is (lib/run.py:407-426's r; rebuilt when not valid, pending updates written back
+ * first; the variance lib/run.py:171-200 set up is its base), one more row of the series; then
+ * synchronises.  For tests, and for a resumed run, which re-makes the last due draw. */
+int d3d_noise_step(d3d_ctx *ctx, int64_t sweep_number);
+/* Rows of the series so far (draws of the variance factor of lib/run.py:171-200's variance, summed
+ * as lib/run.py:407-426 does). */
+int d3d_noise_count(d3d_ctx *ctx, int64_t *draws);
+/* series (draws, G): the scales s_g = 1 / tau_g of every draw (NaN: N_g < 2); sweeps (draws): the
+ * sweep number of every row; voxels (G) and last_sum (G): N_g and Q_g of the last draw (the sums of
+ * lib/run.py:407-426 per group, on the base variance of lib/run.py:171-200); tau (D): the factor
+ * SLOT_IVAR carries in every channel now.  Any pointer may be NULL. */
+int d3d_noise_get(d3d_ctx *ctx, double *series /*draws*G*/, int64_t *sweeps /*draws*/, double *voxels /*G*/,
+                  double *last_sum /*G*/, double *tau /*D*/);
+/* Disarm: the base cube goes back into SLOT_IVAR bit for bit, d3d_variance_is_uniform answers as
+ * before d3d_noise_begin, the buffers are freed: the chain of lib/run.py:171-200's variance again,
+ * summed as in lib/run.py:407-426 (d3d_ctx_destroy frees them too). */
+int d3d_noise_end(d3d_ctx *ctx);
 
 #ifdef __cplusplus
 }
