@@ -246,6 +246,45 @@ int build_colour_lists(d3d_ctx *c) {
         pt.wide = pt.layers == 1 && c->mh_wide && partitioned && c->Dp == 128 && most > 0 &&
                   most <= c->flow_grid / 4 && c->mh_defer == 1;
         pt.small = pt.layers == 1 && most_wgs < c->flow_grid / 2;
+        // Lattice-row strips (d3d_strips.h): the whole cube of one context, the wave-specialised
+        // deferred kernels, launches that fill the chip (a latency-bound launch gains nothing; a
+        // forced count lifts that condition).  Every colour's list strip-major; within a strip the
+        // order stays what it was above, real spaxels first.
+        pt.strips = 1;
+        pt.soff.clear();
+        pt.sreal.clear();
+        {
+            // (automatic: not the uniform-variance kernels, whose launches are shorter and lose --
+            // profiles/sweep_strips_ab.txt)
+            const bool uv = c->ivar_is_uniform && c->uniform_fast_path;
+            const int want = c->mh_strips_opt >= 2 ? c->mh_strips_opt
+                             : (c->mh_strips_opt == 0 && most_wgs >= c->flow_grid / 2 && !uv) ? MH_STRIPS_AUTO : 1;
+            d3d_strips::Plan plan;
+            if (want >= 2 && !empty && !partitioned && c->mh_defer == 1 && (c->Dp <= d3d::MH_WS_MAX_DP || c->mh_zb) &&
+                !d3dh::mh_part_uses_tables(c, pt) && !c->mh_chain_opt && !c->mh_flow && !c->mh_pair &&
+                d3d_strips::plan(c->H, c->fh, want, &plan)) {
+                pt.strips = plan.S;
+                pt.soff.assign((size_t)ncol * (plan.S + 1), 0);
+                pt.sreal.assign((size_t)ncol * plan.S, 0);
+                for (int col = 0; col < ncol; ++col) {
+                    const int cy = col / c->fw;  // == the local residue (not tiled)
+                    auto key = [&](const int4 &e) {
+                        return 2 * d3d_strips::strip_of_row(plan, d3d_strips::lattice_row(e.x, cy, c->fh)) + (e.z ? 0 : 1);
+                    };
+                    const auto b = list.begin() + pt.off[col], e = list.begin() + pt.off[col + 1];
+                    for (auto it = b; it != e; ++it)
+                        if (key(*it) < 0) return fail(D3D_ERR_HIP, "internal: lattice row outside the strips");
+                    std::stable_sort(b, e, [&](const int4 &p, const int4 &q) { return key(p) < key(q); });
+                    int *so = &pt.soff[(size_t)col * (plan.S + 1)];
+                    for (auto it = b; it != e; ++it) {
+                        const int k = key(*it);
+                        ++so[k / 2 + 1];
+                        if (!(k & 1)) ++pt.sreal[(size_t)col * plan.S + k / 2];
+                    }
+                    for (int s = 0; s < plan.S; ++s) so[s + 1] += so[s];
+                }
+            }
+        }
         // k_mh_chain: whole sweeps of the part in one launch of persistent workgroups, one per
         // lattice slot -- where every slot is resident at once (one workgroup per CU) and a
         // thread can hold its share of the window in registers
@@ -434,6 +473,7 @@ const OptDesc g_opts[] = {
     {"halo_timing", "D3D_HALO_TIMING", &d3d_ctx::halo_timing, OPT_LAUNCH, 0, 1},
     {"mh_zigzag", "D3D_MH_ZIGZAG", &d3d_ctx::mh_zigzag, OPT_MH, 0, 1},
     {"mh_nt_ivar", "D3D_MH_NT_IVAR", &d3d_ctx::mh_nt_ivar_opt, OPT_MH, -1, 1},
+    {"mh_strips", "D3D_MH_STRIPS", &d3d_ctx::mh_strips_opt, OPT_MH, 0, d3d_strips::MAX_STRIPS},
     {"mh_nt", "D3D_MH_NT", &d3d_ctx::mh_nt_opt, OPT_MH, 0, 1024},
     {"uniform_ivar", "D3D_UNIFORM_IVAR", &d3d_ctx::uniform_fast_path, OPT_MH, 0, 1},
     {"conv_rows", "D3D_CONV_ROWS", &d3d_ctx::conv_rows, OPT_LAUNCH, 0, 1},
@@ -649,6 +689,11 @@ int d3d_ctx_destroy(d3d_ctx *c) {
         if (c->snap_done[b]) (void)hipEventDestroy(c->snap_done[b]);
     }
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
+    for (int a = 0; a < d3d_ctx::STRIP_AUX; ++a) {
+        if (c->strip_stream[a]) (void)hipStreamDestroy(c->strip_stream[a]);
+        if (c->strip_join[a]) (void)hipEventDestroy(c->strip_join[a]);
+    }
+    if (c->strip_fork) (void)hipEventDestroy(c->strip_fork);
     for (hipEvent_t e : c->halo_ev) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -755,6 +800,10 @@ int d3d_ctx_get_option(d3d_ctx *c, const char *key, long *value) {
     // read-only, derived: what the context actually runs
     if (!strcmp(key, "mh_nt_ivar_on")) {  // the beyond-the-Infinity-Cache policy of k_mh_ws is in effect
         *value = c->mh_nt_ivar ? 1 : 0;
+        return D3D_OK;
+    }
+    if (!strcmp(key, "mh_strips_on")) {   // lattice-row strips the colour rows of d3d_mh_sweeps run in (0: none)
+        *value = (c->have_data && c->parts.size() == 1 && c->parts[0].strips > 1) ? c->parts[0].strips : 0;
         return D3D_OK;
     }
     if (!strcmp(key, "batch_layers")) {   // pending layers of the last d3d_mh_sweeps_batch: 2 = its joint launches filled the chip

@@ -30,6 +30,7 @@
 
 #include "../../include/deconv3d_hip.h"
 #include "d3d_kernels.h"
+#include "d3d_strips.h"
 
 // The WIDE form of a small colour launch at 128 channels: eleven
 // streaming wavefronts per window instead of four -- one per window row of an 11 x 11 FSF
@@ -43,6 +44,10 @@ constexpr int MH_WIDE_NS = D3D_WIDE_NS;
 // k_mh_chain: at most this many threads per workgroup (three wavefronts per SIMD: 168
 // registers each, of which a thread's column of an 11-row window takes 88)
 constexpr int MH_CHAIN_NT = 768;
+// Lattice-row strips an unpartitioned context's chip-filling colour rows run in when option mh_strips
+// is 0 (1: none).  What profiles/sweep_strips_ab.txt justifies: two pass the project's rule, three gain
+// less, four lose.
+constexpr int MH_STRIPS_AUTO = 2;
 
 namespace d3dh {
 // sets the thread-local message d3d_last_error() returns; returns `code`
@@ -151,6 +156,12 @@ struct d3d_ctx {
         int last_col = -1;                       // its last active colour
         std::vector<int> off;                    // fh*fw + 1: start of each colour's list in spx
         std::vector<int> real;                   // fh*fw: real spaxels of each colour
+        // Lattice-row strips (d3d_strips.h): with strips > 1 every colour's list is
+        // strip-major -- per strip its real spaxels, then its virtual positions -- and the strips of a
+        // colour row run on streams of their own (run_part)
+        int strips = 1;                          // 1: whole colour launches
+        std::vector<int> soff;                   // [fh*fw][strips + 1] start of each strip in the colour's list
+        std::vector<int> sreal;                  // [fh*fw][strips] real spaxels of each strip
     };
     std::vector<Part> parts;
     std::vector<int4> part_rects;  // as given to d3d_set_parts ({y0,y1,x0,x1}; .phase apart)
@@ -176,6 +187,13 @@ struct d3d_ctx {
     DevBuf<double> snap_dev[STREAM_NB]; // [HW*4]: params (HW*3) | dlog (HW)
     double *snap_host[STREAM_NB] = {};  // pinned
     hipEvent_t snap_ready[STREAM_NB] = {}, snap_done[STREAM_NB] = {};
+    // lattice-row strips of a colour row (Part::strips): strip 0 runs on `stream`, strip s > 0 on
+    // strip_stream[s - 1]; one fork and one join per colour row (run_part).  Created on first use.
+    static constexpr int STRIP_AUX = 3;
+    hipStream_t strip_stream[STRIP_AUX] = {};
+    hipEvent_t strip_fork = nullptr, strip_join[STRIP_AUX] = {};
+    int mh_strips_opt = 0;        // option mh_strips: 0 automatic, 1 off, 2..4 that many strips (forced: also
+                                  // where the colour launches do not fill the chip)
     // RCCL communicator of the tiled chain (d3d_comm_init)
     ncclComm_t comm = nullptr;
     int comm_rank = -1, comm_size = 0;
@@ -219,7 +237,8 @@ struct d3d_ctx {
     bool ivar_is_uniform = false; // SLOT_IVAR holds one constant (k_mh_ws<.., true> skips reading it)
     double ivar_uniform = 0.0;
     int uniform_fast_path = 1;    // option uniform_ivar = 0 turns the variant off
-    DevBuf<double> gbuf[4];  // update coefficients [slots][Dp]
+    static constexpr int GBUFS = 8;
+    DevBuf<double> gbuf[GBUFS];  // update coefficients [slots][Dp]; 4 .. 7 only where colour rows run in strips
     // pending layers, oldest first: colour class and G buffer of each update that has
     // not been written into SLOT_ERR yet (k_mh_ws applies up to mh_layers of them)
     int lay_n = 0, lay_cy[3] = {-1, -1, -1}, lay_cx[3] = {-1, -1, -1}, lay_g[3] = {0, 0, 0};
@@ -533,13 +552,17 @@ int pend_free_buf(const d3d_ctx *c);
 void pend_push(d3d_ctx *c, int cy, int cx, int g);
 void fill_mh_args(d3d_ctx *c, d3d::MHArgs &P);
 int launch_mh(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep);
-int launch_mh_zb(d3d_ctx *c, d3d::MHArgs &P, unsigned n_items, uint32_t sweep, int layers);
+// (total: the windows of the whole colour where the launch is one strip of it -- the kernel variant
+// follows the colour, not the strip; 0: the launch is the colour.  item0: the strip's first window
+// in the colour's list)
+int launch_mh_zb(d3d_ctx *c, d3d::MHArgs &P, unsigned n_items, uint32_t sweep, int layers, unsigned total = 0,
+                 unsigned item0 = 0);
 // a colour launch of R chains together (MHArgs::batch; d3d_mh_sweeps_batch), grid = R x windows
 int launch_mh_batch(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep, int layers);
 // what differs between the chains of a joint launch; tables: with the chain's sweep tables
 void fill_chain_args(const d3d_ctx *c, d3d::MHChainArgs &B, bool tables);
 int launch_mh_defer(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep, int layers,
-                    bool wide);
+                    bool wide, unsigned total = 0);
 int flush_pending(d3d_ctx *c);
 // the proposals of sweep `sweep` for every owned spaxel (MHArgs::props), once per sweep
 int ensure_proposals(d3d_ctx *c, uint32_t sweep);

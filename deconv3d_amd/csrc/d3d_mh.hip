@@ -442,20 +442,21 @@ int launch_mh_small(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sw
 // context take different ones.
 template <bool UV>
 int launch_mh_ws(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep, int layers,
-                 bool wide) {
+                 bool wide, unsigned total) {
+    // (a strip of a colour takes the colour's variant: `total` windows decide, `grid` are launched)
+    const bool few = total < (unsigned)c->flow_grid / 2;
     // (the uniform-variance variant also gains from the deeper queue at full size:
     // 35.2 -> 33.3 us per colour; the general one loses, 43.5 -> 49.7)
-    const bool small = UV || grid < (unsigned)c->flow_grid / 2;
+    const bool small = UV || few;
     // (round 4: the parts whose launches do not fill the chip -- run_part hands them the line table)
     if (P.ltab && layers <= 2)
-        return launch_mh_small<UV>(c, P, grid, sweep, wide, layers, !(grid < (unsigned)c->flow_grid / 2));
+        return launch_mh_small<UV>(c, P, grid, sweep, wide, layers, !few);
     // 257 .. 512 channels (round 3): the same kernel with 512 streaming threads (thread <->
     // channel in the tail; the staged G rows, 4 Dp <= 4 x 576, in four registers); the position
     // groups (512 / HL) are those of k_mh_defer<512>, so the chain stays bit-identical to it
     if (c->Dp > 256) {
         bool ntv = false;
-        if constexpr (!UV) ntv = c->mh_nt_ivar && !(grid < (unsigned)c->flow_grid / 2);
-        const bool few = grid < (unsigned)c->flow_grid / 2;
+        if constexpr (!UV) ntv = c->mh_nt_ivar && !few;
         if (layers >= 2) {
             if (few) return launch_mh_ws_um<UV, 4, 2, 4, false, 512>(c, P, grid, sweep);
             // (four positions in flight: 300x300x320 106 us per launch against 111 with two and 141
@@ -633,11 +634,11 @@ int launch_mh_pair(d3d_ctx *c, int ka, uint32_t sweep) {
 // on every block, up to the wave sums of the decision -- and k_mh_zdecide per window: totals,
 // accept, Gibbs draw, G row.  Deferred write-back and pending layers as in k_mh_ws.
 template <bool UV>
-int launch_mh_zb_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned n_items, uint32_t sweep, int layers) {
+int launch_mh_zb_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned n_items, uint32_t sweep, int layers, unsigned total) {
     constexpr int NS = 256;
     const int db = P.z_db;
     const unsigned grid = n_items * (unsigned)P.z_nb;
-    const bool few = grid < (unsigned)c->flow_grid / 2;
+    const bool few = total * (unsigned)P.z_nb < (unsigned)c->flow_grid / 2;
     // (the blocks' kernel takes no decision: the prior is k_mh_zdecide's alone)
     auto go = [&](auto kern, int M) {
         // (LDS of the 256-channel kernel: 35-40 KB, four workgroups per CU)
@@ -678,20 +679,24 @@ int launch_mh_zb_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned n_items, uint32_t 
     return 0;
 }
 
-int launch_mh_zb(d3d_ctx *c, d3d::MHArgs &P, unsigned n_items, uint32_t sweep, int layers) {
+int launch_mh_zb(d3d_ctx *c, d3d::MHArgs &P, unsigned n_items, uint32_t sweep, int layers, unsigned total,
+                 unsigned item0) {
+    if (!total) total = n_items;
     NEED(P.n_lay <= (layers >= 2 ? 2 : 1), D3D_ERR_STATE, "internal: %d pending layers for the z-blocked kernel",
          P.n_lay);
     // the blocks' wave sums of one launch and the lines of its updates.  A launch's windows
     // are distinct points of one colour class's lattice, up to one period outside the cube:
     // allocated once, for the largest launch there can be
     const size_t max_items = (size_t)(c->H / c->fh + 2) * (c->W / c->fw + 2);
-    NEED((size_t)n_items <= max_items, D3D_ERR_STATE, "internal: %u windows in one colour launch", n_items);
+    NEED((size_t)item0 + n_items <= max_items, D3D_ERR_STATE, "internal: %u windows in one colour launch",
+         item0 + n_items);
     if (!c->z_part) HIP_TRY(c->z_part.alloc(max_items * P.z_nb * 32));
     if (!c->z_E) HIP_TRY(c->z_E.alloc((size_t)2 * c->slots * c->Dp));
-    P.z_part = c->z_part;
+    // (a strip's wave sums behind those of the strips before it: they may run at the same time)
+    P.z_part = c->z_part + (size_t)item0 * P.z_nb * 32;
     P.z_E = c->z_E;
-    if (c->ivar_is_uniform && c->uniform_fast_path) return launch_mh_zb_t<true>(c, P, n_items, sweep, layers);
-    return launch_mh_zb_t<false>(c, P, n_items, sweep, layers);
+    if (c->ivar_is_uniform && c->uniform_fast_path) return launch_mh_zb_t<true>(c, P, n_items, sweep, layers, total);
+    return launch_mh_zb_t<false>(c, P, n_items, sweep, layers, total);
 }
 
 // ---- batched chains: R contexts of one geometry, ONE launch per colour class -------------
@@ -743,13 +748,14 @@ int launch_mh_batch(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sw
 }
 
 int launch_mh_defer(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep, int layers,
-                    bool wide) {
+                    bool wide, unsigned total) {
+    if (!total) total = grid;
     // wave-specialised kernel: 256 (or, above 256 channels, 512) streaming threads -- thread
     // <-> channel in the tail, so D <= 512 -- + one prepare wavefront
     if (c->mh_defer == 1 && c->Dp <= d3d::MH_WS_MAX_DP) {
         if (c->ivar_is_uniform && c->uniform_fast_path)
-            return launch_mh_ws<true>(c, P, grid, sweep, layers, wide);
-        return launch_mh_ws<false>(c, P, grid, sweep, layers, wide);
+            return launch_mh_ws<true>(c, P, grid, sweep, layers, wide, total);
+        return launch_mh_ws<false>(c, P, grid, sweep, layers, wide, total);
     }
     switch (c->mh_nt) {
         case 128: return launch_mh_defer_nt<128>(c, P, grid, sweep);

@@ -122,6 +122,78 @@ void push_colour_layer(d3d_ctx *c, int pi, int col, int g, bool wrote_back) {
     c->pend_part = pi;
 }
 
+// The real spaxels of colour `col` through the kernels that write the residual at once (k_mh): the
+// head of the colour's list, or -- a part whose lists are strip-major -- the head of every strip's.
+int launch_real(d3d_ctx *c, const d3d_ctx::Part &pt, int col, const d3d::MHArgs &P, uint32_t sweep) {
+    if (pt.strips <= 1) return launch_mh(c, P, (unsigned)pt.real[col], sweep);
+    for (int s = 0; s < pt.strips; ++s) {
+        const int n = pt.sreal[(size_t)col * pt.strips + s];
+        if (n <= 0) continue;
+        d3d::MHArgs Ps = P;
+        Ps.spx = P.spx + pt.soff[(size_t)col * (pt.strips + 1) + s];
+        if (int rc = launch_mh(c, Ps, (unsigned)n, sweep)) return rc;
+    }
+    return 0;
+}
+
+// Lattice-row strips of a colour row (Part::strips, d3d_strips.h).  The launches of the colours
+// (cy, 0 .. fw - 1) on a strip of lattice rows touch only that strip's bands of the residual, its
+// spaxels and its slot rows of the G buffers, so the strips run on streams of their own, free of each
+// other, between ONE fork before the row's first active colour and ONE join after its last:
+// strip 0 on the context's stream, strip s on strip_stream[s - 1].  On every way out of run_part:
+// joined, the context back on its stream.
+struct StripScope {
+    d3d_ctx *c;
+    hipStream_t main;
+    int S = 1, row = -1;  // strips in flight (1: none), their colour row
+    unsigned locked = 0;  // G buffers of the layers of other colour rows that were pending at the fork
+    int setup() {
+        if (c->strip_fork) return 0;
+        // (G buffers beyond the four of whole launches: up to three locked, three pending, one to write)
+        for (int b = 4; b < d3d_ctx::GBUFS; ++b) {
+            HIP_TRY(c->gbuf[b].alloc((size_t)c->slots * c->Dp));
+            HIP_TRY(hipMemsetAsync(c->gbuf[b], 0, (size_t)c->slots * c->Dp * sizeof(double), main));
+        }
+        HIP_TRY(hipEventCreateWithFlags(&c->strip_fork, hipEventDisableTiming));
+        for (int a = 0; a < d3d_ctx::STRIP_AUX; ++a) {
+            HIP_TRY(hipStreamCreateWithFlags(&c->strip_stream[a], hipStreamNonBlocking));
+            HIP_TRY(hipEventCreateWithFlags(&c->strip_join[a], hipEventDisableTiming));
+        }
+        return 0;
+    }
+    // a G buffer that holds no pending layer and is not locked
+    int free_buf() const {
+        for (int b = 0; b < d3d_ctx::GBUFS; ++b) {
+            bool used = (locked >> b) & 1;
+            for (int j = 0; j < c->lay_n; ++j) used = used || c->lay_g[j] == b;
+            if (!used) return b;
+        }
+        return 0;  // unreachable: at most 3 locked and 3 pending of GBUFS = 8
+    }
+    int fork(int strips, int colour_row, unsigned locked_bufs) {
+        if (int rc = setup()) return rc;
+        locked = locked_bufs;
+        HIP_TRY(hipEventRecord(c->strip_fork, main));
+        for (int a = 0; a + 1 < strips; ++a) HIP_TRY(hipStreamWaitEvent(c->strip_stream[a], c->strip_fork, 0));
+        S = strips;
+        row = colour_row;
+        return 0;
+    }
+    int join() {
+        c->stream = main;
+        const int n = S;
+        S = 1;
+        row = -1;
+        locked = 0;
+        for (int a = 0; a + 1 < n; ++a) {
+            HIP_TRY(hipEventRecord(c->strip_join[a], c->strip_stream[a]));
+            HIP_TRY(hipStreamWaitEvent(main, c->strip_join[a], 0));
+        }
+        return 0;
+    }
+    ~StripScope() { (void)join(); }
+};
+
 // d3d_mh_sweeps_batch: R contexts of one geometry share every colour launch.  The leader -- the
 // context run_part is called on -- carries what they share: work lists, taps, pending layers.
 struct Batch {
@@ -133,7 +205,9 @@ struct Batch {
 
 // Every colour class of one part, for one sweep (lib/run.py:367-519 restricted to
 // the part, in colour order).
-int run_part(d3d_ctx *c, int pi, uint32_t sweep, const Batch *b = nullptr) {
+// strips: the colour rows may run in the part's lattice-row strips (d3d_mh_sweeps; stepping by phase
+// keeps whole colour launches).
+int run_part(d3d_ctx *c, int pi, uint32_t sweep, const Batch *b = nullptr, bool strips_allowed = false) {
     d3d_ctx::Part &pt = c->parts[pi];
     const int ncol = c->fh * c->fw;
     const int layers = b ? b->layers : pt.layers;
@@ -164,6 +238,13 @@ int run_part(d3d_ctx *c, int pi, uint32_t sweep, const Batch *b = nullptr) {
     const int tables = b ? (b->small ? 2 : 0)
                          : (c->mh_props && deferred && (c->mh_zb || (pt.layers == 1 && !c->deep) || small))
                                ? (small ? 2 : 1) : 0;
+    // lattice-row strips: this context alone, the wave-specialised deferred kernels
+    bool strips_ok = strips_allowed && !b && pt.strips > 1 && deferred && !partitioned && c->mh_defer == 1 && tables < 2 &&
+                     (c->mh_zb || c->Dp <= d3d::MH_WS_MAX_DP);
+#ifdef D3D_EXPERIMENTS
+    strips_ok = strips_ok && !c->stampbuf && !pairs;  // (phase stamps are per colour launch)
+#endif
+    StripScope strips = {c, c->stream};
     int ord = 0;  // ordinal of `col` among the active colours
     for (int col = 0; col < ncol; ++col) {
         const int n_real = pt.real[col];
@@ -190,11 +271,47 @@ int run_part(d3d_ctx *c, int pi, uint32_t sweep, const Batch *b = nullptr) {
         d3d::MHArgs P;
         fill_colour_args(c, pt, col, ka, deferred ? layers : 0, tables, P);
         if (!deferred) {
-            if (int rc = launch_mh(c, P, (unsigned)n_real, sweep)) return rc;
+            if (int rc = launch_real(c, pt, col, P, sweep)) return rc;
             continue;
         }
         // real + virtual positions: the windows of this launch tile the domain
         const int n_all = pt.off[col + 1] - pt.off[col];
+        if (strips.S > 1 && col / c->fw != strips.row)  // the next colour row: its bands lie one cube row lower
+            if (int rc = strips.join()) return rc;
+        // The strips part ways at the row's first active colour.  A layer still pending from the row
+        // before lies one cube row higher: the G rows it has under a window come from the neighbouring
+        // strip too.  They were written before the join, and the buffers that hold such layers take no
+        // launch's updates for the rest of this row, so a strip that runs ahead never writes what a
+        // strip behind it still reads.
+        if (strips_ok && strips.S == 1) {
+            int cy, cx;
+            colour_residue(c, col, &cy, &cx);
+            unsigned locked = 0;
+            for (int j = 0; j < c->lay_n; ++j)
+                if (c->lay_cy[j] != cy) locked |= 1u << c->lay_g[j];
+            if (int rc = strips.fork(pt.strips, col / c->fw, locked)) return rc;
+        }
+        if (strips.S > 1) {
+            // the colour's arguments once; every strip its range of the list on its stream.  The kernel
+            // variant follows the colour's windows, not the strip's; a strip of virtual positions
+            // alone still launches (a storing launch needs their write-back).
+            const int g_cur = strips.free_buf();
+            P.Gcur = c->gbuf[g_cur];
+            const int *so = &pt.soff[(size_t)col * (pt.strips + 1)];
+            for (int s = 0; s < pt.strips; ++s) {
+                const int n = so[s + 1] - so[s];
+                if (n <= 0) continue;
+                d3d::MHArgs Ps = P;
+                Ps.spx = P.spx + so[s];
+                c->stream = s ? c->strip_stream[s - 1] : strips.main;
+                const int rc = c->mh_zb ? launch_mh_zb(c, Ps, (unsigned)n, sweep, layers, (unsigned)n_all, (unsigned)so[s])
+                                        : launch_mh_defer(c, Ps, (unsigned)n, sweep, layers, pt.wide, (unsigned)n_all);
+                c->stream = strips.main;
+                if (rc) return rc;
+            }
+            push_colour_layer(c, pi, col, g_cur, P.write_back);
+            continue;
+        }
 #ifdef D3D_EXPERIMENTS
         if (!b && c->stampbuf && c->stamp_next < c->stamp_launches && (size_t)n_all * 8 <= c->stamp_stride)
             P.stamp = c->stampbuf + (c->stamp_next++) * c->stamp_stride;
@@ -214,13 +331,13 @@ int run_part(d3d_ctx *c, int pi, uint32_t sweep, const Batch *b = nullptr) {
         if (rc) return rc;
         for (int r = 0; r < (b ? b->R : 1); ++r) push_colour_layer(cs[r], pi, col, g_cur, P.write_back);
     }
-    return 0;
+    return strips.join();
 }
 
-int run_phase(d3d_ctx *c, int phase, uint32_t sweep) {
+int run_phase(d3d_ctx *c, int phase, uint32_t sweep, bool strips_allowed = false) {
     for (size_t pi = 0; pi < c->parts.size(); ++pi)
         if (c->parts[pi].phase == phase)
-            if (int rc = run_part(c, (int)pi, sweep)) return rc;
+            if (int rc = run_part(c, (int)pi, sweep, nullptr, strips_allowed)) return rc;
     return 0;
 }
 
@@ -337,7 +454,7 @@ int d3d_mh_sweeps(d3d_ctx *c, int n_sweeps, int first_sweep, int keep_one_in, do
 #endif
         {
             for (int ph = 0; ph < n_phases; ++ph) {
-                int rc = run_phase(c, ph, rs);
+                int rc = run_phase(c, ph, rs, true);
                 if (rc) return rc;
                 if (plan_has_entries(c, ph)) {
                     hipEvent_t ev[2] = {nullptr, nullptr};
@@ -535,7 +652,7 @@ int d3d_mh_colour(d3d_ctx *c, int colour, int sweep) {
         if (n_real <= 0) continue;
         d3d::MHArgs P;
         fill_colour_args(c, pt, colour, active_ordinal(pt, colour), 0, 0, P);
-        int rc = launch_mh(c, P, (unsigned)n_real, (uint32_t)sweep + c->sweep_origin);
+        int rc = launch_real(c, pt, colour, P, (uint32_t)sweep + c->sweep_origin);
         if (rc) return rc;
     }
     return D3D_OK;
