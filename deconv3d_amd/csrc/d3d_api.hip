@@ -449,6 +449,75 @@ int prior_kernels_ok(const d3d_ctx *c) {
 
 int d3dh::download_device_cube(d3d_ctx *c, const double *src, double *host) { return download_cube(c, src, host); }
 
+const char *d3dh::setup_differs(const d3d_ctx *c, const d3d_ctx *L) {
+    if (!(c->device == L->device && c->D == L->D && c->H == L->H && c->W == L->W && c->fh == L->fh && c->fw == L->fw))
+        return "device or shape";
+    if (!(c->h_mask == L->h_mask && c->h_fsf == L->h_fsf && c->h_has_lsf == L->h_has_lsf &&
+          (!c->h_has_lsf || c->h_lsf == L->h_lsf) && c->h_thr == L->h_thr))
+        return "mask, FSF or LSF";
+    bool same_line = c->line.K == L->line.K;
+    for (int k = 0; k < d3d::LINE_KMAX; ++k)
+        same_line = same_line && c->line.off[k] == L->line.off[k] && c->line.ratio[k] == L->line.ratio[k];
+    // (and the table: where chains share a launch the leader's device copy serves every one)
+    same_line = same_line && c->line.n == L->line.n && c->line.support == L->line.support && c->h_line_tab == L->h_line_tab;
+    return same_line ? nullptr : "line shape";
+}
+
+// ---- variance rescaling (d3d_ctx::Rescale) ----------------------------------------------------
+d3dh::RescaleName d3dh::rescale_name(const d3d_ctx *c) {
+    static const RescaleName names[] = {{"no rescalers", "none"}, {"robust weights", "robust"}, {"noise scales", "noise"}};
+    return names[c->rescale.who];
+}
+
+int d3dh::rescale_free_for(const d3d_ctx *c, d3d_ctx::Rescale::Who who) {
+    NEED(!c->rescale.who || c->rescale.who == who, D3D_ERR_UNSUPPORTED,
+         "%s are armed (d3d_%s_begin): both rewrite SLOT_IVAR from the base cube; d3d_%s_end first", rescale_name(c).what,
+         rescale_name(c).api, rescale_name(c).api);
+    return 0;
+}
+
+int d3dh::rescale_arm(d3d_ctx *c, d3d_ctx::Rescale::Who who, int every, int64_t start) {
+    if (int rc = rescale_free_for(c, who)) return rc;
+    rescale_disarm(c, who);  // (held already: the base cube first goes back)
+    const size_t bytes = c->cube_elems * sizeof(double);
+    hipError_t e = c->rescale.i0.alloc(c->cube_elems);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(c->rescale.i0, c->slot[D3D_SLOT_IVAR], bytes, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // the context stays usable for the chain of known variance
+        c->rescale = {};
+        return fail(D3D_ERR_HIP, "the base 1/variance (a cube of %zu bytes): %s", bytes, hipGetErrorString(e));
+    }
+    c->rescale.who = who;
+    c->rescale.every = every;
+    c->rescale.start = start;
+    c->rescale.was_uniform = c->ivar_is_uniform;
+    c->ivar_is_uniform = false;  // the slot is read from now on (bit-identical while it holds the base cube)
+    return 0;
+}
+
+void d3dh::rescale_disarm(d3d_ctx *c, d3d_ctx::Rescale::Who who) {
+    if (!who || c->rescale.who != who) return;
+    (void)hipMemcpyAsync(c->slot[D3D_SLOT_IVAR], c->rescale.i0, c->cube_elems * sizeof(double), hipMemcpyDeviceToDevice,
+                         c->stream);
+    (void)hipStreamSynchronize(c->stream);
+    c->ivar_is_uniform = c->rescale.was_uniform;
+    c->rescale = {};
+}
+
+bool d3dh::rescale_due(const d3d_ctx *c, int s) {
+    if (!c->rescale.who) return false;
+    const int64_t rs = (int64_t)s + (int64_t)c->sweep_origin;
+    return rs >= c->rescale.start && (rs - c->rescale.start) % c->rescale.every == 0;
+}
+
+int d3dh::rescale_after_sweep(d3d_ctx *c, int s) {
+    if (!rescale_due(c, s)) return 0;
+    const int64_t rs = (int64_t)s + (int64_t)c->sweep_origin;
+    return c->rescale.who == d3d_ctx::Rescale::ROBUST ? robust_draw(c, rs) : noise_draw(c, rs);
+}
+
 namespace {
 
 // ---- per-context options (d3d_ctx_set_option) -----------------------------------------
@@ -1053,8 +1122,8 @@ static int set_taps_impl(d3d_ctx *c, const double *fsf, const double *lsf, doubl
 int d3d_set_data(d3d_ctx *c, const double *data, const double *var, double var_scalar,
                  const uint8_t *mask) {
     NEED(c && data, D3D_ERR_INVALID, "NULL argument");
-    NEED(!c->robust.on, D3D_ERR_STATE, "robust weights are armed on the old variance: d3d_robust_end first");
-    NEED(!c->noise.on, D3D_ERR_STATE, "noise scales are armed on the old variance: d3d_noise_end first");
+    NEED(!c->rescale.who, D3D_ERR_STATE, "%s are armed on the old variance: d3d_%s_end first",
+         rescale_name(c).what, rescale_name(c).api);
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)c->D * c->HW;
     // mask: user mask AND no NaN anywhere in the spectrum (lib/run.py:153-162)
@@ -1226,10 +1295,8 @@ int d3d_convolve_slots(d3d_ctx *c, int src, int dst) {
     NEED(c->have_taps, D3D_ERR_STATE, "taps not set");
     NEED(dst != D3D_SLOT_TMP1 && src != D3D_SLOT_TMP1, D3D_ERR_INVALID,
          "SLOT_TMP1 is the convolution's intermediate");
-    NEED(dst != D3D_SLOT_IVAR || !c->robust.on, D3D_ERR_STATE,
-         "SLOT_IVAR is rewritten by the robust weights: d3d_robust_end first");
-    NEED(dst != D3D_SLOT_IVAR || !c->noise.on, D3D_ERR_STATE,
-         "SLOT_IVAR is rewritten by the noise scales: d3d_noise_end first");
+    NEED(dst != D3D_SLOT_IVAR || !c->rescale.who, D3D_ERR_STATE, "SLOT_IVAR is rewritten by the %s: d3d_%s_end first",
+         rescale_name(c).what, rescale_name(c).api);
     HIP_TRY(hipSetDevice(c->device));
     if (src == D3D_SLOT_ERR)
         if (int rc = flush_pending(c)) return rc;
@@ -1249,10 +1316,8 @@ int d3d_convolve_slots(d3d_ctx *c, int src, int dst) {
 int d3d_upload_slot(d3d_ctx *c, int slot, const double *cube) {
     NEED(c && cube, D3D_ERR_INVALID, "NULL argument");
     NEED(slot >= 0 && slot < D3D_SLOT_COUNT, D3D_ERR_INVALID, "bad slot %d", slot);
-    NEED(slot != D3D_SLOT_IVAR || !c->robust.on, D3D_ERR_STATE,
-         "SLOT_IVAR is rewritten by the robust weights: d3d_robust_end first");
-    NEED(slot != D3D_SLOT_IVAR || !c->noise.on, D3D_ERR_STATE,
-         "SLOT_IVAR is rewritten by the noise scales: d3d_noise_end first");
+    NEED(slot != D3D_SLOT_IVAR || !c->rescale.who, D3D_ERR_STATE, "SLOT_IVAR is rewritten by the %s: d3d_%s_end first",
+         rescale_name(c).what, rescale_name(c).api);
     HIP_TRY(hipSetDevice(c->device));
     int rc = upload_cube(c, cube, c->slot[slot]);
     if (rc) return rc;
@@ -1706,10 +1771,8 @@ int d3d_set_tile(d3d_ctx *c, int gy0, int gx0, int Wg, int oy0, int oy1, int ox0
          "per-spaxel jump scales are on (d3d_adapt_begin): not on a tile; call d3d_adapt_end first");
     NEED(!c->prior.on, D3D_ERR_UNSUPPORTED,
          "the smoothness prior is on (d3d_prior_begin): not on a tile; call d3d_prior_end first");
-    NEED(!c->robust.on, D3D_ERR_UNSUPPORTED,
-         "robust weights are armed (d3d_robust_begin): not on a tile; call d3d_robust_end first");
-    NEED(!c->noise.on, D3D_ERR_UNSUPPORTED,
-         "noise scales are armed (d3d_noise_begin): not on a tile; call d3d_noise_end first");
+    NEED(!c->rescale.who, D3D_ERR_UNSUPPORTED, "%s are armed (d3d_%s_begin): not on a tile; call d3d_%s_end first",
+         rescale_name(c).what, rescale_name(c).api, rescale_name(c).api);
     c->gy0 = gy0;
     c->gx0 = gx0;
     c->Wg = Wg;

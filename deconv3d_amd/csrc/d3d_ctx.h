@@ -9,7 +9,9 @@
 // Ownership: every device allocation is a DevBuf, freed by whoever holds it -- the context or group
 // it is a member of (their `delete`), or the call it is a local of.  An optional feature's state is
 // one sub-struct of the context, and its *_end is `c->feature = {}`: buffers freed, fields back at
-// their defaults.  A DevBuf never synchronises: whoever frees one has drained the stream that uses it.
+// their defaults (Post, Hist, Regions, Adapt, Prior, Robust, Pred, Noise; and Rescale, which whichever of
+// Robust and Noise rewrites SLOT_IVAR holds: rescale_disarm is its `c->rescale = {}`, the base cube put
+// back first).  A DevBuf never synchronises: whoever frees one has drained the stream that uses it.
 // Not installed: the public interface is include/deconv3d_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -400,16 +402,22 @@ struct d3d_ctx {
         double lam[3] = {0.0, 0.0, 0.0};
         DevBuf<double> part;      // [PRIOR_BLOCKS + 1][4] block partials | totals of k_prior_energy
     } prior;
+    // variance rescaling (d3dh::rescale_*): at most one feature -- the holder -- rewrites SLOT_IVAR from the
+    // base 1/variance after the due sweeps.  Every other writer of SLOT_IVAR refuses while it is held.
+    struct Rescale {
+        enum Who { NONE, ROBUST, NOISE } who = NONE;  // the holder (d3d_robust_begin / d3d_noise_begin)
+        bool was_uniform = false; // ivar_is_uniform before arming (false while armed)
+        int every = 1;
+        int64_t start = 0;        // due: s >= start and (s - start) % every == 0, the run's numbering
+        DevBuf<double> i0;        // the base 1/variance d3d_set_data left in SLOT_IVAR, device layout
+    } rescale;
     // Student-t likelihood (d3d_robust_*): after the due sweeps k_robust_step redraws one weight per
-    // voxel from the residual and writes SLOT_IVAR = weight * base 1/variance
+    // voxel from the residual and writes SLOT_IVAR = weight * base 1/variance (holds `rescale`)
     struct Robust {
         bool on = false;
-        bool was_uniform = false; // ivar_is_uniform before arming (false while armed)
-        int nu = 0, every = 1;
-        int64_t start = 0;        // due: s >= start and (s - start) % every == 0, the run's numbering
+        int nu = 0;
         int64_t accum_from = 0;   // draws of the sweeps from this one on enter the weight mean
         int64_t count = 0;        // draws in the weight mean
-        DevBuf<double> i0;        // the base 1/variance d3d_set_data left in SLOT_IVAR, device layout
         DevBuf<double> mean;      // running mean of the weights, device layout (0 where i0 == 0)
     } robust;
     // pointwise predictive accuracy (d3d_pred_*): per voxel and per sample of the moments the
@@ -423,16 +431,14 @@ struct d3d_ctx {
     // noise-scale inference (d3d_noise_*): every group of channels has a variance factor s_g with an
     // inverse-gamma prior; after the due sweeps k_noise_sums / k_noise_draw redraw tau_g = 1 / s_g from
     // the residual and k_noise_apply writes SLOT_IVAR = base 1/variance * tau of the channel's group
+    // (holds `rescale`)
     struct Noise {
         bool on = false;
-        bool was_uniform = false; // ivar_is_uniform before arming (false while armed)
         bool has_spaxels = false; // a map of counted spaxels was given (else every spaxel)
-        int G = 0, every = 1;
-        int64_t start = 0;        // due: s >= start and (s - start) % every == 0, the run's numbering
+        int G = 0;
         double shape = 0.0, rate = 0.0;  // the prior InvGamma(shape, rate) of every s_g
         int64_t capacity = 0, draws = 0; // rows of the series, rows written
         std::vector<int64_t> sweeps;     // the sweep (the run's numbering) of every row
-        DevBuf<double> i0;        // the base 1/variance d3d_set_data left in SLOT_IVAR, device layout
         DevBuf<int> group;        // [D] group of every channel, -1: never rescaled
         DevBuf<uint8_t> spaxels;  // [HW] 0/1 counted spaxels (has_spaxels)
         DevBuf<double> part_q;    // [NOISE_STREAMS][Dp] partial sums of r^2 i0
@@ -528,15 +534,42 @@ int halo_exchange(d3d_ctx *c, int plan);
 // a cube in the device layout into a host array (D,H,W), synchronously (through c->stage)
 int download_device_cube(d3d_ctx *c, const double *src, double *host);
 
+// `c` and `L` can share a launch or trade state: same device and shape, same mask, FSF and LSF, same line
+// shape and table.  NULL, or what differs (d3d_mh_sweeps_batch, d3d_temper_create).
+const char *setup_differs(const d3d_ctx *c, const d3d_ctx *L);
+
+// ---- variance rescaling (d3d_ctx::Rescale; defined in d3d_api.hip) ------------------------------
+// the wording of a refusal: what the context's holder is called, and its <api> in d3d_<api>_begin / _end
+struct RescaleName {
+    const char *what, *api;
+};
+RescaleName rescale_name(const d3d_ctx *c);
+// 0, or the refusal of `who`: another feature holds the rescale (d3d_*_begin, ahead of their other checks)
+int rescale_free_for(const d3d_ctx *c, d3d_ctx::Rescale::Who who);
+// `who` takes the rescale (the caller has drained the stream): the base cube copied out of SLOT_IVAR and
+// waited for, ivar_is_uniform saved and cleared.  Refused while another feature holds it; where `who`
+// holds it already, the base cube first goes back.  On failure nothing is held and the context stays usable.
+int rescale_arm(d3d_ctx *c, d3d_ctx::Rescale::Who who, int every, int64_t start);
+// where `who` holds it: the base cube back into the slot (on the context's stream, waited for),
+// ivar_is_uniform restored, c->rescale = {}.  Nothing otherwise.
+void rescale_disarm(d3d_ctx *c, d3d_ctx::Rescale::Who who);
+bool rescale_due(const d3d_ctx *c, int s);   // sweep s (the caller's numbering) is followed by the holder's draw
+int rescale_after_sweep(d3d_ctx *c, int s);  // where due: the pending layers written back, then the draw
+// the base 1/variance: the saved cube while the rescale is held, else SLOT_IVAR
+inline const double *rescale_base(const d3d_ctx *c) {
+    return c->rescale.who ? c->rescale.i0.get() : c->slot[D3D_SLOT_IVAR].get();
+}
+
 // ---- d3d_robust.hip: the weights of a Student-t likelihood --------------------------------
-bool robust_due(const d3d_ctx *c, int s);   // sweep s (the caller's numbering) is followed by a draw
-int robust_after_sweep(d3d_ctx *c, int s);  // the pending layers written back, then the draw, where due
+// the draw of sweep `rs` (the run's numbering) from the residual, its pending layers written back first
+int robust_draw(d3d_ctx *c, int64_t rs);
 
 // ---- d3d_noise.hip: the variance factors of channel groups --------------------------------
 // streams of the reduction of k_noise_sums: stream j adds the spaxels j, j + NOISE_STREAMS, ... in turn
 constexpr int NOISE_STREAMS = 1024;
-bool noise_due(const d3d_ctx *c, int s);   // sweep s (the caller's numbering) is followed by a draw
-int noise_after_sweep(d3d_ctx *c, int s);  // the pending layers written back, then the draw, where due
+// the draw of sweep `rs` likewise (ev: four events recorded around the launches, or NULL -- option
+// noise_timing of d3d_noise_step)
+int noise_draw(d3d_ctx *c, int64_t rs, hipEvent_t *ev = nullptr);
 
 // ---- d3d_pred.hip: pointwise predictive accuracy ------------------------------------------
 // the chain state's residual (made valid, pending layers written back) as sample number

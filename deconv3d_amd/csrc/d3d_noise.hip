@@ -206,12 +206,6 @@ static __global__ __launch_bounds__(256) void k_noise_apply(NoiseArgs A) {
 
 namespace d3dh {
 
-bool noise_due(const d3d_ctx *c, int s) {
-    if (!c->noise.on) return false;
-    const int64_t rs = (int64_t)s + (int64_t)c->sweep_origin;
-    return rs >= c->noise.start && (rs - c->noise.start) % c->noise.every == 0;
-}
-
 static void noise_args(const d3d_ctx *c, int64_t rs, d3d::NoiseArgs &A) {
     A.HW = c->HW;
     A.HL = c->HL;
@@ -226,7 +220,7 @@ static void noise_args(const d3d_ctx *c, int64_t rs, d3d::NoiseArgs &A) {
     A.rate = c->noise.rate;
     A.row = (long)c->noise.draws;
     A.err = c->slot[D3D_SLOT_ERR];
-    A.i0 = c->noise.i0;
+    A.i0 = rescale_base(c);
     A.spaxels = c->noise.has_spaxels ? c->noise.spaxels.get() : nullptr;
     A.group = c->noise.group;
     A.part_q = c->noise.part_q;
@@ -238,10 +232,8 @@ static void noise_args(const d3d_ctx *c, int64_t rs, d3d::NoiseArgs &A) {
     A.ivar = c->slot[D3D_SLOT_IVAR];
 }
 
-// the draw of sweep `rs` (the run's numbering) from the residual as it is: four launches on the
-// context's stream, nothing but device memory between them
-// (ev: four events recorded around the launches, or NULL -- option noise_timing of d3d_noise_step)
-static int noise_draw(d3d_ctx *c, int64_t rs, hipEvent_t *ev = nullptr) {
+// four launches on the context's stream, nothing but device memory between them
+int noise_draw(d3d_ctx *c, int64_t rs, hipEvent_t *ev) {
     NEED(c->noise.draws < c->noise.capacity, D3D_ERR_STATE,
          "the series of noise scales is full (%lld draws): d3d_noise_begin with a larger capacity",
          (long long)c->noise.capacity);
@@ -266,19 +258,9 @@ static int noise_draw(d3d_ctx *c, int64_t rs, hipEvent_t *ev = nullptr) {
     return 0;
 }
 
-int noise_after_sweep(d3d_ctx *c, int s) {
-    if (!noise_due(c, s)) return 0;
-    return noise_draw(c, (int64_t)s + (int64_t)c->sweep_origin);
-}
-
-// the base cube back into the slot (on the context's stream, waited for), the buffers freed
+// the base cube back into the slot, the buffers freed (the caller has drained the stream)
 static void noise_free(d3d_ctx *c) {
-    if (c->noise.on) {
-        (void)hipMemcpyAsync(c->slot[D3D_SLOT_IVAR], c->noise.i0, c->cube_elems * sizeof(double),
-                             hipMemcpyDeviceToDevice, c->stream);
-        (void)hipStreamSynchronize(c->stream);
-        c->ivar_is_uniform = c->noise.was_uniform;
-    }
+    rescale_disarm(c, d3d_ctx::Rescale::NOISE);
     c->noise = {};
 }
 
@@ -293,9 +275,7 @@ int d3d_noise_begin(d3d_ctx *c, const int32_t *group, int G, const uint8_t *spax
     NEED(c && group, D3D_ERR_INVALID, "NULL argument");
     NEED(!c->tiled, D3D_ERR_UNSUPPORTED,
          "noise scales on a tile: the sums of a channel run over the voxels of every rank");
-    NEED(!c->robust.on, D3D_ERR_UNSUPPORTED,
-         "robust weights are armed (d3d_robust_begin): both rewrite SLOT_IVAR from the base cube; "
-         "d3d_robust_end first");
+    if (int rc = rescale_free_for(c, d3d_ctx::Rescale::NOISE)) return rc;
     NEED(!c->pred.on, D3D_ERR_UNSUPPORTED,
          "predictive accuracy is armed (d3d_pred_begin): its normaliser 1/2 log i0 would change with every "
          "sample; d3d_pred_end first");
@@ -313,13 +293,12 @@ int d3d_noise_begin(d3d_ctx *c, const int32_t *group, int G, const uint8_t *spax
     NEED(c->have_data, D3D_ERR_STATE, "data not set: the base 1/variance is d3d_set_data's");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    noise_free(c);  // (armed already: the base cube first goes back)
+    c->noise = {};  // (armed already: rescale_arm first puts the base cube back)
+    if (int rc = rescale_arm(c, d3d_ctx::Rescale::NOISE, every, start)) return rc;
     d3d_ctx::Noise &N = c->noise;
-    const size_t bytes = c->cube_elems * sizeof(double);
     const size_t Dp = (size_t)c->Dp, S = (size_t)NOISE_STREAMS;
     std::vector<double> one(std::max(Dp, (size_t)3 * G), 0.0);
-    hipError_t e = N.i0.alloc(c->cube_elems);
-    if (e == hipSuccess) e = N.group.alloc((size_t)c->D);
+    hipError_t e = N.group.alloc((size_t)c->D);
     if (e == hipSuccess && spaxels) e = N.spaxels.alloc((size_t)c->HW);
     if (e == hipSuccess) e = N.part_q.alloc(S * Dp);
     if (e == hipSuccess) e = N.part_n.alloc(S * Dp);
@@ -327,8 +306,6 @@ int d3d_noise_begin(d3d_ctx *c, const int32_t *group, int G, const uint8_t *spax
     if (e == hipSuccess) e = N.tau.alloc(Dp);
     if (e == hipSuccess) e = N.tau_g.alloc((size_t)3 * G);
     if (e == hipSuccess) e = N.series.alloc((size_t)capacity * G);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(N.i0, c->slot[D3D_SLOT_IVAR], bytes, hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(N.group, group, (size_t)c->D * sizeof(int), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && spaxels)
         e = hipMemcpyAsync(N.spaxels, spaxels, (size_t)c->HW, hipMemcpyHostToDevice, c->stream);
@@ -342,20 +319,15 @@ int d3d_noise_begin(d3d_ctx *c, const int32_t *group, int G, const uint8_t *spax
     if (e != hipSuccess) {
         (void)hipGetLastError();  // the context stays usable for the chain of known variance
         noise_free(c);
-        return fail(D3D_ERR_HIP, "noise scales (a cube of %zu bytes, %d x %zu partials, %lld x %d scales): %s", bytes,
-                    NOISE_STREAMS, Dp, (long long)capacity, G, hipGetErrorString(e));
+        return fail(D3D_ERR_HIP, "noise scales (%d x %zu partials, %lld x %d scales): %s", NOISE_STREAMS, Dp,
+                    (long long)capacity, G, hipGetErrorString(e));
     }
     N.on = true;
     N.has_spaxels = spaxels != nullptr;
     N.G = G;
-    N.every = every;
-    N.start = start;
     N.shape = shape;
     N.rate = rate;
     N.capacity = capacity;
-    N.draws = 0;
-    N.was_uniform = c->ivar_is_uniform;
-    c->ivar_is_uniform = false;  // the slot is read from now on (bit-identical while it holds the base cube)
     return D3D_OK;
 }
 

@@ -18,7 +18,7 @@ struct PredArgs {
     double n;               // number of this sample, counted from 1 (extraction: the samples held)
     double nu, half;        // Student-t: degrees of freedom and (nu + 1) / 2
     double kc;              // extraction: the part of k_v that no voxel changes
-    const double *err, *i0; // residual; base 1/variance (robust.i0 while the weights are armed)
+    const double *err, *i0; // residual; base 1/variance (rescale_base)
     double *M, *S, *mean, *m2;
 };
 
@@ -158,7 +158,7 @@ static d3d::PredArgs pred_args(const d3d_ctx *c) {
     A.kc = c->pred.nu ? std::lgamma(A.half) - std::lgamma(0.5 * A.nu) - 0.5 * std::log(A.nu * M_PI)
                       : -0.5 * std::log(2.0 * M_PI);
     A.err = c->slot[D3D_SLOT_ERR];
-    A.i0 = c->robust.on ? c->robust.i0 : c->slot[D3D_SLOT_IVAR];
+    A.i0 = rescale_base(c);
     A.M = c->pred.cube[0];
     A.S = c->pred.cube[1];
     A.mean = c->pred.cube[2];

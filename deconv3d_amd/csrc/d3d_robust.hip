@@ -108,14 +108,7 @@ static __global__ __launch_bounds__(256) void k_robust_view(long n, const double
 
 namespace d3dh {
 
-bool robust_due(const d3d_ctx *c, int s) {
-    if (!c->robust.on) return false;
-    const int64_t rs = (int64_t)s + (int64_t)c->sweep_origin;
-    return rs >= c->robust.start && (rs - c->robust.start) % c->robust.every == 0;
-}
-
-// the draw of sweep `rs` (the run's numbering) from the residual as it is
-static int robust_draw(d3d_ctx *c, int64_t rs) {
+int robust_draw(d3d_ctx *c, int64_t rs) {
     if (int rc = flush_pending(c)) return rc;  // the residual is stored only every second colour
     d3d::RobustArgs A;
     A.HW = c->HW;
@@ -130,7 +123,7 @@ static int robust_draw(d3d_ctx *c, int64_t rs) {
     const bool acc = rs >= c->robust.accum_from;
     A.n = acc ? (double)(c->robust.count + 1) : 0.0;
     A.err = c->slot[D3D_SLOT_ERR];
-    A.i0 = c->robust.i0;
+    A.i0 = rescale_base(c);
     A.ivar = c->slot[D3D_SLOT_IVAR];
     A.mean = c->robust.mean;
     const dim3 grid((unsigned)((c->HW + 3) / 4));
@@ -143,19 +136,9 @@ static int robust_draw(d3d_ctx *c, int64_t rs) {
     return 0;
 }
 
-int robust_after_sweep(d3d_ctx *c, int s) {
-    if (!robust_due(c, s)) return 0;
-    return robust_draw(c, (int64_t)s + (int64_t)c->sweep_origin);
-}
-
-// the base cube back into the slot (on the context's stream, waited for), the buffers freed
+// the base cube back into the slot, the buffers freed (the caller has drained the stream)
 static void robust_free(d3d_ctx *c) {
-    if (c->robust.on) {
-        (void)hipMemcpyAsync(c->slot[D3D_SLOT_IVAR], c->robust.i0, c->cube_elems * sizeof(double),
-                             hipMemcpyDeviceToDevice, c->stream);
-        (void)hipStreamSynchronize(c->stream);
-        c->ivar_is_uniform = c->robust.was_uniform;
-    }
+    rescale_disarm(c, d3d_ctx::Rescale::ROBUST);
     c->robust = {};
 }
 
@@ -173,35 +156,27 @@ int d3d_robust_begin(d3d_ctx *c, int nu, int every, int64_t start, int64_t accum
     NEED(start >= 0 && accumulate_from >= 0, D3D_ERR_INVALID, "start = %lld / accumulate_from = %lld is negative",
          (long long)start, (long long)accumulate_from);
     NEED(c->have_data, D3D_ERR_STATE, "data not set: the base 1/variance is d3d_set_data's");
-    NEED(!c->noise.on, D3D_ERR_UNSUPPORTED,
-         "noise scales are armed (d3d_noise_begin): both rewrite SLOT_IVAR from the base cube; d3d_noise_end first");
+    if (int rc = rescale_free_for(c, d3d_ctx::Rescale::ROBUST)) return rc;
     NEED(!c->tiled, D3D_ERR_UNSUPPORTED,
          "robust weights on a tile: the voxels of its frame belong to other ranks");
     NEED((double)c->D * (double)c->HW < 4294967296.0, D3D_ERR_UNSUPPORTED,
          "robust weights key their random numbers by a 32-bit voxel index: D*H*W must be < 2^32");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    robust_free(c);  // (armed already: the base cube first goes back)
+    c->robust = {};  // (armed already: rescale_arm first puts the base cube back)
+    if (int rc = rescale_arm(c, d3d_ctx::Rescale::ROBUST, every, start)) return rc;
     const size_t bytes = c->cube_elems * sizeof(double);
-    hipError_t e = c->robust.i0.alloc(c->cube_elems);
-    if (e == hipSuccess) e = c->robust.mean.alloc(c->cube_elems);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(c->robust.i0, c->slot[D3D_SLOT_IVAR], bytes, hipMemcpyDeviceToDevice, c->stream);
+    hipError_t e = c->robust.mean.alloc(c->cube_elems);
     if (e == hipSuccess) e = hipMemsetAsync(c->robust.mean, 0, bytes, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         (void)hipGetLastError();  // the context stays usable for the Gaussian chain
         robust_free(c);
-        return fail(D3D_ERR_HIP, "robust weights (2 cubes of %zu bytes): %s", bytes, hipGetErrorString(e));
+        return fail(D3D_ERR_HIP, "robust weights (a cube of %zu bytes): %s", bytes, hipGetErrorString(e));
     }
     c->robust.on = true;
     c->robust.nu = nu;
-    c->robust.every = every;
-    c->robust.start = start;
     c->robust.accum_from = accumulate_from;
-    c->robust.count = 0;
-    c->robust.was_uniform = c->ivar_is_uniform;
-    c->ivar_is_uniform = false;  // the slot is read from now on (bit-identical while it holds the base cube)
     return D3D_OK;
 }
 
@@ -230,7 +205,7 @@ int d3d_robust_get(d3d_ctx *c, double *weights, double *weight_mean, int64_t *co
         double *const out = k == 0 ? weights : weight_mean;
         if (!out) continue;
         hipLaunchKernelGGL(d3d::k_robust_view, dim3(grid), dim3(256), 0, c->stream, (long)c->cube_elems,
-                           (const double *)(k == 0 ? c->slot[D3D_SLOT_IVAR] : c->robust.mean), (const double *)c->robust.i0,
+                           (const double *)(k == 0 ? c->slot[D3D_SLOT_IVAR] : c->robust.mean), rescale_base(c),
                            k == 0 ? 1 : 0, scratch);
         HIP_TRY(hipGetLastError());
         if (int rc = download_device_cube(c, scratch, out)) return rc;

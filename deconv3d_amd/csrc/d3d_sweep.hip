@@ -360,10 +360,9 @@ int end_sweep(d3d_ctx *c, int s, int keep_one_in, SnapQueue &snaps, double *chai
         }
         if (int rc = forward_into(c, c->slot[D3D_SLOT_ERR], true)) return rc;
     }
-    // d3d_robust_begin: the weights of a Student-t likelihood, redrawn from the refreshed residual
-    if (int rc = robust_after_sweep(c, s)) return rc;
-    // d3d_noise_begin: the variance factors of the channel groups, likewise (the two exclude each other)
-    return noise_after_sweep(c, s);
+    // d3d_robust_begin / d3d_noise_begin: the weights of a Student-t likelihood, or the variance factors
+    // of the channel groups, redrawn from the refreshed residual
+    return rescale_after_sweep(c, s);
 }
 
 // option halo_timing: the oldest event pair in flight, reduced into halo_ms / halo_count
@@ -436,7 +435,7 @@ int d3d_mh_sweeps(d3d_ctx *c, int n_sweeps, int first_sweep, int keep_one_in, do
             for (int t = s; t <= last; ++t) {
                 const bool saved = t % keep_one_in == 0 && (chain_out || dlog_out);
                 const bool refresh = c->refresh_every > 0 && t % c->refresh_every == 0;
-                if (saved || refresh || post_due(c, t) || robust_due(c, t) || noise_due(c, t)) {
+                if (saved || refresh || post_due(c, t) || rescale_due(c, t)) {
                     last = t;
                     break;
                 }
@@ -518,24 +517,13 @@ int d3d_mh_sweeps_batch(d3d_ctx **ctxs, int n_ctx, int n_sweeps, int first_sweep
              "ctx %d is tiled or partitioned: batched chains are whole cubes", r);
         NEED(c->mh_defer == 1 && c->Dp <= 256 && !c->deep, D3D_ERR_UNSUPPORTED,
              "ctx %d: batched chains take cubes up to 256 channels with the default write-back scheme", r);
-        NEED(c->device == L->device && c->D == L->D && c->H == L->H && c->W == L->W && c->fh == L->fh &&
-                 c->fw == L->fw,
-             D3D_ERR_INVALID, "ctx %d: another device or shape than ctx 0", r);
-        NEED(c->h_mask == L->h_mask && c->h_fsf == L->h_fsf && c->h_has_lsf == L->h_has_lsf &&
-                 (!c->h_has_lsf || c->h_lsf == L->h_lsf) && c->h_thr == L->h_thr,
-             D3D_ERR_INVALID, "ctx %d: another mask, FSF or LSF than ctx 0 (the chains share the work lists and taps)", r);
+        const char *const differs = setup_differs(c, L);
+        NEED(!differs, D3D_ERR_INVALID, "ctx %d: another %s than ctx 0 (the chains share the work lists, the taps and "
+             "the launch's arguments)", r, differs);
         NEED((c->ivar_is_uniform && c->uniform_fast_path) == (L->ivar_is_uniform && L->uniform_fast_path),
              D3D_ERR_INVALID, "ctx %d: uniform and per-voxel variances cannot share a launch", r);
         NEED(c->mh_zigzag == L->mh_zigzag && c->sweep_origin == L->sweep_origin, D3D_ERR_INVALID,
              "ctx %d: another walk order or sweep origin than ctx 0", r);
-        bool same_line = c->line.K == L->line.K;
-        for (int k = 0; k < d3d::LINE_KMAX; ++k)
-            same_line = same_line && c->line.off[k] == L->line.off[k] && c->line.ratio[k] == L->line.ratio[k];
-        // (and the table: the leader's device copy serves every chain)
-        same_line = same_line && c->line.n == L->line.n && c->line.support == L->line.support &&
-                    c->h_line_tab == L->h_line_tab;
-        NEED(same_line, D3D_ERR_INVALID,
-             "ctx %d: another line shape than ctx 0 (the chains share the launch's arguments)", r);
         // (the chains share the leader's pending-layer state, and a from-scratch residual
         // clears a chain's own: they must all be rebuilt at the same sweeps)
         NEED(c->prior.on == L->prior.on, D3D_ERR_INVALID,
@@ -545,14 +533,11 @@ int d3d_mh_sweeps_batch(d3d_ctx **ctxs, int n_ctx, int n_sweeps, int first_sweep
              "ctx %d: refresh_every %d differs from ctx 0's %d (batched chains rebuild their residuals together)",
              r, c->refresh_every, L->refresh_every);
         // (and written back at the same sweeps: d3d_robust_begin's draws flush the pending layers)
-        NEED(c->robust.on == L->robust.on && (!c->robust.on || (c->robust.every == L->robust.every && c->robust.start == L->robust.start)),
-             D3D_ERR_INVALID,
-             "ctx %d: robust weights (d3d_robust_begin) armed, every or start differ from ctx 0's (batched chains "
-             "write their pending residual updates back together)", r);
-        NEED(c->noise.on == L->noise.on && (!c->noise.on || (c->noise.every == L->noise.every && c->noise.start == L->noise.start)),
-             D3D_ERR_INVALID,
-             "ctx %d: noise scales (d3d_noise_begin) armed, every or start differ from ctx 0's (batched chains "
-             "write their pending residual updates back together)", r);
+        const d3d_ctx::Rescale &mine = c->rescale, &lead = L->rescale;
+        const RescaleName held = rescale_name(mine.who ? c : L);
+        NEED(mine.who == lead.who && (!mine.who || (mine.every == lead.every && mine.start == lead.start)), D3D_ERR_INVALID,
+             "ctx %d: %s (d3d_%s_begin) armed, every or start differ from ctx 0's (batched chains write their pending "
+             "residual updates back together)", r, held.what, held.api);
     }
     HIP_TRY(hipSetDevice(L->device));
     // saved sweeps (lib/run.py:353, 430-432, 449-451): every chain streams its samples as

@@ -669,18 +669,9 @@ int d3d_temper_create(d3d_temper **out, d3d_ctx **ctxs, int n, const double *bet
              "ctx %d: noise scales are armed (d3d_noise_begin): a rung's variance / beta is not rescaled with them", r);
         NEED(!c->extbuf, D3D_ERR_UNSUPPORTED,
              "ctx %d is driven by d3d_mh_colour_lines: its lines live on the host, tempering swaps device state", r);
-        NEED(c->device == L->device && c->D == L->D && c->H == L->H && c->W == L->W && c->fh == L->fh &&
-                 c->fw == L->fw,
-             D3D_ERR_INVALID, "ctx %d: another device or shape than ctx 0", r);
-        NEED(c->h_mask == L->h_mask && c->h_fsf == L->h_fsf && c->h_has_lsf == L->h_has_lsf &&
-                 (!c->h_has_lsf || c->h_lsf == L->h_lsf) && c->h_thr == L->h_thr,
-             D3D_ERR_INVALID, "ctx %d: another mask, FSF or LSF than ctx 0 (the rungs trade residuals)", r);
-        bool same_line = c->line.K == L->line.K;
-        for (int k = 0; k < d3d::LINE_KMAX; ++k)
-            same_line = same_line && c->line.off[k] == L->line.off[k] && c->line.ratio[k] == L->line.ratio[k];
-        same_line = same_line && c->line.n == L->line.n && c->line.support == L->line.support &&
-                    c->h_line_tab == L->h_line_tab;
-        NEED(same_line, D3D_ERR_INVALID, "ctx %d: another line shape than ctx 0 (the rungs trade parameters)", r);
+        const char *const differs = d3dh::setup_differs(c, L);
+        NEED(!differs, D3D_ERR_INVALID, "ctx %d: another %s than ctx 0 (the rungs trade residuals and parameters)", r,
+             differs);
     }
     HIP_TRY(hipSetDevice(L->device));
     d3d_temper *t = new (std::nothrow) d3d_temper;

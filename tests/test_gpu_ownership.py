@@ -2,7 +2,8 @@
 GPU tests of who owns the library's device memory.  Every reading is the read-only option
 ``device_bytes``: the bytes the library's buffers hold in this process, all contexts together.
 
-  1. an optional feature's end returns what its begin took (and a second begin takes no more);
+  1. an optional feature's end returns what its begin took (and a second begin takes no more); the base
+     1/variance has one holder at a time, robust weights or noise scales (a (16, 12, 12) cube);
   2. closing engines and groups returns everything, whatever was armed, grown or allocated on use;
   3. the buffers of a one-call function do not outlive the call;
   4. arming the posterior features does not change the chain, bit for bit.
@@ -149,6 +150,37 @@ def test_end_returns_what_begin_took():
         assert readings[0] == readings[1] > b
         eng.post_end()                                      # histograms and regions still armed
         assert held(eng) == b
+
+
+@pytest.mark.parametrize("uniform", [True, False])
+def test_the_base_variance_passes_from_robust_weights_to_noise_scales_and_back(uniform):
+    """One base 1/variance, one holder at a time: a second robust_begin saves the base cube and not the
+    rescaled one, ending the feature that does not hold it changes nothing, and the holder's end gives
+    back the cube, the uniform flag and the memory of before the first begin."""
+    case = small_case((16, 12, 12), (3, 3))
+    with engine_for(case) as eng:
+        if uniform:
+            eng.set_data(case["data"], None, 0.09, mask=case["mask"])
+        assert eng.variance_is_uniform() == uniform
+        warm(eng, case)
+        base, b = eng.download_slot(_lib.SLOT_IVAR), held(eng)
+        assert np.isfinite(base).all() and (base > 0.).any()
+        eng.robust_begin(4)
+        eng.robust_step(1)
+        assert not np.array_equal(eng.download_slot(_lib.SLOT_IVAR), base)
+        eng.robust_begin(4)
+        np.testing.assert_array_equal(eng.download_slot(_lib.SLOT_IVAR), base)
+        eng.robust_end()
+        eng.noise_begin(np.arange(16) // 4)
+        eng.noise_step(1)
+        rescaled = eng.download_slot(_lib.SLOT_IVAR)
+        assert not np.array_equal(rescaled, base)
+        eng.robust_end()                                    # (not the holder)
+        np.testing.assert_array_equal(eng.download_slot(_lib.SLOT_IVAR), rescaled)
+        assert not eng.variance_is_uniform() and eng.noise_count() == 1
+        eng.noise_end()
+        np.testing.assert_array_equal(eng.download_slot(_lib.SLOT_IVAR), base)
+        assert eng.variance_is_uniform() == uniform and held(eng) == b
 
 
 # ---- 2. destroy frees everything -------------------------------------------------------------------
