@@ -166,6 +166,41 @@ SPATIAL_TILE = 10000      # the tile kernel k_spatial<NT>: SPATIAL_TILE + NT
 SPECTRAL_BLOCKS, SPECTRAL_DEEP, SPECTRAL_DENSE, SPECTRAL_TAPS, SPECTRAL_SHFL = 1, 2, 3, 4, 5
 STAGE_ZMAJOR, STAGE_TRANSPOSE = 1, 2
 
+# read-only options mh_path / mh_path_layers / mh_path_launches: what the dispatcher of the MH sweep
+# launched (include/deconv3d_hip.h: D3D_MH_*).  mh_path_fields() takes the packed code apart.
+MH_FAMILY_MASK = 0xf
+(MH_WS, MH_SMALL, MH_SMALL_WIDE, MH_ZB, MH_BATCH_WS, MH_BATCH_SMALL, MH_DEFER, MH_IMMEDIATE, MH_DEEP,
+ MH_FLOW, MH_PAIR, MH_CHAIN, MH_SMALL_FULL) = range(1, 14)
+MH_U_SHIFT, MH_U_MASK = 4, 0xf
+MH_M_SHIFT, MH_M_MASK = 8, 0x3
+MH_K_SHIFT, MH_K_MASK = 10, 0x7
+MH_NTV, MH_UV, MH_PRIOR, MH_MULTI = 1 << 13, 1 << 14, 1 << 15, 1 << 16
+MH_NS_SHIFT, MH_NS_MASK = 17, 0x7ff
+MH_FAMILY_NAMES = {MH_WS: "ws", MH_SMALL: "small", MH_SMALL_WIDE: "small wide", MH_ZB: "zb",
+                   MH_BATCH_WS: "batch ws", MH_BATCH_SMALL: "batch small", MH_DEFER: "defer",
+                   MH_IMMEDIATE: "immediate", MH_DEEP: "deep", MH_FLOW: "flow", MH_PAIR: "pair",
+                   MH_CHAIN: "chain", MH_SMALL_FULL: "small full"}
+
+
+def mh_path_fields(code):
+    """The fields of a packed mh_path code: family (its name, None for 0: nothing launched), NS
+    (streaming threads), U (window positions in flight), M (pending layers the kernel can apply), K
+    (staging registers; U and K are 0 where the kernel has no such parameter) and the flags NTV, UV,
+    prior and multi."""
+    code = int(code)
+    return {"family": MH_FAMILY_NAMES.get(code & MH_FAMILY_MASK),
+            "NS": (code >> MH_NS_SHIFT) & MH_NS_MASK,
+            "U": (code >> MH_U_SHIFT) & MH_U_MASK,
+            "M": (code >> MH_M_SHIFT) & MH_M_MASK,
+            "K": (code >> MH_K_SHIFT) & MH_K_MASK,
+            "NTV": bool(code & MH_NTV), "UV": bool(code & MH_UV),
+            "prior": bool(code & MH_PRIOR), "multi": bool(code & MH_MULTI)}
+
+
+def mh_layers_seen(bits):
+    """The pending-layer counts in an mh_path_layers word, as a sorted tuple."""
+    return tuple(n for n in range(4) if (int(bits) >> n) & 1)
+
 
 class HipLibraryMissing(ImportError):
     """libdeconv3d_hip.so has not been built (run __graft_entry__.build())."""

@@ -875,6 +875,24 @@ int d3d_ctx_get_option(d3d_ctx *c, const char *key, long *value) {
         *value = (c->have_data && c->parts.size() == 1 && c->parts[0].strips > 1) ? c->parts[0].strips : 0;
         return D3D_OK;
     }
+    // read-only: what the launchers of d3d_mh.hip launched since the record was last cleared (D3D_MH_*)
+    if (!strcmp(key, "mh_path")) {           // the packed code of the last sweep-kernel launch
+        *value = c->mh_path.code;
+        return D3D_OK;
+    }
+    if (!strcmp(key, "mh_path_layers")) {    // bit n: a launch found n layers pending
+        *value = (long)c->mh_path.layers;
+        return D3D_OK;
+    }
+    if (!strcmp(key, "mh_path_launches")) {  // the launches counted; this read clears the record
+        *value = c->mh_path.launches;
+        c->mh_path = {};
+        return D3D_OK;
+    }
+    if (!strcmp(key, "device_cus")) {        // compute units of the ctx's device: a colour launch of fewer than
+        *value = c->flow_grid / 4;           // 2 workgroups per CU "does not fill the chip" (launch_mh_ws: few)
+        return D3D_OK;
+    }
     if (!strcmp(key, "batch_layers")) {   // pending layers of the last d3d_mh_sweeps_batch: 2 = its joint launches filled the chip
         *value = c->batch_layers;
         return D3D_OK;
@@ -1463,6 +1481,7 @@ int d3d_mh_config(d3d_ctx *c, const double min_b[3], const double max_b[3],
     c->refresh_every = refresh_every;
     c->have_cfg = true;
     c->props_sweep = -1;
+    c->mh_path = {};  // (read-only options mh_path*: the record of a chain starts with its configuration)
     return D3D_OK;
 }
 

@@ -230,7 +230,7 @@ struct d3d_ctx {
     int mh_defer_opt = 1;         // option mh_defer
     int mh_zblocks = 1;           // option mh_zblocks = 0: cubes deeper than 512 channels keep k_mh_defer / k_mh_deep
     bool mh_zb = false;           // the z-blocked kernels run (k_mh_ws<..., ZBK> + k_mh_zdecide)
-    DevBuf<double> z_part;        // [items of a launch][blocks][4 waves][8] wave sums
+    DevBuf<double> z_part;        // [strip][items of a launch][blocks][4 waves][8] wave sums (launch_mh_zb)
     DevBuf<double> z_E;           // [2][slots][Dp] lines of the updates of the last colour class
 #ifdef D3D_EXPERIMENTS
     DevBuf<unsigned long long> stampbuf; // D3D_MH_STAMP=1: [launch][workgroup][8]
@@ -463,6 +463,15 @@ struct d3d_ctx {
     // kernel family the last launch_spatial / launch_spectral / d3d_stage_convolve took (read-only
     // options spatial_path / spectral_path / stage_path: D3D_SPATIAL_*, D3D_SPECTRAL_*, D3D_STAGE_*)
     int spatial_path = 0, spectral_path = 0, stage_path = 0;
+    // what the launchers of d3d_mh.hip launched (read-only options mh_path / mh_path_layers /
+    // mh_path_launches): the D3D_MH_* code of the last sweep-kernel launch, the pending-layer counts
+    // the launches found (bit n: n layers), the launches -- since d3d_mh_config or the last read of
+    // mh_path_launches.  Written by the host thread that launches, strips included.
+    struct MHPath {
+        int code = 0;
+        unsigned layers = 0;
+        long launches = 0;
+    } mh_path;
 };
 
 namespace d3dh {
@@ -586,10 +595,10 @@ void pend_push(d3d_ctx *c, int cy, int cx, int g);
 void fill_mh_args(d3d_ctx *c, d3d::MHArgs &P);
 int launch_mh(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep);
 // (total: the windows of the whole colour where the launch is one strip of it -- the kernel variant
-// follows the colour, not the strip; 0: the launch is the colour.  item0: the strip's first window
-// in the colour's list)
+// follows the colour, not the strip; 0: the launch is the colour.  strip: which strip of the colour row
+// the launch is -- every strip keeps its blocks' wave sums in a region of its own)
 int launch_mh_zb(d3d_ctx *c, d3d::MHArgs &P, unsigned n_items, uint32_t sweep, int layers, unsigned total = 0,
-                 unsigned item0 = 0);
+                 unsigned strip = 0);
 // a colour launch of R chains together (MHArgs::batch; d3d_mh_sweeps_batch), grid = R x windows
 int launch_mh_batch(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep, int layers);
 // what differs between the chains of a joint launch; tables: with the chain's sweep tables

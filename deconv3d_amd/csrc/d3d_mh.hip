@@ -6,6 +6,17 @@ namespace d3dh {
 
 using namespace d3d;
 
+// The record of what is launched (d3d_ctx::mh_path, D3D_MH_*): host side, one call where each sweep
+// kernel is launched.  u / k: 0 where the kernel has no such parameter.
+static inline void mh_record(d3d_ctx *c, int family, int ns, int u, int m, int k, bool ntv, bool uv,
+                             const d3d::MHArgs &P) {
+    c->mh_path.code = family | (u << D3D_MH_U_SHIFT) | (m << D3D_MH_M_SHIFT) | (k << D3D_MH_K_SHIFT) |
+                      (ntv ? D3D_MH_NTV : 0) | (uv ? D3D_MH_UV : 0) | (P.prior ? D3D_MH_PRIOR : 0) |
+                      (d3d::line_multi(P.line) ? D3D_MH_MULTI : 0) | (ns << D3D_MH_NS_SHIFT);
+    c->mh_path.layers |= 1u << (P.n_lay & 3);
+    ++c->mh_path.launches;
+}
+
 void pend_clear(d3d_ctx *c) {
     c->lay_n = 0;
     c->pend_part = -1;
@@ -206,26 +217,32 @@ static int need_single_line(const d3d_ctx *c, const char *what) {
 template <int NT, int MAXIT>
 int launch_mh_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep) {
     const size_t lds = d3d::mh_lds_doubles(NT, c->HL, c->Dp, c->N, P.npos) * sizeof(double);
+    auto rec = [&] { mh_record(c, D3D_MH_IMMEDIATE, NT, 0, 0, 0, false, false, P); };
     if (d3d::line_multi(c->line)) {
         if constexpr (MAXIT != 0) return need_single_line(c, "option mh_maxit (register-resident k_mh)");
         if constexpr (MAXIT == 0) {
             if (P.prior) {
+                rec();
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh<NT, 0, true, true>), dim3(grid), dim3(NT), lds,
                                    c->stream, P, sweep);
                 HIP_TRY(hipGetLastError());
                 return 0;
             }
         }
+        rec();
         hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh<NT, MAXIT, true>), dim3(grid), dim3(NT), lds, c->stream,
                            P, sweep);
     } else if (P.prior) {
         if constexpr (MAXIT != 0)
             return fail(D3D_ERR_UNSUPPORTED, "option mh_maxit (register-resident k_mh) has no form with the "
                         "smoothness prior (d3d_prior_begin)");
-        else
+        else {
+            rec();
             hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh<NT, 0, false, true>), dim3(grid), dim3(NT), lds,
                                c->stream, P, sweep);
+        }
     } else {
+        rec();
         hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh<NT, MAXIT>), dim3(grid), dim3(NT), lds, c->stream,
                            P, sweep);
     }
@@ -255,6 +272,7 @@ int launch_mh(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep) {
                             : (d3d::line_multi(c->line) ? &d3d::k_mh_deep<true> : &d3d::k_mh_deep<false>);
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        mh_record(c, D3D_MH_DEEP, 1024, 0, 0, 0, false, false, P);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), lds, c->stream, P, sweep);
         HIP_TRY(hipGetLastError());
         return 0;
@@ -272,6 +290,7 @@ int launch_mh_defer_nt(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t
     const size_t lds = d3d::mh_lds_doubles(NT, c->HL, c->Dp, c->N, P.npos) * sizeof(double);
     auto kern = P.prior ? (d3d::line_multi(c->line) ? &d3d::k_mh_defer<NT, true, true> : &d3d::k_mh_defer<NT, false, true>)
                         : (d3d::line_multi(c->line) ? &d3d::k_mh_defer<NT, true> : &d3d::k_mh_defer<NT, false>);
+    mh_record(c, D3D_MH_DEFER, NT, 0, 1, 0, false, false, P);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, c->stream, P, sweep);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -290,6 +309,7 @@ int launch_mh_ws_um(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sw
         if (lds > 65536)
             attr = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        mh_record(c, D3D_MH_WS, NS, U, M, K, NTV, UV, P);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(NS + 64), lds, c->stream, P, sweep);
     };
     // (the number of pending layers as a template constant: see k_mh_ws)
@@ -383,6 +403,7 @@ int ensure_ptab(d3d_ctx *c) {
 template <bool UV, int NS, int U, int K, int M = 1, bool FULL = false, bool NTV = false>
 int launch_mh_small_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sweep) {
     const size_t lds = d3d::mh_small_lds_doubles(NS, c->HL, c->Dp, P.npos, M) * sizeof(double);
+    mh_record(c, FULL ? D3D_MH_SMALL_FULL : NS == 256 ? D3D_MH_SMALL : D3D_MH_SMALL_WIDE, NS, U, M, K, NTV, UV, P);
     if (P.prior)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh_small<NS, UV, U, K, false, M, FULL, NTV, true>), dim3(grid),
                            dim3(NS), lds, c->stream, P, sweep);
@@ -533,6 +554,7 @@ int launch_mh_flow_t(d3d_ctx *c, const d3d::MHArgs &P, const d3d::MHFlow &F, uin
     constexpr int NS = 256;
     size_t lds = d3d::mh_ws_lds_doubles(NS, c->HL, c->Dp, c->N, P.npos) * sizeof(double);
     lds += 16;  // the ticket
+    mh_record(c, D3D_MH_FLOW, NS, 0, 1, 0, false, UV, P);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh_flow<NS, UV>), dim3((unsigned)c->flow_items),
                        dim3(NS + 64), lds, c->stream, P, F, sweep);
     HIP_TRY(hipGetLastError());
@@ -575,6 +597,7 @@ template <bool UV, int U, int K>
 int launch_mh_pair_t(d3d_ctx *c, const d3d::MHArgs &P, const d3d::MHPair &F, uint32_t sweep) {
     constexpr int NS = 256;
     const size_t lds = d3d::mh_ws_lds_doubles(NS, c->HL, c->Dp, c->N, P.npos, 2) * sizeof(double);
+    mh_record(c, D3D_MH_PAIR, NS, U, 2, K, false, UV, P);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(d3d::k_mh_pair<NS, UV, U, K>), dim3((unsigned)(F.n_a + F.n_b)),
                        dim3(NS + 64), lds, c->stream, P, F, sweep);
     HIP_TRY(hipGetLastError());
@@ -640,7 +663,10 @@ int launch_mh_zb_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned n_items, uint32_t 
     const unsigned grid = n_items * (unsigned)P.z_nb;
     const bool few = total * (unsigned)P.z_nb < (unsigned)c->flow_grid / 2;
     // (the blocks' kernel takes no decision: the prior is k_mh_zdecide's alone)
-    auto go = [&](auto kern, int M) {
+    // (U, M, K, NTV: the instantiation's own, for the record -- one per colour launch, the blocks' kernel and
+    // k_mh_zdecide together)
+    auto go = [&](auto kern, int U, int M, int K, bool NTV) {
+        mh_record(c, D3D_MH_ZB, NS, U, M, K, NTV, UV, P);
         // (LDS of the 256-channel kernel: 35-40 KB, four workgroups per CU)
         const size_t lds =
             d3d::mh_ws_lds_doubles(NS, db / 2, db, db + 2 * d3d::LSF_RL, P.npos, M) * sizeof(double);
@@ -652,23 +678,23 @@ int launch_mh_zb_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned n_items, uint32_t 
     const int nl = P.n_lay;
     if (layers >= 2) {
         if (few) {
-            if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 2, 4, 0, false, true>(d3d::line_multi(P.line), false), 2);
-            else if (nl == 1) go(mh_ws_kernel<NS, UV, 4, 2, 4, 1, false, true>(d3d::line_multi(P.line), false), 2);
-            else go(mh_ws_kernel<NS, UV, 4, 2, 4, 2, false, true>(d3d::line_multi(P.line), false), 2);
+            if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 2, 4, 0, false, true>(d3d::line_multi(P.line), false), 4, 2, 4, false);
+            else if (nl == 1) go(mh_ws_kernel<NS, UV, 4, 2, 4, 1, false, true>(d3d::line_multi(P.line), false), 4, 2, 4, false);
+            else go(mh_ws_kernel<NS, UV, 4, 2, 4, 2, false, true>(d3d::line_multi(P.line), false), 4, 2, 4, false);
         } else if (ntv) {
             if constexpr (!UV) {
-                if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 4, 0, true, true>(d3d::line_multi(P.line), false), 2);
-                else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 4, 1, true, true>(d3d::line_multi(P.line), false), 2);
-                else go(mh_ws_kernel<NS, UV, 2, 2, 4, 2, true, true>(d3d::line_multi(P.line), false), 2);
+                if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 4, 0, true, true>(d3d::line_multi(P.line), false), 2, 2, 4, true);
+                else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 4, 1, true, true>(d3d::line_multi(P.line), false), 2, 2, 4, true);
+                else go(mh_ws_kernel<NS, UV, 2, 2, 4, 2, true, true>(d3d::line_multi(P.line), false), 2, 2, 4, true);
             }
         } else {
-            if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 4, 0, false, true>(d3d::line_multi(P.line), false), 2);
-            else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 4, 1, false, true>(d3d::line_multi(P.line), false), 2);
-            else go(mh_ws_kernel<NS, UV, 2, 2, 4, 2, false, true>(d3d::line_multi(P.line), false), 2);
+            if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 4, 0, false, true>(d3d::line_multi(P.line), false), 2, 2, 4, false);
+            else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 4, 1, false, true>(d3d::line_multi(P.line), false), 2, 2, 4, false);
+            else go(mh_ws_kernel<NS, UV, 2, 2, 4, 2, false, true>(d3d::line_multi(P.line), false), 2, 2, 4, false);
         }
     } else {
-        if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 1, 4, 0, false, true>(d3d::line_multi(P.line), false), 1);
-        else go(mh_ws_kernel<NS, UV, 4, 1, 4, 1, false, true>(d3d::line_multi(P.line), false), 1);
+        if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 1, 4, 0, false, true>(d3d::line_multi(P.line), false), 4, 1, 4, false);
+        else go(mh_ws_kernel<NS, UV, 4, 1, 4, 1, false, true>(d3d::line_multi(P.line), false), 4, 1, 4, false);
     }
     HIP_TRY(hipGetLastError());
     const int nw = P.z_nb * (NS / 64);
@@ -680,7 +706,7 @@ int launch_mh_zb_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned n_items, uint32_t 
 }
 
 int launch_mh_zb(d3d_ctx *c, d3d::MHArgs &P, unsigned n_items, uint32_t sweep, int layers, unsigned total,
-                 unsigned item0) {
+                 unsigned strip) {
     if (!total) total = n_items;
     NEED(P.n_lay <= (layers >= 2 ? 2 : 1), D3D_ERR_STATE, "internal: %d pending layers for the z-blocked kernel",
          P.n_lay);
@@ -688,12 +714,14 @@ int launch_mh_zb(d3d_ctx *c, d3d::MHArgs &P, unsigned n_items, uint32_t sweep, i
     // are distinct points of one colour class's lattice, up to one period outside the cube:
     // allocated once, for the largest launch there can be
     const size_t max_items = (size_t)(c->H / c->fh + 2) * (c->W / c->fw + 2);
-    NEED((size_t)item0 + n_items <= max_items, D3D_ERR_STATE, "internal: %u windows in one colour launch",
-         item0 + n_items);
-    if (!c->z_part) HIP_TRY(c->z_part.alloc(max_items * P.z_nb * 32));
+    NEED(n_items <= max_items && strip <= (unsigned)d3d_ctx::STRIP_AUX, D3D_ERR_STATE,
+         "internal: %u windows in one colour launch (strip %u)", n_items, strip);
+    if (!c->z_part) HIP_TRY(c->z_part.alloc(max_items * P.z_nb * 32 * (d3d_ctx::STRIP_AUX + 1)));
     if (!c->z_E) HIP_TRY(c->z_E.alloc((size_t)2 * c->slots * c->Dp));
-    // (a strip's wave sums behind those of the strips before it: they may run at the same time)
-    P.z_part = c->z_part + (size_t)item0 * P.z_nb * 32;
+    // (every strip its own region, the same for every colour of the row: the strips run at the same time
+    // and a strip may be a colour ahead -- placed behind the strips before it in the COLOUR's list, a
+    // colour of more windows per lattice row wrote over sums a strip behind had not read yet)
+    P.z_part = c->z_part + (size_t)strip * max_items * P.z_nb * 32;
     P.z_E = c->z_E;
     if (c->ivar_is_uniform && c->uniform_fast_path) return launch_mh_zb_t<true>(c, P, n_items, sweep, layers, total);
     return launch_mh_zb_t<false>(c, P, n_items, sweep, layers, total);
@@ -708,35 +736,39 @@ int launch_mh_batch_t(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t 
     const bool few = grid < (unsigned)c->flow_grid / 2;
     if (P.ltab && layers == 1) {  // the joint launch does not fill the chip either: k_mh_small
         const size_t lds = d3d::mh_small_lds_doubles(NS, c->HL, c->Dp, P.npos, 1) * sizeof(double);
-        auto go_small = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(NS), lds, c->stream, P, sweep); };
+        auto go_small = [&](auto kern, int K) {
+            mh_record(c, D3D_MH_BATCH_SMALL, NS, 8, 1, K, false, UV, P);
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(NS), lds, c->stream, P, sweep);
+        };
         if (P.prior) {
-            if (c->Dp <= 64) go_small(d3d::k_mh_small<NS, UV, 8, 1, true, 1, false, false, true>);
-            else if (c->Dp <= 128) go_small(d3d::k_mh_small<NS, UV, 8, 2, true, 1, false, false, true>);
-            else go_small(d3d::k_mh_small<NS, UV, 8, 4, true, 1, false, false, true>);
-        } else if (c->Dp <= 64) go_small(d3d::k_mh_small<NS, UV, 8, 1, true>);
-        else if (c->Dp <= 128) go_small(d3d::k_mh_small<NS, UV, 8, 2, true>);
-        else go_small(d3d::k_mh_small<NS, UV, 8, 4, true>);
+            if (c->Dp <= 64) go_small(d3d::k_mh_small<NS, UV, 8, 1, true, 1, false, false, true>, 1);
+            else if (c->Dp <= 128) go_small(d3d::k_mh_small<NS, UV, 8, 2, true, 1, false, false, true>, 2);
+            else go_small(d3d::k_mh_small<NS, UV, 8, 4, true, 1, false, false, true>, 4);
+        } else if (c->Dp <= 64) go_small(d3d::k_mh_small<NS, UV, 8, 1, true>, 1);
+        else if (c->Dp <= 128) go_small(d3d::k_mh_small<NS, UV, 8, 2, true>, 2);
+        else go_small(d3d::k_mh_small<NS, UV, 8, 4, true>, 4);
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    auto go = [&](auto kern, int M) {
+    auto go = [&](auto kern, int U, int M, int K, bool) {
+        mh_record(c, D3D_MH_BATCH_WS, NS, U, M, K, false, UV, P);
         const size_t lds = d3d::mh_ws_lds_doubles(NS, c->HL, c->Dp, c->N, P.npos, M) * sizeof(double);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(NS + 64), lds, c->stream, P, sweep);
     };
     const int nl = P.n_lay;
     if (layers >= 2) {  // Dp <= 160: the staged G rows in two registers
         if (few) {
-            if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 2, 2, 0, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 2);
-            else if (nl == 1) go(mh_ws_kernel<NS, UV, 4, 2, 2, 1, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 2);
-            else go(mh_ws_kernel<NS, UV, 4, 2, 2, 2, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 2);
+            if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 2, 2, 0, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 4, 2, 2, false);
+            else if (nl == 1) go(mh_ws_kernel<NS, UV, 4, 2, 2, 1, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 4, 2, 2, false);
+            else go(mh_ws_kernel<NS, UV, 4, 2, 2, 2, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 4, 2, 2, false);
         } else {
-            if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 2, 0, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 2);
-            else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 2, 1, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 2);
-            else go(mh_ws_kernel<NS, UV, 2, 2, 2, 2, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 2);
+            if (nl == 0) go(mh_ws_kernel<NS, UV, 2, 2, 2, 0, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 2, 2, 2, false);
+            else if (nl == 1) go(mh_ws_kernel<NS, UV, 2, 2, 2, 1, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 2, 2, 2, false);
+            else go(mh_ws_kernel<NS, UV, 2, 2, 2, 2, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 2, 2, 2, false);
         }
     } else {
-        if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 1, 4, 0, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 1);
-        else go(mh_ws_kernel<NS, UV, 4, 1, 4, 1, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 1);
+        if (nl == 0) go(mh_ws_kernel<NS, UV, 4, 1, 4, 0, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 4, 1, 4, false);
+        else go(mh_ws_kernel<NS, UV, 4, 1, 4, 1, false, false, true>(d3d::line_multi(P.line), P.prior != 0), 4, 1, 4, false);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -848,6 +880,7 @@ int launch_mh_chain_t(d3d_ctx *c, const d3d::MHArgs &P, const d3d::MHChain &F, i
     if (lds > (size_t)160 * 1024) return fail(D3D_ERR_STATE, "internal: chain kernel needs %zu B of LDS", lds);
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    mh_record(c, D3D_MH_CHAIN, F.NS, 0, 1, 0, false, UV, P);
     hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(nw * 64 + 64), lds, c->stream, P, F);
     HIP_TRY(hipGetLastError());
     return 0;

@@ -304,7 +304,7 @@ int run_part(d3d_ctx *c, int pi, uint32_t sweep, const Batch *b = nullptr, bool 
                 d3d::MHArgs Ps = P;
                 Ps.spx = P.spx + so[s];
                 c->stream = s ? c->strip_stream[s - 1] : strips.main;
-                const int rc = c->mh_zb ? launch_mh_zb(c, Ps, (unsigned)n, sweep, layers, (unsigned)n_all, (unsigned)so[s])
+                const int rc = c->mh_zb ? launch_mh_zb(c, Ps, (unsigned)n, sweep, layers, (unsigned)n_all, (unsigned)s)
                                         : launch_mh_defer(c, Ps, (unsigned)n, sweep, layers, pt.wide, (unsigned)n_all);
                 c->stream = strips.main;
                 if (rc) return rc;

@@ -115,7 +115,48 @@ int d3d_timer_stop(d3d_ctx *ctx, double *elapsed_ms);
  * the last d3d_noise_step made with the option noise_timing = 1 (HIP events between its launches; the
  * draws of the sweeps are never timed).
  * "device_bytes" (read-only): the bytes of device memory the library holds, over all contexts and
- * tempering groups of the process (the pinned snapshot ring is host memory and not counted). */
+ * tempering groups of the process (the pinned snapshot ring is host memory and not counted).
+ * Three read-only keys say what the dispatcher of the MH sweep launched (host-side words of the ctx,
+ * written where each sweep kernel is launched; no kernel argument, nothing in the library reads them):
+ * "mh_path", the packed D3D_MH_* code of the LAST sweep-kernel launch (0: none since the record was
+ * cleared) -- kernel family, streaming threads NS, window positions in flight U, pending layers the
+ * kernel can apply M, staging registers K and the flags NTV (non-temporal 1/variance, write-through
+ * residual), UV (uniform variance), PRIOR and MULTI (multiplet or tabulated line); "mh_path_layers",
+ * bit n set when a launch found n layers pending (n = 0..3); "mh_path_launches", the launches counted.
+ * All three count since the record was last cleared: by d3d_mh_config, and by READING
+ * "mh_path_launches" (read it last).  A launch in lattice-row strips counts once per strip; of a
+ * d3d_mh_sweeps_batch the record is the leader's (ctx 0).
+ * "device_cus" (read-only): the compute units of the ctx's device.  A colour launch of fewer than 2
+ * workgroups per compute unit "does not fill the chip": the rule by which the dispatcher picks the
+ * variants with more window positions in flight. */
+enum {
+    D3D_MH_FAMILY_MASK = 0xf,      /* code & mask: one of the families below */
+    D3D_MH_WS = 1,                 /* k_mh_ws (NS 256, 512, or the wide form's) */
+    D3D_MH_SMALL = 2,              /* k_mh_small, 256 threads */
+    D3D_MH_SMALL_WIDE = 3,         /* k_mh_small, the wide form of a partitioned ctx at 128 channels */
+    D3D_MH_ZB = 4,                 /* k_mh_ws<..., ZBK> on (window, 256-channel block) + k_mh_zdecide */
+    D3D_MH_BATCH_WS = 5,           /* d3d_mh_sweeps_batch: k_mh_ws<..., BATCH> */
+    D3D_MH_BATCH_SMALL = 6,        /* d3d_mh_sweeps_batch: k_mh_small<..., BATCH> */
+    D3D_MH_DEFER = 7,              /* k_mh_defer<NS> (option mh_defer = 2; deep cubes without z-blocks) */
+    D3D_MH_IMMEDIATE = 8,          /* k_mh<NS> (option mh_defer = 0, d3d_mh_colour) */
+    D3D_MH_DEEP = 9,               /* k_mh_deep: more than 1024 channels, threads loop over z-pairs */
+    D3D_MH_FLOW = 10,              /* k_mh_flow (`make EXPERIMENTS=1`) */
+    D3D_MH_PAIR = 11,              /* k_mh_pair (`make EXPERIMENTS=1`) */
+    D3D_MH_CHAIN = 12,             /* k_mh_chain (`make EXPERIMENTS=1`) */
+    D3D_MH_SMALL_FULL = 13,        /* k_mh_small<..., FULL> (`make EXPERIMENTS=1`, option mh_small = 2) */
+    D3D_MH_U_SHIFT = 4,            /* 4 bits: window positions in flight per thread (0: not a parameter) */
+    D3D_MH_U_MASK = 0xf,
+    D3D_MH_M_SHIFT = 8,            /* 2 bits: pending layers the kernel can apply */
+    D3D_MH_M_MASK = 0x3,
+    D3D_MH_K_SHIFT = 10,           /* 3 bits: registers a staged G row takes (0: not a parameter) */
+    D3D_MH_K_MASK = 0x7,
+    D3D_MH_NTV = 1 << 13,          /* non-temporal 1/variance loads, write-through residual stores */
+    D3D_MH_UV = 1 << 14,           /* the uniform-variance instantiation */
+    D3D_MH_PRIOR = 1 << 15,        /* the smoothness prior's terms (d3d_prior_begin) */
+    D3D_MH_MULTI = 1 << 16,        /* the multiplet / tabulated form of the unit line */
+    D3D_MH_NS_SHIFT = 17,          /* 11 bits: streaming threads (k_mh, k_mh_defer, k_mh_deep: all threads) */
+    D3D_MH_NS_MASK = 0x7ff
+};
 enum {
     D3D_SPATIAL_CONV_ROWS = 1,     /* k_conv_rows, FSF only, one block of <= 128 channels */
     D3D_SPATIAL_CONV_ROWS_ZB = 2,  /* k_conv_rows in z-blocks of 128 channels (FSF only) */

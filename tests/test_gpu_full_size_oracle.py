@@ -33,6 +33,15 @@ pytestmark = pytest.mark.gpu
 SEED = 12345
 
 
+def assert_two_strips_and_path(eng, **fields):
+    """The chip-filling launches of a per-voxel variance run in two lattice-row strips (the default
+    since the strips), and the last launch was the kernel variant the test is about."""
+    want = dict(family="ws", NS=256, U=2, M=2, K=2, NTV=False, UV=False, prior=False, multi=False)
+    want.update(fields)
+    assert eng.get_option("mh_strips_on") == 2
+    assert _lib.mh_path_fields(eng.get_option("mh_path")) == want
+
+
 def build(D, H, W, fs, options=None, line_shape=None):
     """line_shape: (offsets, ratios), set before the data are built -- bench.synthetic_inputs
     builds them with the engine's own forward model."""
@@ -83,6 +92,7 @@ def test_config3_full_sweep_update_by_update_against_the_oracle():
         err0 = start(eng, pb)
         st = oracle_state(pb, err0)
         accepted = eng.mh_sweeps(1, 1)
+        assert_two_strips_and_path(eng)
         assert O.mh_sweep(st, 1) == int(pb["mask"].sum())
         assert_matches_oracle(eng, st, accepted, pb)
 
@@ -135,6 +145,7 @@ def check_beyond_cache_policy(line_shape=None, sweeps=2):
             assert eng.get_option("mh_nt_ivar_on") == nt
             err0 = start(eng, pb)
             accepted = eng.mh_sweeps(sweeps, 1)
+            assert_two_strips_and_path(eng, NTV=bool(nt), multi=line_shape is not None)
             if nt:
                 st = oracle_state(pb, err0)
                 for s in range(1, sweeps + 1):
@@ -159,6 +170,7 @@ def test_512_thread_kernel_with_chip_filling_launches_matches_the_oracle():
             assert eng.mh_layers() == 2
             err0 = start(eng, pb)
             accepted = eng.mh_sweeps(1, 1)
+            assert_two_strips_and_path(eng, NS=512, U=4, K=4, NTV=bool(nt))
             if nt:
                 st = oracle_state(pb, err0)
                 O.mh_sweep(st, 1)
@@ -187,10 +199,13 @@ def test_z_blocked_kernels_with_chip_filling_launches():
                 # update -- one sweep of 12 541 updates, ~1 MB of window each
                 st = oracle_state(pb, err0)
                 accepted = eng.mh_sweeps(1, 1)
+                assert_two_strips_and_path(eng, family="zb", K=4)
                 O.mh_sweep(st, 1)
                 assert_matches_oracle(eng, st, accepted, pb)
                 start(eng, pb)
             accepted = eng.mh_sweeps(3, 1)
+            if "mh_nt_ivar" in opts:
+                assert_two_strips_and_path(eng, family="zb", K=4, NTV=bool(opts["mh_nt_ivar"]))
             carried = eng.download_slot(_lib.SLOT_ERR)
             params = eng.get_params()
             fresh = eng.residual()

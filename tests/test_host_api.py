@@ -54,6 +54,30 @@ def test_path_codes_of_the_binding_equal_the_header():
         assert len(set(values)) == len(values) and 0 not in values
 
 
+def test_mh_path_layout_of_the_binding_equals_the_header():
+    """The read-only option mh_path packs D3D_MH_* fields; _lib mirrors every constant, its decoder
+    takes a code apart into the fields it was made of, and the fields do not overlap."""
+    text = open(os.path.join(ROOT, "include", "deconv3d_hip.h")).read()
+    consts = {}
+    for name, value in re.findall(r"\bD3D_(MH_[A-Z_]+) = (0x[0-9a-f]+|\d+(?: << \d+)?)", text):
+        consts[name] = eval(value)      # "13", "0x7ff" or "1 << 13"
+    assert len(consts) == 26
+    for name, value in consts.items():
+        assert getattr(_lib, name) == value, name
+    families = [v for k, v in consts.items() if not re.search(r"_(MASK|SHIFT|NTV|UV|PRIOR|MULTI)$", k)]
+    assert sorted(families) == list(range(1, 14)) and sorted(_lib.MH_FAMILY_NAMES) == sorted(families)
+    fields = [_lib.MH_FAMILY_MASK, _lib.MH_U_MASK << _lib.MH_U_SHIFT, _lib.MH_M_MASK << _lib.MH_M_SHIFT,
+              _lib.MH_K_MASK << _lib.MH_K_SHIFT, _lib.MH_NTV, _lib.MH_UV, _lib.MH_PRIOR, _lib.MH_MULTI,
+              _lib.MH_NS_MASK << _lib.MH_NS_SHIFT]
+    assert sum(fields) == (1 << 28) - 1 and all(a & b == 0 for i, a in enumerate(fields) for b in fields[:i])
+    code = (_lib.MH_ZB | 2 << _lib.MH_U_SHIFT | 3 << _lib.MH_M_SHIFT | 4 << _lib.MH_K_SHIFT | _lib.MH_NTV
+            | _lib.MH_MULTI | 704 << _lib.MH_NS_SHIFT)
+    assert _lib.mh_path_fields(code) == dict(family="zb", NS=704, U=2, M=3, K=4, NTV=True, UV=False,
+                                             prior=False, multi=True)
+    assert _lib.mh_path_fields(0)["family"] is None
+    assert _lib.mh_layers_seen(0b0110) == (1, 2) and _lib.mh_layers_seen(0) == ()
+
+
 def test_every_entry_point_cites_the_reference():
     text = open(os.path.join(ROOT, "include", "deconv3d_hip.h")).read()
     assert text.count("lib/run.py:") >= 15
