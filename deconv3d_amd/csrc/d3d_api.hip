@@ -285,6 +285,15 @@ int build_colour_lists(d3d_ctx *c) {
                 }
             }
         }
+        // The strips chained from colour row to colour row (d3d_strip_order.h) where the option asks for
+        // it and the schedule can be built: every active colour row holds pt.layers colours at least.
+        pt.order = d3d_strip_order::Schedule();
+        if (pt.strips > 1 && (c->mh_strip_order_opt ? c->mh_strip_order_opt : MH_STRIP_ORDER_AUTO) == 2) {
+            std::vector<int> active;
+            for (int col = 0; col < ncol; ++col)
+                if (pt.real[col] > 0) active.push_back(col);
+            (void)d3d_strip_order::build(pt.strips, c->fw, active, pt.layers, &pt.order);
+        }
         // k_mh_chain: whole sweeps of the part in one launch of persistent workgroups, one per
         // lattice slot -- where every slot is resident at once (one workgroup per CU) and a
         // thread can hold its share of the window in registers
@@ -543,6 +552,8 @@ const OptDesc g_opts[] = {
     {"mh_zigzag", "D3D_MH_ZIGZAG", &d3d_ctx::mh_zigzag, OPT_MH, 0, 1},
     {"mh_nt_ivar", "D3D_MH_NT_IVAR", &d3d_ctx::mh_nt_ivar_opt, OPT_MH, -1, 1},
     {"mh_strips", "D3D_MH_STRIPS", &d3d_ctx::mh_strips_opt, OPT_MH, 0, d3d_strips::MAX_STRIPS},
+    {"mh_strip_order", "D3D_MH_STRIP_ORDER", &d3d_ctx::mh_strip_order_opt, OPT_MH, 0, 2},
+    {"mh_strip_lag", "D3D_MH_STRIP_LAG", &d3d_ctx::mh_strip_lag, OPT_LAUNCH, 0, d3d_strips::MAX_STRIPS},
     {"mh_nt", "D3D_MH_NT", &d3d_ctx::mh_nt_opt, OPT_MH, 0, 1024},
     {"uniform_ivar", "D3D_UNIFORM_IVAR", &d3d_ctx::uniform_fast_path, OPT_MH, 0, 1},
     {"conv_rows", "D3D_CONV_ROWS", &d3d_ctx::conv_rows, OPT_LAUNCH, 0, 1},
@@ -763,6 +774,8 @@ int d3d_ctx_destroy(d3d_ctx *c) {
         if (c->strip_join[a]) (void)hipEventDestroy(c->strip_join[a]);
     }
     if (c->strip_fork) (void)hipEventDestroy(c->strip_fork);
+    for (hipEvent_t e : c->strip_ev)
+        if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->halo_ev) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -873,6 +886,11 @@ int d3d_ctx_get_option(d3d_ctx *c, const char *key, long *value) {
     }
     if (!strcmp(key, "mh_strips_on")) {   // lattice-row strips the colour rows of d3d_mh_sweeps run in (0: none)
         *value = (c->have_data && c->parts.size() == 1 && c->parts[0].strips > 1) ? c->parts[0].strips : 0;
+        return D3D_OK;
+    }
+    if (!strcmp(key, "mh_strip_order_on")) {  // how those strips are ordered: 0 no strips, 1 joined per colour row, 2 chained
+        const bool strips = c->have_data && c->parts.size() == 1 && c->parts[0].strips > 1;
+        *value = !strips ? 0 : c->parts[0].order.S > 1 ? 2 : 1;
         return D3D_OK;
     }
     // read-only: what the launchers of d3d_mh.hip launched since the record was last cleared (D3D_MH_*)

@@ -32,6 +32,7 @@
 
 #include "../../include/deconv3d_hip.h"
 #include "d3d_kernels.h"
+#include "d3d_strip_order.h"
 #include "d3d_strips.h"
 
 // The WIDE form of a small colour launch at 128 channels: eleven
@@ -50,6 +51,11 @@ constexpr int MH_CHAIN_NT = 768;
 // is 0 (1: none).  What profiles/sweep_strips_ab.txt justifies: two pass the project's rule, three gain
 // less, four lose.
 constexpr int MH_STRIPS_AUTO = 2;
+// How the strips of consecutive colour rows are ordered when option mh_strip_order is 0: 1 joined after
+// every colour row, 2 chained row to row by events with one join per sweep (d3d_strip_order.h).  What
+// profiles/sweep_chained_ab.txt justifies: chained passes the project's rule with two strips and with
+// three (which the z-blocked form loses with: the automatic count stays two), the joined form with none.
+constexpr int MH_STRIP_ORDER_AUTO = 2;
 
 namespace d3dh {
 // sets the thread-local message d3d_last_error() returns; returns `code`
@@ -164,6 +170,9 @@ struct d3d_ctx {
         int strips = 1;                          // 1: whole colour launches
         std::vector<int> soff;                   // [fh*fw][strips + 1] start of each strip in the colour's list
         std::vector<int> sreal;                  // [fh*fw][strips] real spaxels of each strip
+        // the strips chained from colour row to colour row (option mh_strip_order; order.S == 0: joined
+        // after every colour row): the schedule run_part executes, one step per active colour
+        d3d_strip_order::Schedule order;
     };
     std::vector<Part> parts;
     std::vector<int4> part_rects;  // as given to d3d_set_parts ({y0,y1,x0,x1}; .phase apart)
@@ -190,12 +199,20 @@ struct d3d_ctx {
     double *snap_host[STREAM_NB] = {};  // pinned
     hipEvent_t snap_ready[STREAM_NB] = {}, snap_done[STREAM_NB] = {};
     // lattice-row strips of a colour row (Part::strips): strip 0 runs on `stream`, strip s > 0 on
-    // strip_stream[s - 1]; one fork and one join per colour row (run_part).  Created on first use.
+    // strip_stream[s - 1]; one fork and one join per colour row, or -- chained -- per sweep (run_part).
+    // Created on first use.
     static constexpr int STRIP_AUX = 3;
     hipStream_t strip_stream[STRIP_AUX] = {};
     hipEvent_t strip_fork = nullptr, strip_join[STRIP_AUX] = {};
     int mh_strips_opt = 0;        // option mh_strips: 0 automatic, 1 off, 2..4 that many strips (forced: also
                                   // where the colour launches do not fill the chip)
+    // the chained order (d3d_strip_order.h): its events; the G buffer behind every slot the schedule names
+    // (the pending layers always lie in the pool the sweep's first row does not write); the pool that row takes
+    hipEvent_t strip_ev[d3d_strip_order::NEV] = {};
+    int strip_gbuf[d3d_strip_order::GSLOTS] = {0, 1, 2, 3, 4, 5, 6, 7};
+    int strip_pool = 0;
+    int mh_strip_order_opt = 0;   // option mh_strip_order: 0 automatic, 1 joined after every colour row, 2 chained
+    int mh_strip_lag = 0;         // test option mh_strip_lag: s + 1 delays strip s at the start of every colour row
     // RCCL communicator of the tiled chain (d3d_comm_init)
     ncclComm_t comm = nullptr;
     int comm_rank = -1, comm_size = 0;

@@ -142,6 +142,19 @@ int launch_real(d3d_ctx *c, const d3d_ctx::Part &pt, int col, const d3d::MHArgs 
 // other, between ONE fork before the row's first active colour and ONE join after its last:
 // strip 0 on the context's stream, strip s on strip_stream[s - 1].  On every way out of run_part:
 // joined, the context back on its stream.
+//
+// Chained (Part::order, option mh_strip_order): ONE fork per sweep and ONE join at its end; between
+// them the strips of consecutive colour rows are ordered by the events of d3d_strip_order.h, and the
+// colours write the G buffers its schedule names.
+static_assert(d3d_ctx::GBUFS == d3d_strip_order::GSLOTS, "a G buffer behind every slot of the schedule");
+
+// Test option mh_strip_lag: one wavefront that ends once the constant 100 MHz counter has advanced by
+// 100 us -- or after 40 sleeps of some 3 us, whichever comes first.  It reads and writes no memory.
+__global__ __launch_bounds__(64) void k_strip_lag() {
+    const uint64_t t0 = wall_clock64();
+    for (int i = 0; i < 40 && wall_clock64() - t0 < 10000; ++i) __builtin_amdgcn_s_sleep(127);
+}
+
 struct StripScope {
     d3d_ctx *c;
     hipStream_t main;
@@ -179,8 +192,85 @@ struct StripScope {
         row = colour_row;
         return 0;
     }
+    // ---- the chained order (d3d_strip_order.h): the schedule's steps, nothing else ----
+    const d3d_strip_order::Schedule *sched = nullptr;  // the sweep's schedule once its first step has run
+    int pool0 = 0;                                     // pool of the sweep's first active row
+    hipStream_t stream_of(int s) const { return s ? c->strip_stream[s - 1] : main; }
+    int record(unsigned mask, int s) {
+        for (int e = 0; e < d3d_strip_order::NEV; ++e)
+            if ((mask >> e) & 1) HIP_TRY(hipEventRecord(c->strip_ev[e], stream_of(s)));
+        return 0;
+    }
+    int wait(unsigned mask, int s) {
+        for (int e = 0; e < d3d_strip_order::NEV; ++e)
+            if ((mask >> e) & 1) HIP_TRY(hipStreamWaitEvent(stream_of(s), c->strip_ev[e], 0));
+        return 0;
+    }
+    // Before the launches of step k: its records, its waits.  The first step of a sweep also sees to the G
+    // buffers: every layer pending from before must lie in the pool this sweep's first row does NOT write
+    // (its last reader in another strip runs in that row).  Layers the chained sweep before left do; others
+    // (whole launches, joined strips) get the slots of that pool, the free buffers the rest.
+    int enter(const d3d_strip_order::Schedule &sd, int k) {
+        namespace so = d3d_strip_order;
+        const so::Step &st = sd.steps[(size_t)k];
+        if (k == 0) {
+            if (int rc = setup()) return rc;
+            for (int e = 0; e < so::NEV; ++e)
+                if (!c->strip_ev[e]) HIP_TRY(hipEventCreateWithFlags(&c->strip_ev[e], hipEventDisableTiming));
+            pool0 = c->strip_pool & 1;
+            const int other = (1 - pool0) * (sd.M + 1);
+            bool placed = true;
+            for (int j = 0; j < c->lay_n; ++j) {
+                bool in = false;
+                for (int q = 0; q <= sd.M; ++q) in = in || c->strip_gbuf[other + q] == c->lay_g[j];
+                placed = placed && in;
+            }
+            if (!placed) {
+                int order[d3d_ctx::GBUFS], n = 0;
+                for (int j = 0; j < c->lay_n; ++j) order[n++] = c->lay_g[j];
+                for (int b = 0; b < d3d_ctx::GBUFS; ++b) {
+                    bool pending = false;
+                    for (int j = 0; j < c->lay_n; ++j) pending = pending || c->lay_g[j] == b;
+                    if (!pending) order[n++] = b;
+                }
+                n = 0;
+                for (int q = 0; q <= sd.M; ++q) c->strip_gbuf[other + q] = order[n++];
+                for (int q = 0; q <= sd.M; ++q) c->strip_gbuf[pool0 * (sd.M + 1) + q] = order[n++];
+                for (int q = 2 * (sd.M + 1); q < so::GSLOTS; ++q) c->strip_gbuf[q] = order[n++];  // (stays a permutation)
+            }
+            c->strip_pool = so::pool_after(sd, pool0);
+            S = sd.S;
+            sched = &sd;
+        }
+        for (int s = 0; s < sd.S; ++s)
+            if (int rc = record(st.pre[s], s)) return rc;
+        for (int s = 0; s < sd.S; ++s)
+            if (int rc = wait(st.wait[s], s)) return rc;
+        // test option mh_strip_lag: one strip late at every colour row -- the chain must not notice
+        if (st.first_of_row && c->mh_strip_lag >= 1 && c->mh_strip_lag <= sd.S) {
+            hipLaunchKernelGGL(k_strip_lag, dim3(1), dim3(64), 0, stream_of(c->mh_strip_lag - 1));
+            HIP_TRY(hipGetLastError());
+        }
+        return 0;
+    }
+    int buf_of(int k) const { return c->strip_gbuf[d3d_strip_order::gslot(*sched, sched->steps[(size_t)k], pool0)]; }
+    int leave(int k) {
+        for (int s = 0; s < sched->S; ++s)
+            if (int rc = record(sched->steps[(size_t)k].post[s], s)) return rc;
+        return 0;
+    }
     int join() {
         c->stream = main;
+        if (sched) {  // the sweep-end join of the schedule
+            const d3d_strip_order::Schedule &sd = *sched;
+            sched = nullptr;
+            S = 1;
+            for (int s = 0; s < sd.S; ++s)
+                if (int rc = record(sd.tail_post[s], s)) return rc;
+            for (int s = 0; s < sd.S; ++s)
+                if (int rc = wait(sd.tail_wait[s], s)) return rc;
+            return 0;
+        }
         const int n = S;
         S = 1;
         row = -1;
@@ -276,6 +366,35 @@ int run_part(d3d_ctx *c, int pi, uint32_t sweep, const Batch *b = nullptr, bool 
         }
         // real + virtual positions: the windows of this launch tile the domain
         const int n_all = pt.off[col + 1] - pt.off[col];
+        // the colour's arguments once; every strip its range of the list on its stream.  The kernel
+        // variant follows the colour's windows, not the strip's; a strip of virtual positions
+        // alone still launches (a storing launch needs their write-back).
+        auto launch_strips = [&](int g_cur) {
+            P.Gcur = c->gbuf[g_cur];
+            const int *so = &pt.soff[(size_t)col * (pt.strips + 1)];
+            for (int s = 0; s < pt.strips; ++s) {
+                const int n = so[s + 1] - so[s];
+                if (n <= 0) continue;
+                d3d::MHArgs Ps = P;
+                Ps.spx = P.spx + so[s];
+                c->stream = s ? c->strip_stream[s - 1] : strips.main;
+                const int rc = c->mh_zb ? launch_mh_zb(c, Ps, (unsigned)n, sweep, layers, (unsigned)n_all, (unsigned)s)
+                                        : launch_mh_defer(c, Ps, (unsigned)n, sweep, layers, pt.wide, (unsigned)n_all);
+                c->stream = strips.main;
+                if (rc) return rc;
+            }
+            push_colour_layer(c, pi, col, g_cur, P.write_back);
+            return 0;
+        };
+        if (strips_ok && pt.order.S > 1) {  // chained: the schedule's step of this colour
+            NEED(pt.order.S == pt.strips && pt.order.M == layers && ka < (int)pt.order.steps.size() &&
+                     pt.order.steps[(size_t)ka].col == col,
+                 D3D_ERR_STATE, "internal: the strips' schedule does not describe colour %d", col);
+            if (int rc = strips.enter(pt.order, ka)) return rc;
+            if (int rc = launch_strips(strips.buf_of(ka))) return rc;
+            if (int rc = strips.leave(ka)) return rc;
+            continue;
+        }
         if (strips.S > 1 && col / c->fw != strips.row)  // the next colour row: its bands lie one cube row lower
             if (int rc = strips.join()) return rc;
         // The strips part ways at the row's first active colour.  A layer still pending from the row
@@ -292,24 +411,7 @@ int run_part(d3d_ctx *c, int pi, uint32_t sweep, const Batch *b = nullptr, bool 
             if (int rc = strips.fork(pt.strips, col / c->fw, locked)) return rc;
         }
         if (strips.S > 1) {
-            // the colour's arguments once; every strip its range of the list on its stream.  The kernel
-            // variant follows the colour's windows, not the strip's; a strip of virtual positions
-            // alone still launches (a storing launch needs their write-back).
-            const int g_cur = strips.free_buf();
-            P.Gcur = c->gbuf[g_cur];
-            const int *so = &pt.soff[(size_t)col * (pt.strips + 1)];
-            for (int s = 0; s < pt.strips; ++s) {
-                const int n = so[s + 1] - so[s];
-                if (n <= 0) continue;
-                d3d::MHArgs Ps = P;
-                Ps.spx = P.spx + so[s];
-                c->stream = s ? c->strip_stream[s - 1] : strips.main;
-                const int rc = c->mh_zb ? launch_mh_zb(c, Ps, (unsigned)n, sweep, layers, (unsigned)n_all, (unsigned)s)
-                                        : launch_mh_defer(c, Ps, (unsigned)n, sweep, layers, pt.wide, (unsigned)n_all);
-                c->stream = strips.main;
-                if (rc) return rc;
-            }
-            push_colour_layer(c, pi, col, g_cur, P.write_back);
+            if (int rc = launch_strips(strips.free_buf())) return rc;
             continue;
         }
 #ifdef D3D_EXPERIMENTS

@@ -94,7 +94,8 @@ int d3d_timer_stop(d3d_ctx *ctx, double *elapsed_ms);
  * Changing an option flushes pending residual updates and re-derives what depends
  * on it (work lists, tap analysis), so it may be called at any time between calls.
  * Keys: mh_defer 0|1|2, mh_zblocks, mh_layers 0(auto)|1|2|3,
- * mh_wide, mh_props, halo_timing, mh_zigzag, mh_nt_ivar -1(auto)|0|1, mh_nt, uniform_ivar, conv_rows,
+ * mh_wide, mh_props, halo_timing, mh_zigzag, mh_nt_ivar -1(auto)|0|1, mh_strips 0(auto)|1|2|3|4,
+ * mh_strip_order 0(auto)|1 joined|2 chained, mh_strip_lag (tests only), mh_nt, uniform_ivar, conv_rows,
  * conv_zb, conv_hy, spatial_sep, sep_fuse, spatial_mode, march_hy, zmajor, zmajor_hy,
  * spectral_dense, spectral_blocks, lines_dense, lines_rounds, spatial_nt, xcd_remap, alt_dir, stagger,
  * post_nt, noise_timing; a build with

@@ -1,21 +1,23 @@
 """Lattice-row strips of a colour row (option mh_strips): same-box A/B and the
 overlap of the strips' kernels, for profiles/sweep_strips_ab.txt.
 
-  python tools/mh_strips.py ab [--lib NAME=PATH ...] [--strips 1,2,3,4] [--rounds 4] [-- bench args]
+  python tools/mh_strips.py ab [--lib NAME=PATH ...] [--strips 1,2,3,4] [--order 1,2] [--rounds 4] [-- bench args]
       bench.py in child processes, alternating between the libraries (DECONV3D_HIP_LIB; the tree's
-      library is "tree") and the strip counts (D3D_MH_STRIPS, the default of new contexts) inside
-      one job, `rounds` times over; prints every ms_per_step, medians, spreads and the project's
+      library is "tree"), the strip counts (D3D_MH_STRIPS, the default of new contexts) and, with
+      --order, how the strips of consecutive colour rows are ordered (D3D_MH_STRIP_ORDER: 1 joined,
+      2 chained; a column NAME/STRIPS/oORDER each) inside one job, `rounds` times over; prints every ms_per_step, medians, spreads and the project's
       rule against the first column (every run faster, median gain >= 5 x the larger spread).
       With --dump DIR every column also runs `--steps 5 --warmup 1 --dump-outputs` once and the
       outputs are compared with the first column's as 64-bit patterns.
       --key PATH: another figure of bench.py's record than ms_per_step, e.g.
       extras.uniform_variance.avg_launch_us (with `-- --full --no-cpu`).
 
-  python tools/mh_strips.py overlap TRACE.csv
+  python tools/mh_strips.py overlap TRACE.csv [--colours 121] [--colour-rows 11]
       a rocprofv3 --kernel-trace CSV of the plain bench command: per sweep kernel launch the
       duration, and over the timed part how much of the wall time has 0, 1, 2, ... k_mh_ws kernels
       in flight; the gap at a join (last end of a colour row to the next start) against the gap
-      between two launches of one stream.
+      between two launches of one stream; the time with nothing in flight per colour row and per
+      sweep (a sweep: --colours launches of the busiest stream, in --colour-rows rows).
 """
 import argparse
 import csv
@@ -29,14 +31,17 @@ import numpy as np
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 
 
-def bench(lib, strips, args, timeout=900):
+def bench(lib, strips, args, timeout=900, order=None):
     env = dict(os.environ)
     env.pop("DECONV3D_HIP_LIB", None)
     env.pop("D3D_MH_STRIPS", None)
+    env.pop("D3D_MH_STRIP_ORDER", None)
     if lib:
         env["DECONV3D_HIP_LIB"] = lib
     if strips is not None:
         env["D3D_MH_STRIPS"] = str(strips)
+    if order is not None:
+        env["D3D_MH_STRIP_ORDER"] = str(order)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, timeout=timeout,
                          stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout
     return json.loads(out.strip().splitlines()[-1])
@@ -53,15 +58,19 @@ def ab(a, bench_args):
     cols = []
     for name, path in libs:
         if name != "tree" and name in a.plain:
-            cols.append((name, path, None))       # a library from before the option: no strip counts
+            cols.append((name, path, None, None))  # a library from before the option: no strip counts
         else:
-            cols += [("%s/%d" % (name, s), path, s) for s in a.strips]
+            for s in a.strips:
+                if a.order and s > 1:
+                    cols += [("%s/%d/o%d" % (name, s, o), path, s, o) for o in a.order]
+                else:
+                    cols.append(("%s/%d" % (name, s), path, s, None))
     cols.sort(key=lambda c: c[0] not in a.first)  # the reference column first
     if a.dump:
         ref = None
-        for name, path, s in cols:
+        for name, path, s, o in cols:
             d = os.path.join(a.dump, name.replace("/", "_"))
-            bench(path, s, ["--gpus", "1", "--steps", "5", "--warmup", "1", "--dump-outputs", d])
+            bench(path, s, ["--gpus", "1", "--steps", "5", "--warmup", "1", "--dump-outputs", d], order=o)
             got = {f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d)) if f.endswith(".npy")}
             if ref is None:
                 ref = got
@@ -74,19 +83,19 @@ def ab(a, bench_args):
     runs = {c[0]: [] for c in cols}
     args = bench_args or ["--gpus", "1", "--steps", "20", "--warmup", "3"]
     for r in range(a.rounds):
-        for name, path, s in cols:
-            runs[name].append(dig(bench(path, s, args), a.key))
-        print("round %d  " % (r + 1) + "  ".join("%s %.4f" % (n, runs[n][-1]) for n, _, _ in cols), flush=True)
+        for name, path, s, o in cols:
+            runs[name].append(dig(bench(path, s, args, order=o), a.key))
+        print("round %d  " % (r + 1) + "  ".join("%s %.4f" % (n, runs[n][-1]) for n, _, _, _ in cols), flush=True)
     print("\n%s of `bench.py %s`" % (a.key, " ".join(args)))
-    print("  run     " + "".join("%-12s" % n for n, _, _ in cols))
+    print("  run     " + "".join("%-12s" % n for n, _, _, _ in cols))
     for r in range(a.rounds):
-        print("  %-8d" % (r + 1) + "".join("%-12.4f" % runs[n][r] for n, _, _ in cols))
+        print("  %-8d" % (r + 1) + "".join("%-12.4f" % runs[n][r] for n, _, _, _ in cols))
     med = {n: float(np.median(v)) for n, v in runs.items()}
     spread = {n: (max(v) - min(v)) / med[n] for n, v in runs.items()}
-    print("  median  " + "".join("%-12.4f" % med[n] for n, _, _ in cols))
-    print("  spread  " + "".join("%-12s" % ("%.2f %%" % (100 * spread[n])) for n, _, _ in cols))
+    print("  median  " + "".join("%-12.4f" % med[n] for n, _, _, _ in cols))
+    print("  spread  " + "".join("%-12s" % ("%.2f %%" % (100 * spread[n])) for n, _, _, _ in cols))
     base = cols[0][0]
-    for n, _, _ in cols[1:]:
+    for n, _, _, _ in cols[1:]:
         gain = 1.0 - med[n] / med[base]
         every = max(runs[n]) < min(runs[base])
         noise = max(spread[n], spread[base])
@@ -96,7 +105,7 @@ def ab(a, bench_args):
                  "passes" if every and gain >= 5 * noise else "does not pass"))
 
 
-def overlap(path):
+def overlap(path, colours=121, colour_rows=11):
     rows = []
     with open(path) as fh:
         for rec in csv.DictReader(fh):
@@ -123,6 +132,14 @@ def overlap(path):
                                                    wall / 1e3 / len(ws), np.median(dur), dur.min(), dur.max()))
     for k in sorted(hist):
         print("  %d kernels in flight: %5.1f %% of the wall time" % (k, 100.0 * hist[k] / wall))
+    # a sweep is `colours` launches of the busiest stream (strip 0 launches every colour)
+    per_stream = {}
+    for r in ws:
+        per_stream[r[3]] = per_stream.get(r[3], 0) + 1
+    sweeps = max(per_stream.values()) / float(colours)
+    idle = hist.get(0, 0) / 1e3
+    print("  %.1f sweeps: %.1f us with nothing in flight per colour row, %.1f us per sweep; %.1f us of wall time per sweep"
+          % (sweeps, idle / (sweeps * colour_rows), idle / sweeps, wall / 1e3 / sweeps))
     # gaps with nothing in flight, by length: the longest ones are the joins
     gaps, depth, last = [], 0, t0
     for t, d in ev:
@@ -175,15 +192,19 @@ def main():
                    help="a library without the option (the parent's): one column, no strip counts")
     p.add_argument("--first", action="append", default=[], metavar="COLUMN", help="the reference column")
     p.add_argument("--strips", type=lambda s: [int(v) for v in s.split(",")], default=[1, 2, 3, 4])
+    p.add_argument("--order", type=lambda s: [int(v) for v in s.split(",")], default=[],
+                   help="orders of the strips of consecutive colour rows (1 joined, 2 chained): a column each")
     p.add_argument("--rounds", type=int, default=4)
     p.add_argument("--key", default="ms_per_step")
     p.add_argument("--dump", default=None, metavar="DIR")
     p.add_argument("bench_args", nargs=argparse.REMAINDER)
     q = sub.add_parser("overlap")
     q.add_argument("trace")
+    q.add_argument("--colours", type=int, default=121, help="active colours of a sweep (11 x 11 taps: 121)")
+    q.add_argument("--colour-rows", type=int, default=11, help="colour rows of a sweep")
     a = ap.parse_args()
     if a.cmd == "overlap":
-        return overlap(a.trace)
+        return overlap(a.trace, a.colours, a.colour_rows)
     rest = a.bench_args[1:] if a.bench_args[:1] == ["--"] else a.bench_args
     if not a.first:
         a.first = [a.plain[0]] if a.plain else ["tree/1"]
