@@ -176,8 +176,11 @@ class NoiseChain(object):
 FSF5 = np.outer([0.1, 0.2, 0.4, 0.2, 0.1], [0.15, 0.2, 0.3, 0.2, 0.15])
 STEP_SEED, STEP_SWEEP = 77, 1
 # odd depth and pad channel | a plain one | several blocks | three lane steps per spectrum | more
-# spaxels (1147) than streams, and no multiple of them
-STEP_SHAPES = [(13, 5, 7), (32, 6, 5), (21, 30, 24), (300, 4, 4), (6, 37, 31)]
+# spaxels (1147) than streams, and no multiple of them | 5625 spaxels: k_noise_sums' outer loop
+# (sp += 4 * STREAMS) takes a second trip, in which every stream adds a fifth spaxel and streams
+# 0 .. 504 a sixth (4097 .. 5120 spaxels would only partly fill the trip's first group), at an odd
+# depth with its pad channel
+STEP_SHAPES = [(13, 5, 7), (32, 6, 5), (21, 30, 24), (300, 4, 4), (6, 37, 31), (5, 75, 75)]
 GROUPINGS = ("channel", "cube", "three")
 
 

@@ -18,6 +18,7 @@ import deconv3d_amd as d3d
 from deconv3d_amd import _lib, regions, tiling
 from deconv3d_amd.spread_functions import ImageFieldSpreadFunction, VectorLineSpreadFunction
 from oracle import deconv3d_oracle as O
+from tests import composed_oracle as CO
 from tests import noise_oracle as NO
 from tests.cases import make_case
 from tests.test_gpu_run import synthetic_cube
@@ -348,12 +349,15 @@ def test_inflated_channels_are_recovered():
 # ---- 9. with the other keywords ----------------------------------------------------------------------------------
 
 def test_runs_with_adaptation_prior_histograms_and_regions(tmp_path):
+    """The keywords together, one sweep per device call and 64: every output bit for bit the same; the
+    first six sweeps (draws after 2, 4 and 6, the prior on) are tests/composed_oracle.py's at 1e-9."""
     inst, cube, var, _, _ = synthetic_cube(D=16, H=9, W=9, seed=4)
-    run = d3d.Run(cube, inst, variance=var, seed=3, min_acceptance_rate=0., max_iterations=60, refresh_every=25,
-                  noise=dict(per=np.arange(16) // 4, every=2, shape=1., rate=1., spaxels="unmasked"),
-                  adapt_sweeps=20, adapt_window=10, smoothness=dict(c=1.),
-                  posterior_burn_in=20, posterior_histograms=dict(pilot=10, span=6.),
-                  regions=regions.blocks((9, 9), 3))
+    kw = dict(variance=var, seed=3, min_acceptance_rate=0., max_iterations=60, refresh_every=25,
+              noise=dict(per=np.arange(16) // 4, every=2, shape=1., rate=1., spaxels="unmasked"),
+              adapt_sweeps=20, adapt_window=10, smoothness=dict(c=1.),
+              posterior_burn_in=20, posterior_histograms=dict(pilot=10, span=6.),
+              regions=regions.blocks((9, 9), 3))
+    run = d3d.Run(cube, inst, sweeps_per_call=64, **kw)
     assert np.isfinite(run.chain).all() and np.isfinite(run.parameters).all()
     assert run.noise.count == 29 and run.noise.scale.shape == (29, 4)                    # sweeps 2, 4 .. 58
     assert np.isfinite(run.noise.scale).all() and np.all(run.noise.scale > 0.)
@@ -365,6 +369,18 @@ def test_runs_with_adaptation_prior_histograms_and_regions(tmp_path):
     assert np.isfinite(run.jump_scale).all() and run.adapted_until == 20
     run.noise.save(str(tmp_path / "n"))
     assert np.load(str(tmp_path / "n_noise.npz"))["scale"].shape == (29, 4)
+    one = d3d.Run(cube, inst, sweeps_per_call=1, **kw)
+    a, b = CO.run_outputs(run), CO.run_outputs(one)
+    assert sorted(a) == sorted(b) and "noise_scale" in a
+    for k in sorted(a):
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+    ft = CO.features_of(lam=(0., 1., 0.), adapt=dict(target=0.25, window=10, last=20, gain=2.0, range=(1e-3, 1e3)),
+                        noise=dict(group=np.arange(16) // 4, every=2, start=0, shape=1., rate=1.,
+                                   spaxels=np.asarray(run.mask) == 1))
+    want, co = CO.chain_of_run(run, cube.data, var, inst.fsf.as_image(cube), inst.lsf.as_vector(cube), ft, 6)
+    assert co.noise.sweeps == [2, 4, 6] and min(m.min() for m in co.noise.margins) > 1e-9
+    np.testing.assert_allclose(run.chain[:7], want, rtol=1e-9, atol=1e-9)
+    np.testing.assert_allclose(run.noise.scale[:3], co.noise.scale(), rtol=1e-9, atol=0.)
 
 
 # ---- 10. refusals ---------------------------------------------------------------------------------------------------

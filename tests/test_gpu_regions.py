@@ -17,6 +17,7 @@ import pytest
 
 import deconv3d_amd as d3d
 from deconv3d_amd import _lib, posterior, regions
+from oracle import deconv3d_oracle as O
 from tests import region_oracle as RO
 from tests import tabulated_oracle as TO
 from tests.cases import make_case
@@ -259,9 +260,60 @@ def test_a_multiplet_takes_its_flux_factor_and_its_shape(line):
     assert not np.array_equal(series[..., 0], single[..., 0])
 
 
+# ---- 3b. regions of more than 64 chunks: the folds' second trips -----------------------------------
+
+def wide_field():
+    """96 x 96 x 7 (odd depth, 3 x 3 taps) with a label map and a mask that give, in row-major order:
+    region 1 of exactly 4096 unmasked members (64 full chunks: region_chunk_sums' loop ends on its
+    boundary, k_region_spectra_fold's unroll by 32 has no remainder); region 2 of 4161 unmasked members
+    with every seventh spaxel of its stretch masked (66 chunks, the last of one member: a second trip of
+    two partials and 62 padded lanes, a remainder of two); region 3 of one spaxel; region 4 whose
+    members are all masked."""
+    D, H, W = 7, 96, 96
+    fsf = np.outer([0.25, 0.5, 0.25], [0.2, 0.6, 0.2])
+    lsf = O.gaussian_lsf_vector(D, 0.9088)
+    data, var, _, _, init, min_b, max_b = O.synthetic_case(D, H, W, fsf, lsf, seed=96)
+    i = np.arange(H * W)
+    labels, mask = np.zeros(H * W, dtype=int), np.ones(H * W)
+    labels[:4096] = 1
+    mask[(i >= 4096) & (i % 7 == 3)] = 0
+    last = 4096 + int(np.flatnonzero(np.cumsum(mask[4096:]) == 4161)[0])
+    labels[4096:last + 1] = 2
+    labels[last + 1] = 3
+    mask[last + 1] = 1
+    labels[last + 2:last + 12] = 4
+    mask[last + 2:last + 12] = 0
+    init[..., 2] = np.maximum(init[..., 2], 0.3)
+    case = dict(D=D, H=H, W=W, fsf=fsf, lsf=lsf, data=data, var=var, mask=mask.reshape(H, W), init=init,
+                min_b=min_b, max_b=max_b)
+    return case, labels.reshape(H, W)
+
+
+@pytest.mark.parametrize("line", ["single", "doublet"])
+def test_regions_of_64_and_66_chunks_fold_past_the_first_trip(line):
+    """Parameters set directly, three samples through d3d_post_accumulate: the sizes, the scalars bit
+    for bit, the spectra and their Welford moments at the spectra tests' bars."""
+    case, labels = wide_field()
+    mask = live_mask(case)
+    assert np.array_equal(mask, case["mask"])
+    K = 4
+    maps = random_params(case, np.random.default_rng(12), 3)
+    with engine_for(case, line) as eng:
+        eng.post_begin(0)
+        eng.region_begin(labels, K, capacity=3, spectra=True)
+        mean, _ = check_spectra(eng, maps, labels, mask, K, case["D"], RO.gaussian_unit_line(*LINES[line]),
+                                "wide %s" % line)
+        series, _, _, sizes = eng.region_get()
+    assert sizes.tolist() == [4096, 4161, 1, 0]
+    assert (labels == 4).sum() == 10 and ((labels == 2) & (mask == 0)).sum() > 600
+    np.testing.assert_array_equal(series, RO.series(maps, labels, mask, K, flux_k_of(line)))
+    assert (series[:, 3, 0] == 0.).all() and np.isnan(series[:, 3, 1:]).all()
+    assert (mean[3] == 0.).all() and (mean[:2].max(axis=1) > 0.).all()
+
+
 # ---- 4. chain paths -----------------------------------------------------------------------------
 
-BLOCKS = regions.blocks((16, 16), 4)
+BLOCKS =regions.blocks((16, 16), 4)
 
 
 def watched(case, calls, capacity=10, seed=4321, line="single"):

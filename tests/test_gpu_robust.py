@@ -14,6 +14,7 @@ import deconv3d_amd as d3d
 from deconv3d_amd import _lib, regions, tiling
 from deconv3d_amd.spread_functions import ImageFieldSpreadFunction, VectorLineSpreadFunction
 from oracle import deconv3d_oracle as O
+from tests import composed_oracle as CO
 from tests import robust_oracle as RO
 from tests.cases import make_case
 from tests.test_gpu_run import synthetic_cube
@@ -304,11 +305,14 @@ def test_spiked_voxels_are_downweighted_and_the_flux_map_improves():
 # ---- 9. with the other keywords ----------------------------------------------------------------------------------
 
 def test_runs_with_adaptation_prior_histograms_and_regions():
+    """The keywords together, one sweep per device call and 64: every output bit for bit the same; the
+    first six sweeps (draws after 2, 4 and 6, the prior on) are tests/composed_oracle.py's at 1e-9."""
     inst, cube, var, _, _ = synthetic_cube(D=16, H=9, W=9, seed=4)
-    run = d3d.Run(cube, inst, variance=var, seed=3, min_acceptance_rate=0., max_iterations=60, refresh_every=25,
-                  robust=dict(nu=5, every=2), adapt_sweeps=20, adapt_window=10, smoothness=dict(c=1.),
-                  posterior_burn_in=20, posterior_histograms=dict(pilot=10, span=6.),
-                  regions=regions.blocks((9, 9), 3))
+    kw = dict(variance=var, seed=3, min_acceptance_rate=0., max_iterations=60, refresh_every=25,
+              robust=dict(nu=5, every=2), adapt_sweeps=20, adapt_window=10, smoothness=dict(c=1.),
+              posterior_burn_in=20, posterior_histograms=dict(pilot=10, span=6.),
+              regions=regions.blocks((9, 9), 3))
+    run = d3d.Run(cube, inst, sweeps_per_call=64, **kw)
     assert np.isfinite(run.chain).all() and np.isfinite(run.parameters).all()
     assert run.robust.count == 20 and np.isfinite(run.robust.weight_mean).all()       # sweeps 20, 22 .. 58
     assert np.all(run.robust.weight_mean > 0.) and np.isfinite(run.robust.weights).all()
@@ -316,6 +320,16 @@ def test_runs_with_adaptation_prior_histograms_and_regions():
     assert np.isfinite(run.posterior.histograms.median).all()
     assert np.isfinite(run.posterior.regions.flux).all()
     assert np.isfinite(run.jump_scale).all() and run.adapted_until == 20
+    one = d3d.Run(cube, inst, sweeps_per_call=1, **kw)
+    a, b = CO.run_outputs(run), CO.run_outputs(one)
+    assert sorted(a) == sorted(b) and "robust_weight_mean" in a
+    for k in sorted(a):
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+    ft = CO.features_of(lam=(0., 1., 0.), robust=dict(nu=5, every=2, start=0, accumulate_from=20),
+                        adapt=dict(target=0.25, window=10, last=20, gain=2.0, range=(1e-3, 1e3)))
+    want, co = CO.chain_of_run(run, cube.data, var, inst.fsf.as_image(cube), inst.lsf.as_vector(cube), ft, 6)
+    assert co.rescale_due(6) and not co.rescale_due(5) and not np.array_equal(co.ivar, co.pb["i0"])
+    np.testing.assert_allclose(run.chain[:7], want, rtol=1e-9, atol=1e-9)
 
 
 # ---- 10. refusals ---------------------------------------------------------------------------------------------------

@@ -30,6 +30,23 @@ def test_oracle_sums_agree_with_fsum(n):
         assert abs(got - want) <= bound
 
 
+def test_oracle_sum_of_66_chunks_agrees_with_fsum():
+    """4161 terms: 65 full chunks and one of a single term, the largest region of
+    tests/test_gpu_regions.py's wide field -- within n eps sum |terms| of the exactly rounded sum."""
+    n = 4161
+    rng = np.random.default_rng(n)
+    for scale in (1.0, 1e-8):
+        terms = rng.normal(size=n) * np.exp(scale * rng.normal(size=n))
+        got = RO.chunked_sum(terms)
+        want = math.fsum(terms)
+        bound = n * np.finfo(np.float64).eps * math.fsum(np.abs(terms))
+        print("n = %d: |d| = %.3g (bound %.3g)" % (n, abs(got - want), bound))
+        assert abs(got - want) <= bound
+    # (and the chunking is what it says: 66 partials, the last a single term)
+    parts = [RO.fold_by_halves(terms[m:m + RO.CHUNK]) for m in range(0, n, RO.CHUNK)]
+    assert len(parts) == 66 and parts[-1] == terms[-1]
+
+
 def test_oracle_fold_by_halves_is_the_xor_butterfly():
     """v[:32] + v[32:], ... is what lane 0 of the xor-butterfly v[l] += v[l ^ d], d = 32 .. 1, holds."""
     rng = np.random.default_rng(3)
