@@ -1,5 +1,8 @@
 // C ABI of libdeconv3d_hip.so -- see include/deconv3d_hip.h.
-// Host-side context, device memory, work lists, options, halo exchange.  gfx950 only.
+// Host-side context, device memory, options, halo exchange.  What can be decided without a device is
+// decided in host-only headers, each proved by a stand-alone program on the CPU, and only executed
+// here: the work lists and every part's launch forms (d3d_worklists.h -> build_colour_lists), the
+// forms of the taps (d3d_taps.h -> set_taps_impl).  gfx950 only.
 #include "d3d_ctx.h"
 
 #include <dlfcn.h>
@@ -22,6 +25,42 @@ int fail(int code, const char *fmt, ...) {
     va_end(ap);
     g_err = buf;
     return code;
+}
+
+d3d_worklists::Input worklist_input(const d3d_ctx *c) {
+    d3d_worklists::Input in;
+    in.H = c->H;
+    in.W = c->W;
+    in.Dp = c->Dp;
+    in.fh = c->fh;
+    in.fw = c->fw;
+    in.gy0 = c->gy0;
+    in.gx0 = c->gx0;
+    in.owned = {c->oy0, c->oy1, c->ox0, c->ox1};
+    in.tiled = c->tiled;
+    in.part_rects = c->part_rects.data();
+    in.part_phase = c->part_phase.data();
+    in.n_part_rects = (int)c->part_rects.size();
+    in.mask = c->h_mask.data();
+    in.flow_grid = c->flow_grid;
+    in.cube_elems = c->cube_elems;
+    in.ws_max_dp = d3d::MH_WS_MAX_DP;
+    in.mh_zb = c->mh_zb;
+    in.deep = c->deep;
+    in.mh_defer = c->mh_defer;
+    in.mh_layers_cfg = c->mh_layers_cfg;
+    in.mh_layers_forced = c->mh_layers_forced;
+    in.mh_zigzag = c->mh_zigzag;
+    in.mh_wide = c->mh_wide;
+    in.mh_small = c->mh_small;
+    in.mh_props = c->mh_props;
+    in.strips_opt = c->mh_strips_opt;
+    in.strip_order_opt = c->mh_strip_order_opt;
+    in.chain_opt = c->mh_chain_opt != 0;
+    in.flow = c->mh_flow != 0;
+    in.pair = c->mh_pair != 0;
+    in.uniform = c->ivar_is_uniform && c->uniform_fast_path;
+    return in;
 }
 }  // namespace d3dh
 
@@ -148,269 +187,139 @@ void pick_mh_geometry(d3d_ctx *c) {
     c->mh_layers = c->mh_layers_cfg;
 }
 
-int floor_div(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+// The kernels read a list entry as an int4 {y, x, real, -}: the upload is one copy of the vector.
+static_assert(sizeof(d3d_worklists::Entry) == sizeof(int4) && offsetof(d3d_worklists::Entry, y) == offsetof(int4, x) &&
+                  offsetof(d3d_worklists::Entry, x) == offsetof(int4, y) &&
+                  offsetof(d3d_worklists::Entry, real) == offsetof(int4, z),
+              "d3d_worklists::Entry is not laid out as an int4");
 
-// Work lists of every (part, colour class).  Colour classes are GLOBAL:
-// (cy,cx) = ((y+gy0) mod fh, (x+gx0) mod fw).  A list holds the part's real
-// spaxels (inside the part, unmasked) first, then the VIRTUAL lattice positions:
-// every other point of the class's lattice whose window intersects the part's
-// domain (masked, in another part, or up to one period outside the cube), so that
-// the windows of a launch tile the domain exactly.
-int build_colour_lists(d3d_ctx *c) {
-    const int ncol = c->fh * c->fw;
-    const int fhh = (c->fh - 1) / 2, fhw = (c->fw - 1) / 2;
-    // parts: as set by d3d_set_parts, else one part = the owned rectangle
-    c->parts.clear();
-    if (c->part_rects.empty()) {
-        d3d_ctx::Part pt;
-        pt.y0 = c->oy0;
-        pt.y1 = c->oy1;
-        pt.x0 = c->ox0;
-        pt.x1 = c->ox1;
-        c->parts.push_back(pt);
-        c->n_phases = 1;
-    } else {
-        c->n_phases = 1;
-        for (size_t i = 0; i < c->part_rects.size(); ++i) {
-            d3d_ctx::Part pt;
-            pt.y0 = c->part_rects[i].x;
-            pt.y1 = c->part_rects[i].y;
-            pt.x0 = c->part_rects[i].z;
-            pt.x1 = c->part_rects[i].w;
-            pt.phase = c->part_phase[i];
-            c->n_phases = std::max(c->n_phases, pt.phase + 1);
-            c->parts.push_back(pt);
-        }
-    }
-    std::vector<int4> list;
-    list.reserve(c->spx.size());
-    c->colour_real.assign(ncol, 0);
-    for (d3d_ctx::Part &pt : c->parts) {
-        pt.dy0 = std::max(pt.y0 - fhh, 0);
-        pt.dy1 = std::min(pt.y1 + fhh, c->H);
-        pt.dx0 = std::max(pt.x0 - fhw, 0);
-        pt.dx1 = std::min(pt.x1 + fhw, c->W);
-        pt.off.assign(ncol + 1, 0);
-        pt.real.assign(ncol, 0);
-        const bool empty = pt.y1 <= pt.y0 || pt.x1 <= pt.x0;
-        int most = 0;
-        int ord = 0;  // ordinal of the colour among the part's active ones
-        for (int cy = 0; cy < c->fh; ++cy)
-            for (int cx = 0; cx < c->fw; ++cx) {
-                const int col = cy * c->fw + cx;
-                const int ly = ((cy - c->gy0) % c->fh + c->fh) % c->fh;  // local residues
-                const int lx = ((cx - c->gx0) % c->fw + c->fw) % c->fw;
-                pt.off[col] = (int)list.size();
-                if (empty) continue;
-                // first lattice coordinates whose window reaches the domain
-                const int ys = ly + c->fh * floor_div(pt.dy0 - fhh - ly + c->fh - 1, c->fh);
-                const int xs = lx + c->fw * floor_div(pt.dx0 - fhw - lx + c->fw - 1, c->fw);
-                for (int y = ys; y - fhh < pt.dy1; y += c->fh)
-                    for (int x = xs; x - fhw < pt.dx1; x += c->fw)
-                        if (y >= pt.y0 && y < pt.y1 && x >= pt.x0 && x < pt.x1 &&
-                            c->h_mask[(size_t)y * c->W + x])
-                            list.push_back(make_int4(y, x, 1, 0));
-                pt.real[col] = (int)list.size() - pt.off[col];
-                c->colour_real[col] += pt.real[col];
-                for (int y = ys; y - fhh < pt.dy1; y += c->fh)
-                    for (int x = xs; x - fhw < pt.dx1; x += c->fw) {
-                        const bool is_real = y >= pt.y0 && y < pt.y1 && x >= pt.x0 && x < pt.x1 &&
-                                             c->h_mask[(size_t)y * c->W + x];
-                        if (!is_real) list.push_back(make_int4(y, x, 0, 0));
-                    }
-                // Zig-zag over the cube as well: a launch of more workgroups than the chip
-                // holds runs them in list order, so every other colour starts where its
-                // predecessor ended -- on the lines still in the Infinity Cache.  (Windows of
-                // one colour are independent: the order changes no result.)  Only then: in a
-                // launch that is resident at once, workgroup i of every colour runs on the same
-                // XCD, whose L2 still holds its predecessor's window (64^3: 12.3 vs 12.6 us per
-                // launch with the lists reversed).
-                if (pt.real[col] > 0) {
-                    // (the z-blocked kernels launch a workgroup per window AND 256-channel block)
-                    const long n_all_col =
-                        ((long)list.size() - pt.off[col]) * (c->mh_zb ? (c->Dp + 255) / 256 : 1);
-                    if (c->mh_zigzag && (ord & 1) && n_all_col > c->flow_grid) {
-                        std::reverse(list.begin() + pt.off[col], list.begin() + pt.off[col] + pt.real[col]);
-                        std::reverse(list.begin() + pt.off[col] + pt.real[col], list.end());
-                    }
-                    ++ord;
-                }
-                most = std::max(most, (int)list.size() - pt.off[col]);
-            }
-        pt.off[ncol] = (int)list.size();
-        // Launches that do not fill the chip are latency chains: a second layer only adds
-        // to their setup (64^3: 12.6 -> 13.0 us per colour), so they keep one.
-        const long most_wgs = (long)most * (c->mh_zb ? (c->Dp + 255) / 256 : 1);
-        pt.layers = (!c->mh_layers_forced && most_wgs < c->flow_grid / 2) ? 1 : c->mh_layers_cfg;
-        const bool partitioned = c->tiled || !c->part_rects.empty();
-        pt.wide = pt.layers == 1 && c->mh_wide && partitioned && c->Dp == 128 && most > 0 &&
-                  most <= c->flow_grid / 4 && c->mh_defer == 1;
-        pt.small = pt.layers == 1 && most_wgs < c->flow_grid / 2;
-        // Lattice-row strips (d3d_strips.h): the whole cube of one context, the wave-specialised
-        // deferred kernels, launches that fill the chip (a latency-bound launch gains nothing; a
-        // forced count lifts that condition).  Every colour's list strip-major; within a strip the
-        // order stays what it was above, real spaxels first.
-        pt.strips = 1;
-        pt.soff.clear();
-        pt.sreal.clear();
-        {
-            // (automatic: not the uniform-variance kernels, whose launches are shorter and lose --
-            // profiles/sweep_strips_ab.txt)
-            const bool uv = c->ivar_is_uniform && c->uniform_fast_path;
-            const int want = c->mh_strips_opt >= 2 ? c->mh_strips_opt
-                             : (c->mh_strips_opt == 0 && most_wgs >= c->flow_grid / 2 && !uv) ? MH_STRIPS_AUTO : 1;
-            d3d_strips::Plan plan;
-            if (want >= 2 && !empty && !partitioned && c->mh_defer == 1 && (c->Dp <= d3d::MH_WS_MAX_DP || c->mh_zb) &&
-                !d3dh::mh_part_uses_tables(c, pt) && !c->mh_chain_opt && !c->mh_flow && !c->mh_pair &&
-                d3d_strips::plan(c->H, c->fh, want, &plan)) {
-                pt.strips = plan.S;
-                pt.soff.assign((size_t)ncol * (plan.S + 1), 0);
-                pt.sreal.assign((size_t)ncol * plan.S, 0);
-                for (int col = 0; col < ncol; ++col) {
-                    const int cy = col / c->fw;  // == the local residue (not tiled)
-                    auto key = [&](const int4 &e) {
-                        return 2 * d3d_strips::strip_of_row(plan, d3d_strips::lattice_row(e.x, cy, c->fh)) + (e.z ? 0 : 1);
-                    };
-                    const auto b = list.begin() + pt.off[col], e = list.begin() + pt.off[col + 1];
-                    for (auto it = b; it != e; ++it)
-                        if (key(*it) < 0) return fail(D3D_ERR_HIP, "internal: lattice row outside the strips");
-                    std::stable_sort(b, e, [&](const int4 &p, const int4 &q) { return key(p) < key(q); });
-                    int *so = &pt.soff[(size_t)col * (plan.S + 1)];
-                    for (auto it = b; it != e; ++it) {
-                        const int k = key(*it);
-                        ++so[k / 2 + 1];
-                        if (!(k & 1)) ++pt.sreal[(size_t)col * plan.S + k / 2];
-                    }
-                    for (int s = 0; s < plan.S; ++s) so[s + 1] += so[s];
-                }
-            }
-        }
-        // The strips chained from colour row to colour row (d3d_strip_order.h) where the option asks for
-        // it and the schedule can be built: every active colour row holds pt.layers colours at least.
-        pt.order = d3d_strip_order::Schedule();
-        if (pt.strips > 1 && (c->mh_strip_order_opt ? c->mh_strip_order_opt : MH_STRIP_ORDER_AUTO) == 2) {
-            std::vector<int> active;
-            for (int col = 0; col < ncol; ++col)
-                if (pt.real[col] > 0) active.push_back(col);
-            (void)d3d_strip_order::build(pt.strips, c->fw, active, pt.layers, &pt.order);
-        }
-        // k_mh_chain: whole sweeps of the part in one launch of persistent workgroups, one per
-        // lattice slot -- where every slot is resident at once (one workgroup per CU) and a
-        // thread can hold its share of the window in registers
-        pt.chain = false;
-        pt.K = 0;
-        pt.last_col = -1;
-        for (int col = 0; col < ncol; ++col)
-            if (pt.real[col] > 0) {
-                ++pt.K;
-                pt.last_col = col;
-            }
 #ifdef D3D_EXPERIMENTS
-        if (!empty && pt.K > 0) {
-            const int cus = c->flow_grid / 4;
-            const int fhh_ = (c->fh - 1) / 2, fhw_ = (c->fw - 1) / 2;
-            // slot grid over the window centres [dy0 - fhh, dy1 + fhh) x [.., dx1 + fhw), its
-            // columns aligned with the colour order: slot column boundaries at the local
-            // residue of colour cx = 0, so that a slot's window moves right by one column
-            // per colour class along a row of colours
-            const int lx0 = ((0 - c->gx0) % c->fw + c->fw) % c->fw;
-            pt.chain_sx0 = (pt.dx0 - fhw_) - ((((pt.dx0 - fhw_) - lx0) % c->fw + c->fw) % c->fw);
-            pt.n_sy = (pt.dy1 - pt.dy0 + 2 * c->fh - 2) / c->fh;
-            pt.n_sx = (pt.dx1 + fhw_ - 1 - pt.chain_sx0) / c->fw + 1;
-            (void)fhh_;
-            // fw thread groups of HL threads hold the window's columns; + one deciding wavefront
-            pt.chain_ns = c->fw * c->HL;
-            const int nt = (pt.chain_ns + 63) / 64 * 64 + 64;
-            const bool fh_ok = c->fh == 3 || c->fh == 5 || c->fh == 7 || c->fh == 9 || c->fh == 11;
-            const double g_bytes = 4.0 * pt.K * pt.n_sy * pt.n_sx * c->Dp * 8.0;
-            const size_t lds = d3d::mh_chain_lds_doubles(c->fw, c->Dp, c->N, ncol, pt.K, nt / 64 - 1) * 8;
-            pt.chain = c->mh_chain_opt == 1 && c->mh_defer == 1 && c->Dp <= 256 && pt.layers == 1 &&
-                       (long)pt.n_sy * pt.n_sx <= cus && fh_ok && c->fw >= 3 && nt <= MH_CHAIN_NT &&
-                       c->Dp <= pt.chain_ns && lds <= (size_t)160 * 1024 && g_bytes <= 512e6 &&
-                       c->cube_elems * sizeof(double) < (size_t(1) << 31);
-        }
-#endif
-    }
-    // device tables of the chain form
-    {
-        size_t need_slots = 0, need_G = 0;
-        std::vector<int2> cols((size_t)c->parts.size() * ncol, make_int2(0, 0));
-        bool any = false;
-        for (size_t pi = 0; pi < c->parts.size(); ++pi) {
-            const d3d_ctx::Part &pt = c->parts[pi];
-            if (!pt.chain) continue;
-            any = true;
-            need_slots = std::max(need_slots, (size_t)pt.n_sy * pt.n_sx);
-            need_G = std::max(need_G, (size_t)4 * pt.K * pt.n_sy * pt.n_sx * c->Dp);  // G rows | lines
-            int k = 0;
-            for (int col = 0; col < ncol; ++col)
-                if (pt.real[col] > 0)  // local residues of the (global) colour class
-                    cols[pi * ncol + k++] = make_int2(((col / c->fw - c->gy0) % c->fh + c->fh) % c->fh,
-                                                      ((col % c->fw - c->gx0) % c->fw + c->fw) % c->fw);
-        }
-        if (any) {
-            HIP_TRY(c->chain_cols.reserve(cols.size()));
-            HIP_TRY(hipMemcpyAsync(c->chain_cols, cols.data(), cols.size() * sizeof(int2),
-                                   hipMemcpyHostToDevice, c->stream));
-            if (2 * need_slots > c->chain_flags.size()) {
-                HIP_TRY(c->chain_flags.alloc(2 * need_slots));
-                HIP_TRY(hipMemsetAsync(c->chain_flags, 0, 2 * need_slots * sizeof(unsigned), c->stream));
-                c->chain_base = 0;
+// k_mh_chain: whole sweeps of a part in one launch of persistent workgroups, one per lattice slot
+// -- where every slot is resident at once (one workgroup per CU) and a thread can hold its share of
+// the window in registers.  The slot grid of every part, and the device tables of those that take it.
+int chain_tables(d3d_ctx *c, const d3d_worklists::Input &in) {
+    const int ncol = c->fh * c->fw;
+    const int fhw = (c->fw - 1) / 2;
+    size_t need_slots = 0, need_G = 0;
+    std::vector<int2> cols((size_t)c->parts.size() * ncol, make_int2(0, 0));
+    bool any = false;
+    for (size_t pi = 0; pi < c->parts.size(); ++pi) {
+        d3d_ctx::Part &pt = c->parts[pi];
+        if (pt.y1 <= pt.y0 || pt.x1 <= pt.x0 || pt.K <= 0) continue;
+        const int cus = c->flow_grid / 4;
+        // slot grid over the window centres [dy0 - fhh, dy1 + fhh) x [.., dx1 + fhw), its
+        // columns aligned with the colour order: slot column boundaries at the local
+        // residue of colour cx = 0, so that a slot's window moves right by one column
+        // per colour class along a row of colours
+        int ly0, lx0;
+        d3d_worklists::local_residue(in, 0, &ly0, &lx0);
+        pt.chain_sx0 = (pt.dx0 - fhw) - ((((pt.dx0 - fhw) - lx0) % c->fw + c->fw) % c->fw);
+        pt.n_sy = (pt.dy1 - pt.dy0 + 2 * c->fh - 2) / c->fh;
+        pt.n_sx = (pt.dx1 + fhw - 1 - pt.chain_sx0) / c->fw + 1;
+        // fw thread groups of HL threads hold the window's columns; + one deciding wavefront
+        pt.chain_ns = c->fw * c->HL;
+        const int nt = (pt.chain_ns + 63) / 64 * 64 + 64;
+        const bool fh_ok = c->fh == 3 || c->fh == 5 || c->fh == 7 || c->fh == 9 || c->fh == 11;
+        const double g_bytes = 4.0 * pt.K * pt.n_sy * pt.n_sx * c->Dp * 8.0;
+        const size_t lds = d3d::mh_chain_lds_doubles(c->fw, c->Dp, c->N, ncol, pt.K, nt / 64 - 1) * 8;
+        pt.chain = c->mh_chain_opt == 1 && c->mh_defer == 1 && c->Dp <= 256 && pt.layers == 1 &&
+                   (long)pt.n_sy * pt.n_sx <= cus && fh_ok && c->fw >= 3 && nt <= MH_CHAIN_NT &&
+                   c->Dp <= pt.chain_ns && lds <= (size_t)160 * 1024 && g_bytes <= 512e6 &&
+                   c->cube_elems * sizeof(double) < (size_t(1) << 31);
+        if (!pt.chain) continue;
+        any = true;
+        need_slots = std::max(need_slots, (size_t)pt.n_sy * pt.n_sx);
+        need_G = std::max(need_G, (size_t)4 * pt.K * pt.n_sy * pt.n_sx * c->Dp);  // G rows | lines
+        int k = 0;
+        for (int col = 0; col < ncol; ++col)
+            if (pt.real[col] > 0) {  // local residues of the (global) colour class
+                int2 &r = cols[pi * ncol + k++];
+                d3d_worklists::local_residue(in, col, &r.x, &r.y);
             }
-            HIP_TRY(c->chain_G.reserve(need_G));
-            HIP_TRY(hipStreamSynchronize(c->stream));  // `cols` goes out of scope
-        }
     }
+    if (any) {
+        HIP_TRY(c->chain_cols.reserve(cols.size()));
+        HIP_TRY(hipMemcpyAsync(c->chain_cols, cols.data(), cols.size() * sizeof(int2),
+                               hipMemcpyHostToDevice, c->stream));
+        if (2 * need_slots > c->chain_flags.size()) {
+            HIP_TRY(c->chain_flags.alloc(2 * need_slots));
+            HIP_TRY(hipMemsetAsync(c->chain_flags, 0, 2 * need_slots * sizeof(unsigned), c->stream));
+            c->chain_base = 0;
+        }
+        HIP_TRY(c->chain_G.reserve(need_G));
+        HIP_TRY(hipStreamSynchronize(c->stream));  // `cols` goes out of scope
+    }
+    return 0;
+}
+
+// tables of the dataflow kernel (unpartitioned contexts only): active colours in
+// order, their ticket ranges, and per colour the map lattice point -> index in its list
+int flow_tables(d3d_ctx *c, const std::vector<d3d_worklists::Entry> &list) {
+    const int ncol = c->fh * c->fw;
+    if (c->tiled || c->parts.size() != 1 || list.size() > c->flow_cap_items) return 0;
+    const d3d_ctx::Part &pt = c->parts[0];
+    std::vector<int4> ents, cols;
+    std::vector<int> lat((size_t)ncol * c->flow_LY * c->flow_LX, -1);
+    for (int col = 0; col < ncol; ++col) {
+        if (pt.real[col] <= 0) continue;
+        const int cy = col / c->fw, cx = col % c->fw;  // == local residues (not tiled)
+        const int n_all = pt.off[col + 1] - pt.off[col];
+        const int k = (int)cols.size();
+        cols.push_back(make_int4((int)ents.size(), cy, cx, 0));
+        for (int i = 0; i < n_all; ++i) {
+            const d3d_worklists::Entry e = list[(size_t)pt.off[col] + i];
+            const int iy = (e.y - cy) / c->fh + 1, ix = (e.x - cx) / c->fw + 1;
+            if (iy < 0 || iy >= c->flow_LY || ix < 0 || ix >= c->flow_LX)
+                return fail(D3D_ERR_HIP, "internal: lattice index out of range");
+            lat[((size_t)k * c->flow_LY + iy) * c->flow_LX + ix] = i;
+            ents.push_back(make_int4(e.y, e.x, e.real, k));
+        }
+        c->flow_last_cy = cy;
+        c->flow_last_cx = cx;
+    }
+    c->flow_K = (int)cols.size();
+    c->flow_items = (int)ents.size();
+    c->flow_first.clear();
+    c->flow_colour.clear();
+    for (const int4 &cc : cols) {
+        c->flow_first.push_back(cc.x);
+        c->flow_colour.push_back(cc.y * c->fw + cc.z);
+    }
+    c->flow_first.push_back(c->flow_items);
+    if (c->flow_K > 0) {
+        HIP_TRY(hipMemcpyAsync(c->flow_ent, ents.data(), ents.size() * sizeof(int4),
+                               hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->flow_col, cols.data(), cols.size() * sizeof(int4),
+                               hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->flow_lat, lat.data(),
+                               (size_t)c->flow_K * c->flow_LY * c->flow_LX * sizeof(int),
+                               hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));  // the host vectors go out of scope
+    }
+    return 0;
+}
+#endif
+
+// The work lists of every (part, colour class) and what every part's colour launches run as:
+// d3d_worklists.h builds and decides; here they go to the device, with the tables of the
+// experimental kernels, which read the finished lists.
+int build_colour_lists(d3d_ctx *c) {
+    const d3d_worklists::Input in = worklist_input(c);
+    std::vector<d3d_worklists::Entry> list;
+    list.reserve(c->spx.size());
+    if (d3d_worklists::build(in, &c->parts, &list, &c->colour_real, &c->n_phases))
+        return fail(D3D_ERR_HIP, "internal: lattice row outside the strips");
+#ifdef D3D_EXPERIMENTS
+    if (int rc = chain_tables(c, in)) return rc;
+#endif
     c->mh_layers = 1;
     for (const d3d_ctx::Part &pt : c->parts) c->mh_layers = std::max(c->mh_layers, pt.layers);
     HIP_TRY(c->spx.reserve(list.size()));
-    // tables of the dataflow kernel (unpartitioned contexts only): active colours in
-    // order, their ticket ranges, and per colour the map lattice point -> index in its list
     c->flow_K = 0;
     c->flow_items = 0;
     c->flow_last_cy = c->flow_last_cx = -1;
 #ifdef D3D_EXPERIMENTS
-    if (!c->tiled && c->parts.size() == 1 && list.size() <= c->flow_cap_items) {
-        const d3d_ctx::Part &pt = c->parts[0];
-        std::vector<int4> ents, cols;
-        std::vector<int> lat((size_t)ncol * c->flow_LY * c->flow_LX, -1);
-        for (int col = 0; col < ncol; ++col) {
-            if (pt.real[col] <= 0) continue;
-            const int cy = col / c->fw, cx = col % c->fw;  // == local residues (not tiled)
-            const int n_all = pt.off[col + 1] - pt.off[col];
-            const int k = (int)cols.size();
-            cols.push_back(make_int4((int)ents.size(), cy, cx, 0));
-            for (int i = 0; i < n_all; ++i) {
-                const int4 e = list[(size_t)pt.off[col] + i];
-                const int iy = (e.x - cy) / c->fh + 1, ix = (e.y - cx) / c->fw + 1;
-                if (iy < 0 || iy >= c->flow_LY || ix < 0 || ix >= c->flow_LX)
-                    return fail(D3D_ERR_HIP, "internal: lattice index out of range");
-                lat[((size_t)k * c->flow_LY + iy) * c->flow_LX + ix] = i;
-                ents.push_back(make_int4(e.x, e.y, e.z, k));
-            }
-            c->flow_last_cy = cy;
-            c->flow_last_cx = cx;
-        }
-        c->flow_K = (int)cols.size();
-        c->flow_items = (int)ents.size();
-        c->flow_first.clear();
-        c->flow_colour.clear();
-        for (const int4 &cc : cols) {
-            c->flow_first.push_back(cc.x);
-            c->flow_colour.push_back(cc.y * c->fw + cc.z);
-        }
-        c->flow_first.push_back(c->flow_items);
-        if (c->flow_K > 0) {
-            HIP_TRY(hipMemcpyAsync(c->flow_ent, ents.data(), ents.size() * sizeof(int4),
-                                   hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->flow_col, cols.data(), cols.size() * sizeof(int4),
-                                   hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->flow_lat, lat.data(),
-                                   (size_t)c->flow_K * c->flow_LY * c->flow_LX * sizeof(int),
-                                   hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));  // the host vectors go out of scope
-        }
-    }
+    if (int rc = flow_tables(c, list)) return rc;
 #endif
     if (!list.empty())
         HIP_TRY(hipMemcpyAsync(c->spx, list.data(), list.size() * sizeof(int4),
@@ -948,202 +857,37 @@ int d3d_has_experiments(void) {
 #endif
 }
 
+// d3d_taps.h analyses the taps; here what its flags say goes to the device.
 static int set_taps_impl(d3d_ctx *c, const double *fsf, const double *lsf, double thr) {
     HIP_TRY(hipSetDevice(c->device));
+    const d3d_taps::Result r = d3d_taps::analyse(c->fh, c->fw, c->D, c->N, c->H, c->W, c->HL, c->flow_grid, d3d::LSF_RL,
+                                                 fsf, lsf, thr, c->spatial_sep, c->march_hy_opt);
+    NEED(!r.lsf_empty, D3D_ERR_INVALID, "LSF has no non-zero tap");
     c->ptab_valid = false;  // (the position tables of k_mh_small hold tap values)
-    HIP_TRY(hipMemcpyAsync(c->fsf, fsf, (size_t)c->fh * c->fw * sizeof(double),
-                           hipMemcpyHostToDevice, c->stream));
-    c->fsf_symx = true;
-    for (int k = 0; k < c->fh && c->fsf_symx; ++k)
-        for (int i = 0; i < c->fw / 2; ++i)
-            if (fsf[k * c->fw + i] != fsf[k * c->fw + (c->fw - 1 - i)]) {
-                c->fsf_symx = false;
-                break;
-            }
-    c->fsf_symy = true;
-    for (int k = 0; k < c->fh / 2 && c->fsf_symy; ++k)
-        for (int i = 0; i < c->fw; ++i)
-            if (fsf[k * c->fw + i] != fsf[(c->fh - 1 - k) * c->fw + i]) {
-                c->fsf_symy = false;
-                break;
-            }
-    // outer product?  u = centre column / centre tap, v = centre row
-    {
-        const int cy = (c->fh - 1) / 2, cx = (c->fw - 1) / 2;
-        const double cc = fsf[cy * c->fw + cx];
-        double amax = 0.0;
-        for (int i = 0; i < c->fh * c->fw; ++i) amax = std::max(amax, std::fabs(fsf[i]));
-        std::vector<double> uv((size_t)c->fh + c->fw);
-        bool sep = cc != 0.0 && amax > 0.0;
-        if (sep) {
-            for (int k = 0; k < c->fh; ++k) uv[k] = fsf[k * c->fw + cx] / cc;
-            for (int m = 0; m < c->fw; ++m) uv[c->fh + m] = fsf[cy * c->fw + m];
-            for (int k = 0; k < c->fh && sep; ++k)
-                for (int m = 0; m < c->fw; ++m)
-                    if (!(std::fabs(fsf[k * c->fw + m] - uv[k] * uv[c->fh + m]) <=
-                          8.0 * 2.220446049250313e-16 * amax)) {
-                        sep = false;
-                        break;
-                    }
-        }
-        sep = sep && c->spatial_sep != 0;
-        c->fsf_sep = sep;
-        if (sep)
-            HIP_TRY(hipMemcpyAsync(c->sep_uv, uv.data(), uv.size() * sizeof(double),
-                                   hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));  // uv goes out of scope
-    }
-    if (c->fsf_symx && c->fsf_symy && c->fh == c->fw) {
-        // quadrant taps by distance from the centre: quad[a][e] = fsf[fhh-a][fhh-e] (k_conv_rows)
-        const int fhh = (c->fh - 1) / 2, nq = fhh + 1;
-        std::vector<double> quad((size_t)nq * nq);
-        c->fsf_symt = true;
-        for (int a = 0; a < nq; ++a)
-            for (int m = 0; m < nq; ++m) {
-                quad[(size_t)a * nq + m] = fsf[(fhh - a) * c->fw + (fhh - m)];
-                c->fsf_symt = c->fsf_symt &&
-                              fsf[(fhh - a) * c->fw + (fhh - m)] == fsf[(fhh - m) * c->fw + (fhh - a)];
-            }
-        HIP_TRY(hipMemcpyAsync(c->fsf_quad, quad.data(), quad.size() * sizeof(double),
-                               hipMemcpyHostToDevice, c->stream));
-        if (c->fsf_sep) {
-            // fsf = u v^T (u = centre column / centre tap, v = centre row, as sep_uv):
-            // row 0 = v by distance from the centre, row 1 = u
-            std::vector<double> qs((size_t)nq * nq, 0.0);
-            const double cc = fsf[fhh * c->fw + fhh];
-            for (int e = 0; e < nq; ++e) qs[e] = fsf[fhh * c->fw + (fhh - e)];
-            for (int a = 0; a < nq; ++a) qs[(size_t)nq + a] = fsf[(fhh - a) * c->fw + fhh] / cc;
-            HIP_TRY(hipMemcpyAsync(c->fsf_quad_sep, qs.data(), qs.size() * sizeof(double),
-                                   hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-        }
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    // Rows per strip of the march kernels: a strip is one wavefront's worth of z
-    // (64 / HL strips per wavefront when the spectrum is shorter), the chip holds
-    // two such wavefronts per SIMD, and a strip costs HY + FS - 1 row steps.  Take
-    // the HY in 12..20 that needs the fewest rounds of wavefronts and, among those,
-    // the fewest steps (300 rows: 15 -> 20 strips of 25 steps, all resident at once;
-    // 16 -> 19 strips of 26 steps).
-    {
-        const int TX = (c->fw >= 9 ? 3 : 4);
-        const long slots = 2L * (c->flow_grid > 0 ? c->flow_grid : 1024);  // 8 wavefronts per CU
-        const int per_wave = c->HL >= 64 ? 1 : 64 / (c->HL > 0 ? c->HL : 1);
-        long best_cost = -1;
-        for (int hy = 12; hy <= 20; ++hy) {
-            const long strips = (long)((c->W + TX - 1) / TX) * ((c->H + hy - 1) / hy);
-            const long waves = (strips + per_wave - 1) / per_wave;
-            const long cost = ((waves + slots - 1) / slots) * (hy + c->fh - 1);
-            if (best_cost < 0 || cost <= best_cost) {
-                best_cost = cost;
-                c->march_hy = hy;
-            }
-        }
-    }
-    if (c->march_hy_opt >= 1) c->march_hy = c->march_hy_opt;
-    std::vector<int> shift;
-    std::vector<double> weight;
-    if (lsf) {
-        // closed form of convolve_1d: lib/convolution.py:89-160, SURVEY 8(a) a3
-        const int N = c->N, D = c->D;
-        const int diff = N - D;
-        const int h = (diff & 1) ? diff / 2 + 1 : diff / 2;  // lib/convolution.py:149-153
-        double mx = 0.0, total = 0.0;
-        for (int t = 0; t < D; ++t) {
-            mx = std::fmax(mx, std::fabs(lsf[t]));
-            total += std::fabs(lsf[t]);
-        }
-        // thr >= 0: taps up to thr * max|lsf| are dropped.  thr < 0 (round 4, the python host's
-        // default -1e-16): an ERROR BOUND -- the smallest taps are dropped as long as their summed
-        // magnitude stays within |thr| * sum|lsf|, i.e. below the rounding of the fp64 sum itself.
-        // (Round 3's 1e-20 * max kept a Gaussian's tail out to 9.6 sigma, and the physics-free
-        // threshold, not the LSF, decided whether the taps fit the +-LSF_RL channels of the fused /
-        // z-blocked kernels: sigma >= 0.94 px fell off them.  The bound keeps 8.6 sigma: MUSE's
-        // 2.4-3.0 A LSF at 1.25 A per channel, sigma 0.82-1.02 px, fits.)
-        double cut = thr * mx;
-        if (thr < 0.0) {
-            std::vector<double> mag(lsf, lsf + D);
-            for (double &m : mag) m = std::fabs(m);
-            std::sort(mag.begin(), mag.end());
-            double dropped = 0.0;
-            cut = 0.0;
-            for (int t = 0; t < D && dropped + mag[t] <= -thr * total; ++t) {
-                dropped += mag[t];
-                cut = mag[t];
-            }
-            // (taps EQUAL to the largest dropped magnitude: keep the bound -- drop them only if all fit)
-            double at_cut = 0.0;
-            for (int t = 0; t < D; ++t)
-                if (std::fabs(lsf[t]) <= cut) at_cut += std::fabs(lsf[t]);
-            while (at_cut > -thr * total && cut > 0.0) {   // shrink to the next smaller magnitude
-                double next = 0.0;
-                for (int t = 0; t < D; ++t)
-                    if (mag[t] < cut) next = std::fmax(next, mag[t]);
-                cut = next;
-                at_cut = 0.0;
-                for (int t = 0; t < D; ++t)
-                    if (std::fabs(lsf[t]) <= cut) at_cut += std::fabs(lsf[t]);
-            }
-        }
-        for (int t = 0; t < D; ++t) {
-            if (!(std::fabs(lsf[t]) > cut)) continue;
-            int s = (N / 2 - h - t) % N;
-            if (s < 0) s += N;
-            shift.push_back(s);
-            weight.push_back(lsf[t]);
-        }
-        NEED(!shift.empty(), D3D_ERR_INVALID, "LSF has no non-zero tap");
-    }
-    c->ntaps = (int)shift.size();
+    auto upload = [c](auto &dst, const auto &v) {
+        return hipMemcpyAsync(dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, c->stream);
+    };
+    HIP_TRY(hipMemcpyAsync(c->fsf, fsf, (size_t)c->fh * c->fw * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    c->fsf_symx = r.symx;
+    c->fsf_symy = r.symy;
+    c->fsf_sep = r.sep;
+    c->fsf_symt = r.symt;
+    if (r.sep) HIP_TRY(upload(c->sep_uv, r.uv));
+    if (!r.quad.empty()) HIP_TRY(upload(c->fsf_quad, r.quad));
+    if (!r.quad_sep.empty()) HIP_TRY(upload(c->fsf_quad_sep, r.quad_sep));
+    c->march_hy = r.march_hy;
+    c->ntaps = (int)r.shift.size();
     // dense form for the fused epilogue: out[k] = sum_j wl[j] v[(k + j - RL) mod N]
-    c->lsf_fusable = false;
-    c->lsf_dense_ok = false;
-    c->lsf_dense_any = false;
-    if (c->ntaps) {  // any depth: taps within +-LSF_RL channels (k_spectral_blocks)
-        std::vector<double> dense(2 * d3d::LSF_RL + 1, 0.0);
-        bool ok = c->N >= 4 * d3d::LSF_RL;
-        for (size_t t = 0; ok && t < shift.size(); ++t) {
-            const int sg = shift[t] > c->N / 2 ? shift[t] - c->N : shift[t];
-            if (sg < -d3d::LSF_RL || sg > d3d::LSF_RL) ok = false;
-            else dense[sg + d3d::LSF_RL] += weight[t];
-        }
-        if (ok) {
-            HIP_TRY(hipMemcpyAsync(c->lsf_dense, dense.data(), dense.size() * sizeof(double),
-                                   hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            c->lsf_dense_any = true;
-        }
-    }
-    if (c->ntaps && c->N == c->D && c->D >= 4 * d3d::LSF_RL) {
-        std::vector<double> dense(2 * d3d::LSF_RL + 1, 0.0);
-        bool ok = true;
-        for (size_t t = 0; t < shift.size(); ++t) {
-            int sg = shift[t] > c->N / 2 ? shift[t] - c->N : shift[t];
-            if (sg < -d3d::LSF_RL || sg > d3d::LSF_RL) {
-                ok = false;
-                break;
-            }
-            dense[sg + d3d::LSF_RL] += weight[t];
-        }
-        if (ok) {
-            c->lsf_dense_sym = true;
-            for (int j = 0; j < d3d::LSF_RL; ++j)
-                c->lsf_dense_sym = c->lsf_dense_sym && dense[j] == dense[2 * d3d::LSF_RL - j];
-            HIP_TRY(hipMemcpyAsync(c->lsf_dense, dense.data(), dense.size() * sizeof(double),
-                                   hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            c->lsf_dense_ok = true;
-            // wave-private LDS forms additionally need the spectrum within one wavefront
-            c->lsf_fusable = c->HL <= 64 && 64 % c->HL == 0;
-        }
-    }
+    c->lsf_dense_any = r.dense_any;
+    c->lsf_dense_ok = r.dense_ok;
+    c->lsf_dense_sym = r.dense_sym;
+    c->lsf_fusable = r.fusable;
+    if (r.dense_any) HIP_TRY(upload(c->lsf_dense, r.dense));
     if (c->ntaps) {
-        HIP_TRY(hipMemcpyAsync(c->lsf_shift, shift.data(), shift.size() * sizeof(int),
-                               hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->lsf_weight, weight.data(), weight.size() * sizeof(double),
-                               hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(upload(c->lsf_shift, r.shift));
+        HIP_TRY(upload(c->lsf_weight, r.weight));
     }
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // `r` goes out of scope
     c->have_taps = true;
     c->err_valid = false;
     pend_clear(c);
@@ -1782,7 +1526,7 @@ int d3d_x_stamps_raw(d3d_ctx *c, long first, long nwords, unsigned long long *ou
 int d3d_mh_layers(d3d_ctx *c, int *out) {
     NEED(c && out, D3D_ERR_INVALID, "NULL argument");
     NEED(c->have_data, D3D_ERR_STATE, "data not set");
-    const bool partitioned = c->tiled || c->parts.size() > 1;
+    const bool partitioned = partitioned_sweep(c);
     const bool deferred =
         c->mh_defer &&
         (!partitioned || (c->mh_defer == 1 && (c->Dp <= d3d::MH_WS_MAX_DP || c->mh_zb)));
@@ -1834,7 +1578,7 @@ int d3d_set_parts(d3d_ctx *c, int nparts, const int *rects, const int *phases) {
          "d3d_prior_end first");
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = flush_pending(c)) return rc;
-    std::vector<int4> rr;
+    std::vector<d3d_worklists::Rect> rr;
     std::vector<int> ph;
     for (int i = 0; i < nparts; ++i) {
         const int y0 = rects[4 * i], y1 = rects[4 * i + 1], x0 = rects[4 * i + 2],
@@ -1845,10 +1589,10 @@ int d3d_set_parts(d3d_ctx *c, int nparts, const int *rects, const int *phases) {
         NEED(phases[i] >= 0 && phases[i] < D3D_PLAN_PARAMS, D3D_ERR_INVALID,
              "phase %d of part %d out of range", phases[i], i);
         for (size_t j = 0; j < rr.size(); ++j)  // parts must not overlap
-            NEED(y1 <= rr[j].x || rr[j].y <= y0 || x1 <= rr[j].z || rr[j].w <= x0 || y0 == y1 ||
-                     x0 == x1 || rr[j].x == rr[j].y || rr[j].z == rr[j].w,
+            NEED(y1 <= rr[j].y0 || rr[j].y1 <= y0 || x1 <= rr[j].x0 || rr[j].x1 <= x0 || y0 == y1 ||
+                     x0 == x1 || rr[j].y0 == rr[j].y1 || rr[j].x0 == rr[j].x1,
                  D3D_ERR_INVALID, "parts %d and %zu overlap", i, j);
-        rr.push_back(make_int4(y0, y1, x0, x1));
+        rr.push_back({y0, y1, x0, x1});
         ph.push_back(phases[i]);
     }
     c->part_rects = rr;

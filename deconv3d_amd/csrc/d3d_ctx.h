@@ -34,6 +34,8 @@
 #include "d3d_kernels.h"
 #include "d3d_strip_order.h"
 #include "d3d_strips.h"
+#include "d3d_taps.h"
+#include "d3d_worklists.h"
 
 // The WIDE form of a small colour launch at 128 channels: eleven
 // streaming wavefronts per window instead of four -- one per window row of an 11 x 11 FSF
@@ -47,15 +49,7 @@ constexpr int MH_WIDE_NS = D3D_WIDE_NS;
 // k_mh_chain: at most this many threads per workgroup (three wavefronts per SIMD: 168
 // registers each, of which a thread's column of an 11-row window takes 88)
 constexpr int MH_CHAIN_NT = 768;
-// Lattice-row strips an unpartitioned context's chip-filling colour rows run in when option mh_strips
-// is 0 (1: none).  What profiles/sweep_strips_ab.txt justifies: two pass the project's rule, three gain
-// less, four lose.
-constexpr int MH_STRIPS_AUTO = 2;
-// How the strips of consecutive colour rows are ordered when option mh_strip_order is 0: 1 joined after
-// every colour row, 2 chained row to row by events with one join per sweep (d3d_strip_order.h).  What
-// profiles/sweep_chained_ab.txt justifies: chained passes the project's rule with two strips and with
-// three (which the z-blocked form loses with: the automatic count stays two), the joined form with none.
-constexpr int MH_STRIP_ORDER_AUTO = 2;
+// (MH_STRIPS_AUTO, MH_STRIP_ORDER_AUTO: d3d_worklists.h)
 
 namespace d3dh {
 // sets the thread-local message d3d_last_error() returns; returns `code`
@@ -146,36 +140,10 @@ struct d3d_ctx {
     DevBuf<unsigned> acc_map;  // [HW] accepted moves per spaxel since the last accepted_collect (MHArgs::acc_map)
     DevBuf<int4> spx;  // work lists per (part, colour): real spaxels first, then virtual ones
     std::vector<int> colour_real;  // fh*fw: number of real spaxels of each colour (all parts)
-    // A PART is a rectangle of spaxels updated together: sweep = for every phase, for
-    // every part of the phase, for every colour class, one launch (lib/run.py:553-560
-    // declares the scan order overridable).  An unpartitioned context has one part,
-    // the whole cube (a tile: its owned rectangle).  The DOMAIN of a part is the set
-    // of cells its windows touch.
-    struct Part {
-        int y0 = 0, y1 = 0, x0 = 0, x1 = 0;      // spaxels (local)
-        int dy0 = 0, dy1 = 0, dx0 = 0, dx1 = 0;  // domain (local)
-        int phase = 0;
-        int layers = 1;                          // pending layers in use
-        bool wide = false;                       // its colour launches take the wide form (MH_WIDE_NS)
-        bool small = false;                      // its colour launches do not fill the chip: k_mh_small
-        // k_mh_chain (whole sweeps of the part in one launch): slot grid, or chain = false
-        bool chain = false;
-        int chain_ns = 0, chain_sx0 = 0, n_sy = 0, n_sx = 0, K = 0;
-        int last_col = -1;                       // its last active colour
-        std::vector<int> off;                    // fh*fw + 1: start of each colour's list in spx
-        std::vector<int> real;                   // fh*fw: real spaxels of each colour
-        // Lattice-row strips (d3d_strips.h): with strips > 1 every colour's list is
-        // strip-major -- per strip its real spaxels, then its virtual positions -- and the strips of a
-        // colour row run on streams of their own (run_part)
-        int strips = 1;                          // 1: whole colour launches
-        std::vector<int> soff;                   // [fh*fw][strips + 1] start of each strip in the colour's list
-        std::vector<int> sreal;                  // [fh*fw][strips] real spaxels of each strip
-        // the strips chained from colour row to colour row (option mh_strip_order; order.S == 0: joined
-        // after every colour row): the schedule run_part executes, one step per active colour
-        d3d_strip_order::Schedule order;
-    };
+    // the parts of a sweep and their work lists (d3d_worklists.h decides them, build_colour_lists uploads)
+    using Part = d3d_worklists::Part;
     std::vector<Part> parts;
-    std::vector<int4> part_rects;  // as given to d3d_set_parts ({y0,y1,x0,x1}; .phase apart)
+    std::vector<d3d_worklists::Rect> part_rects;  // as given to d3d_set_parts (.phase apart)
     std::vector<int> part_phase;
     int n_phases = 1;
     int pend_part = -1;            // part the pending layers belong to
@@ -602,8 +570,18 @@ int noise_draw(d3d_ctx *c, int64_t rs, hipEvent_t *ev = nullptr);
 // c->post.n + 1 of the four accumulators
 int pred_sample(d3d_ctx *c);
 
-// ---- d3d_sweep.hip: local colour residues of colour class `col` (a tile's origin shifts them)
-void colour_residue(const d3d_ctx *c, int col, int *cy, int *cx);
+// ---- d3d_api.hip: what the work lists and their decisions are a function of (d3d_worklists.h); valid
+// while the context's mask and part rectangles stay as they are
+d3d_worklists::Input worklist_input(const d3d_ctx *c);
+// The context is cut up as far as the SWEEP's kernels go (run_part, d3d_mh_layers): a tile, or more
+// than one part.  Not d3d_worklists::partitioned_lists, which also counts a single given part
+// rectangle: such a context gets no strips and maybe the wide form from the lists, and runs the
+// unpartitioned kernels here.  Unifying the two would change which kernel it runs.
+inline bool partitioned_sweep(const d3d_ctx *c) { return c->tiled || c->parts.size() > 1; }
+// local colour residues of colour class `col` (a tile's origin shifts them)
+inline void colour_residue(const d3d_ctx *c, int col, int *cy, int *cx) {
+    d3d_worklists::local_residue(c->fh, c->fw, c->gy0, c->gx0, col, cy, cx);
+}
 
 // ---- d3d_mh.hip: the MH-within-Gibbs kernels ---------------------------------------------
 void pend_clear(d3d_ctx *c);

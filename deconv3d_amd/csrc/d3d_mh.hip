@@ -332,12 +332,8 @@ int launch_mh_ws_um(d3d_ctx *c, const d3d::MHArgs &P, unsigned grid, uint32_t sw
 
 // k_mh_small (d3d_mh_small.h): colour launches that do not fill the chip, one pending layer.
 // 256 streaming threads, or -- `wide`, 128 channels in a partitioned context -- 704.
-bool mh_small_usable(const d3d_ctx *c) {
-    // thread t <-> channel t in the tail; window rows / columns as bits of a 32-bit mask;
-    // 32-bit byte offsets into the residual
-    return c->mh_small && c->mh_props && c->mh_defer == 1 && !c->mh_zb && !c->deep && c->Dp <= 256 &&
-           c->fh <= 31 && c->fw <= 31 && (double)c->cube_elems * 8.0 < 4294967296.0;
-}
+// (the conditions: d3d_worklists.h, which decides Part::small with them)
+bool mh_small_usable(const d3d_ctx *c) { return d3d_worklists::small_usable(worklist_input(c)); }
 
 int mh_ptab_row(const d3d_ctx *c, int ly, int lx, int layer) {
     if (layer >= c->lay_n) return c->fh * c->fw;  // nothing pending there
@@ -350,18 +346,7 @@ int mh_ptab_row(const d3d_ctx *c, int ly, int lx, int layer) {
 }
 
 bool mh_part_uses_tables(const d3d_ctx *c, const d3d_ctx::Part &pt) {
-    if (!mh_small_usable(c)) return false;
-    if (pt.small) return true;
-#ifdef D3D_EXPERIMENTS
-    // the chip-filling form (option mh_small = 2): one or two pending layers, 256 streaming
-    // threads.  Bit-identical to k_mh_ws and measured SLOWER than it -- 43.7 against 40.6 us per
-    // launch at 300x300x128, 79.6 against 76.8 at 256 channels, 27.7 against 26.5 at 64
-    // (profiles/r04_table_kernel_full.txt): a launch that fills the chip is bound by HBM, not by
-    // the instruction issue the tables save, and the tables themselves are 3 % more traffic.
-    return c->mh_small == 2 && pt.layers <= 2 && !pt.wide;
-#else
-    return false;
-#endif
+    return d3d_worklists::part_uses_tables(worklist_input(c), pt);
 }
 
 // The relative position tables of k_mh_small (d3d_mh_small.h: MHPos), once per set of taps.

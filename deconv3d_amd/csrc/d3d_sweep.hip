@@ -6,11 +6,6 @@
 
 using namespace d3dh;
 
-void d3dh::colour_residue(const d3d_ctx *c, int col, int *cy, int *cx) {
-    *cy = ((col / c->fw - c->gy0) % c->fh + c->fh) % c->fh;
-    *cx = ((col % c->fw - c->gx0) % c->fw + c->fw) % c->fw;
-}
-
 namespace {
 
 // ---- asynchronous chain streaming ------------------------------------------------
@@ -305,7 +300,7 @@ int run_part(d3d_ctx *c, int pi, uint32_t sweep, const Batch *b = nullptr, bool 
     d3d_ctx *const *cs = b ? b->cs : self;
     // deferred write-back with pending layers: the wave-specialised kernel (D <= 256);
     // an unpartitioned context may also use the plain deferred kernel
-    const bool partitioned = c->tiled || c->parts.size() > 1;
+    const bool partitioned = partitioned_sweep(c);
     const bool deferred =
         c->mh_defer &&
         (!partitioned || (c->mh_defer == 1 && (c->Dp <= d3d::MH_WS_MAX_DP || c->mh_zb)));
@@ -526,9 +521,10 @@ int d3d_mh_sweeps(d3d_ctx *c, int n_sweeps, int first_sweep, int keep_one_in, do
                       c->cube_elems * sizeof(double) < (size_t(1) << 31);
     // One part, no halo plans, the chain form: several sweeps per launch -- up to the next
     // sweep that is saved or followed by a from-scratch residual.
+#ifdef D3D_EXPERIMENTS
     const bool chain_batches = !flow && !any_plan && c->parts.size() == 1 && c->parts[0].chain &&
                                c->mh_defer == 1 && n_phases == 1;
-    (void)chain_batches;
+#endif
     for (int s = first_sweep; s < first_sweep + n_sweeps; ++s) {
         const uint32_t rs = (uint32_t)s + c->sweep_origin;
 #ifdef D3D_EXPERIMENTS
